@@ -7,9 +7,12 @@ RGBA32F frames resident in HBM.  A "step" is one pass of the hot path over one b
 default 31 = a whole number of rounds of workgroups on the chip, see --frames below).
 N > 1: one process per GPU (torch.distributed, backend nccl = RCCL); single-frame NLM shards by
 frame with no data-path collective, so every rank filters its own batch ("weak" scaling) and
-value = all ranks' pixels / max-over-ranks time.  After the timed region (outside it) the run
-also measures, and reports under "also": bilateral r=8 in both layouts (BASELINE configs[1]), the
-temporal +-2 NLM with its RCCL halo exchange (configs[4]) and the PCIe-inclusive pipeline rate.
+value = all ranks' pixels / max-over-ranks time.  A plain run sets up, warms up, times the K steps
+and prints the line (roofline from the timed steps' own hipEvents).  With --full it then also
+measures, outside the timed region: the single-frame launch (config.single_frame_launch), under
+"also" bilateral r=8 in both layouts (BASELINE configs[1]), the temporal +-2 NLM with its RCCL
+halo exchange (configs[4]) and the PCIe-inclusive pipeline rate, and the cpu_baseline.
+--dump-outputs DIR writes what the last timed step computed (rank 0) as float32 .npy files.
 
 Prints ONE JSON line (rank 0).  The oracle is used only for the cpu_baseline leg.
 """
@@ -46,6 +49,7 @@ PEAK_FP32_TFLOPS = 157.3                  # MI355X_MICROARCH.md: fp32 vector = d
 PEAK_HBM_GBS = 8000.0
 SEQ_FRAMES = 64                           # BASELINE configs[4]: one 64-frame animation, temporal +-2
 WATCHDOG_S = 300.0                        # the side measurements after the timed region may take this long before the line is forced out
+DUMP_SAMPLE_PX = 1 << 20                  # --dump-outputs: pixels sampled over all of a step's frames (16 MiB), beside frame 0 in full
 
 
 def synth_frames(n, seed, device, shift=0):
@@ -178,6 +182,19 @@ class Timers:
         for p in self.t:
             self.lib.mid_timer_destroy(p)
         self.t = []
+
+
+def dump_outputs(outs, dirname, seed=0):
+    """--dump-outputs: the frames the timed path wrote in its last step, as a caller receives them (H x W x 4 float32 each),
+    so that two builds can be compared output for output.  outputs_frame0.npy = frame 0 in full (31.6 MiB); outputs_sample.npy =
+    (frames, n, 4): the same n seeded pixel positions of every frame, n = DUMP_SAMPLE_PX / frames (16 MiB in all)."""
+    os.makedirs(dirname, exist_ok=True)
+    torch.cuda.synchronize()
+    np.save(os.path.join(dirname, "outputs_frame0.npy"), outs[0].cpu().numpy())
+    n = min(NPIX, max(1, DUMP_SAMPLE_PX // len(outs)))
+    idx = torch.from_numpy(np.sort(np.random.default_rng(seed).choice(NPIX, size=n, replace=False))).to(outs[0].device)
+    sample = torch.stack([o.view(NPIX, 4).index_select(0, idx) for o in outs])
+    np.save(os.path.join(dirname, "outputs_sample.npy"), sample.cpu().numpy())
 
 
 def synth_c1(seed=1):
@@ -481,14 +498,21 @@ def main():
     ap.add_argument("--workload", choices=["nlm", "bilateral"], default="nlm",
                     help="what the timed region measures: nlm = BASELINE configs[2] (the north_star target, default); "
                          "bilateral = configs[1], r=8, linear-buffer layout, one launch per frame")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything else: the single-frame launch, the side measurements "
+                         "under `also` (other kernels, configurations, pipelines) and the cpu_baseline; off by default")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the cpu_baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: leave out the side measurements under `also`")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/*.npy (float32; rank 0; see dump_outputs)")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU rehearsal of the multi-rank control flow (gloo, no kernels, tiny frames); "
                          "marks its JSON dry_run=true -- never a measurement")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher above us: become one, BEFORE anything touches the GPU (see launch_ranks)
         sys.exit(launch_ranks(args.gpus))
@@ -587,6 +611,8 @@ def main():
     kernel_ms = timers.ms()
     timers.close()
     avg_launch_s = sum(kernel_ms) / len(kernel_ms) / 1e3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(outs, args.dump_outputs)          # before any side measurement reuses these buffers
 
     value = world * F * args.steps * NPIX / 1e6 / elapsed
     px_per_launch = F * NPIX // launches_per_step
@@ -626,9 +652,9 @@ def main():
 
     # ---- outside the timed region -------------------------------------------------------------
     # BASELINE configs[2] read literally is ONE 1920x1080 frame per launch; `value` is the F-frame launch (whole rounds of
-    # workgroups).  The single-frame figure goes into `config` next to it, measured in every run (also with --no-extras):
+    # workgroups).  The single-frame figure goes into `config` next to it, measured in every --full run (also with --no-extras):
     # median of three bursts of 10 launches, hipEvents on the launch stream.
-    if args.workload == "nlm":
+    if args.full and args.workload == "nlm":
         def burst(n=10):
             tm = Timers(mid, ctx, 1)
             tm.tick(0, stream)
@@ -684,7 +710,7 @@ def main():
         in_flight["extra"] = None
 
     XF = 16                             # frames of the 16-frame side measurements (bilateral batch, short pipelines), whatever --frames is
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         def time_gpu(fn, n=10):
             fn()
             torch.cuda.synchronize()
@@ -1148,7 +1174,7 @@ def main():
 
     res["also"] = also
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             res["cpu_baseline"] = cpu_baseline(args.workload)
         except Exception as e:  # the baseline is a reported extra; never fail the GPU measurement on it

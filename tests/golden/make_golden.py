@@ -34,6 +34,21 @@ def save(name, **arrays):
         if sorted(old.files) == sorted(arrays) and all(np.array_equal(old[k], np.asarray(v)) for k, v in arrays.items()):
             return
     np.savez_compressed(path, **arrays)
+    if os.path.getsize(path) > 1 << 20:
+        save_compact(path, arrays)
+
+
+def save_compact(path, arrays):
+    """The same .npz (np.load reads it as usual and returns equal arrays) for a fixture that deflate leaves above the 1 MiB a
+    committed file may have: LZMA members, and 8-bit images stored channel by channel (Fortran order), which compresses better."""
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, "w") as zf:
+        for k, v in arrays.items():
+            v = np.asarray(v)
+            b = io.BytesIO()
+            np.lib.format.write_array(b, np.asfortranarray(v) if v.dtype == np.uint8 and v.ndim == 3 else v, allow_pickle=False)
+            zf.writestr(zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0)), b.getvalue(), compress_type=zipfile.ZIP_LZMA)
 
 
 def main():
@@ -73,6 +88,21 @@ def main():
         out1 = oracle.ref_cpu_bilateral(img, R, threads=1)
         assert np.array_equal(out1, oracle.ref_cpu_bilateral(img, R, threads=8))
         save(f"ref_blue_const_{name}.npz", img=img, img_u8=u8, radius=R, out=out1)
+
+    # --- the cases tests/test_oracle.py runs against the loop itself where oracle/_ref is built -------------
+    # (same seeds and shapes as there): the loop's output at -O2 and at the reference's own flags, so that the
+    # tests hold the oracle against the reference everywhere else too
+    cases = {}
+    for (h, w), R in (((33, 41), 10), ((21, 25), 10), ((30, 19), 4), ((64, 64), 7)):
+        img = np.random.default_rng(R * 100 + h).random((h, w, 4), dtype=np.float32) * 1.5
+        cases[f"img_{h}x{w}_r{R}"] = img
+        cases[f"out_{h}x{w}_r{R}"] = oracle.ref_cpu_bilateral(img, R, 2)
+    img = np.random.default_rng(9).random((37, 53, 4), dtype=np.float32) * 2.0
+    cases["as_shipped_img"] = img
+    for R, th in ((10, 1), (4, 3)):
+        cases[f"as_shipped_O2_r{R}_t{th}"] = oracle.ref_cpu_bilateral(img, R, th)
+        cases[f"as_shipped_O0_r{R}_t{th}"] = oracle.ref_cpu_bilateral(img, R, th, as_shipped=True)
+    save("ref_cpu_bilateral_cases.npz", **cases)
 
     # --- BASELINE configs[0]: 512x512 8-bit PNG, CPU bilateral r=4 ------------------------------
     # Input as the reference decodes a PNG for the CPU path (c * (1/255), :1804-1807), the loop's float output

@@ -131,8 +131,8 @@ def test_bench_stdout_is_exactly_one_json_line_with_the_native_rccl_extra(tmp_pa
     C-ABI, which makes RCCL print its version banner on stdout): stdout must still hold the JSON line and nothing else,
     and the native path must report outputs bit-identical to the plain launch."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--frames", "2", "--no-cpu-baseline"],
-                       capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--frames", "2", "--full",
+                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = r.stdout.strip().splitlines()
     assert len(lines) == 1 and lines[0].startswith("{"), r.stdout[:2000]
@@ -172,7 +172,7 @@ def test_bench_watchdog_prints_the_headline_names_the_hung_extra_and_exits_nonze
         "import image_denoising_filter_amd as mid\n"
         "bench.WATCHDOG_S = 25\n"
         "mid.Context.bilateral_batch_dev = lambda *a, **k: time.sleep(3600)\n"
-        "sys.argv = ['bench.py', '--steps', '2', '--warmup', '1', '--frames', '2', '--no-cpu-baseline']\n"
+        "sys.argv = ['bench.py', '--steps', '2', '--warmup', '1', '--frames', '2', '--full', '--no-cpu-baseline']\n"
         "bench.main()\n")
     r = subprocess.run([sys.executable, str(wrapper)], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 3, (r.returncode, r.stderr[-2000:])

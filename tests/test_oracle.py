@@ -1,7 +1,8 @@
 """CPU suite, part 1: the oracle itself.
 
  - orc_cpu_bilateral is pinned against fixtures produced by the reference's own CPU loop
-   (tests/golden/ref_cpu_bilateral_*.npz) and, when oracle/_ref is built, against that loop live;
+   (tests/golden/ref_cpu_bilateral_*.npz, among them the recorded cases of the "live" tests) and, when oracle/_ref is
+   built, against that loop live;
  - the shader restatements are "parity unpinned" by the reference (it has no tests/fixtures and
    its GLSL cannot run here); they are checked from a second direction (float64 NumPy
    restatement of the formulas) and through properties the filters must satisfy.
@@ -27,23 +28,39 @@ def test_cpu_bilateral_matches_reference_golden(name):
         assert np.array_equal(out, g["out"]), "oracle a7 must be bit-exact with the reference loop"
 
 
-@pytest.mark.skipif(not oracle.have_ref(), reason="oracle/_ref not built (no /root/reference on this box)")
+def _recorded(key):
+    """The reference loop's output for a case below, recorded from oracle/_ref by tests/golden/make_golden.py: where _ref is not
+    built (it needs the reference's sources) the tests hold the oracle against this record, where it is, against the loop live too."""
+    return np.load(os.path.join(GOLDEN, "ref_cpu_bilateral_cases.npz"))[key]
+
+
 @pytest.mark.parametrize("shape,R", [((33, 41), 10), ((21, 25), 10), ((30, 19), 4), ((64, 64), 7)])
 def test_cpu_bilateral_matches_reference_live(shape, R):
     rng = np.random.default_rng(R * 100 + shape[0])
     img = rng.random((*shape, 4), dtype=np.float32) * 1.5
-    assert np.array_equal(oracle.cpu_bilateral(img, R, 10.0, 0.2, True, 2), oracle.ref_cpu_bilateral(img, R, 2))
+    key = f"{shape[0]}x{shape[1]}_r{R}"
+    assert np.array_equal(_recorded("img_" + key), img), "the recorded case must be this case"
+    want = _recorded("out_" + key)
+    if oracle.have_ref():
+        assert np.array_equal(oracle.ref_cpu_bilateral(img, R, 2), want)
+    assert np.array_equal(oracle.cpu_bilateral(img, R, 10.0, 0.2, True, 2), want)
 
 
-@pytest.mark.skipif(not (oracle.have_ref() and oracle.have_ref_as_shipped()), reason="oracle/_ref not built (no /root/reference on this box)")
 def test_reference_loop_gives_the_same_bits_at_its_own_compile_flags():
     """The reference ships "-fopenmp -g" with no optimisation level (CMakeLists.txt:31); the checker and the timed baseline use -O2.
     The loop's arithmetic is libm calls in double, stored to float: the two builds agree bit for bit, so the -O2 timing is the
     same computation (bench.py quotes the -O0 rate once beside it)."""
     rng = np.random.default_rng(9)
     img = rng.random((37, 53, 4), dtype=np.float32) * 2.0
+    assert np.array_equal(_recorded("as_shipped_img"), img), "the recorded case must be this case"
+    live = oracle.have_ref() and oracle.have_ref_as_shipped()
     for R, th in ((10, 1), (4, 3)):
-        assert np.array_equal(oracle.ref_cpu_bilateral(img, R, th), oracle.ref_cpu_bilateral(img, R, th, as_shipped=True))
+        o2, o0 = _recorded(f"as_shipped_O2_r{R}_t{th}"), _recorded(f"as_shipped_O0_r{R}_t{th}")
+        if live:
+            assert np.array_equal(oracle.ref_cpu_bilateral(img, R, th), o2)
+            assert np.array_equal(oracle.ref_cpu_bilateral(img, R, th, as_shipped=True), o0)
+        assert np.array_equal(o2, o0)
+        assert np.array_equal(oracle.cpu_bilateral(img, R, 10.0, 0.2, True, th), o2)
 
 
 def test_cpu_bilateral_reference_quirks():

@@ -12,7 +12,7 @@ cd /tmp && export TMPDIR=/tmp
 # sha256 of the bench kernel's code in the library that is about to be profiled: bench.py compares it with the library it
 # loads before it reads these counters back (image_denoising_filter_amd/_codeobj.py; pure Python, no GPU)
 python3 $R/image_denoising_filter_amd/_codeobj.py $R/image_denoising_filter_amd/libmi_denoise.so > $OUT/code_fingerprint.json || { echo "fingerprint failed"; exit 1; }
-BENCH="python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline"
+BENCH="python3 $R/bench.py --steps 5 --warmup 2 --full --no-cpu-baseline"
 [ "$2" = "trace_main_only" ] || rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $BENCH > $OUT/trace.log 2>&1 || { echo "trace failed"; tail -5 $OUT/trace.log; exit 1; }
 BENCH2="$BENCH --no-extras"
 # the timed loop alone (no side measurements): the dominant kernel's average in this table is the figure to hold against roofline.avg_launch_ms

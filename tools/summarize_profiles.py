@@ -123,7 +123,7 @@ if dom:
              "algorithmic_bytes_per_launch": int(k[1]) // 256 // (34 * 34) * 1920 * 1080 * 32,
              "date": __import__("time").strftime("%Y-%m-%d", __import__("time").gmtime()),
              **({"kernel_symbol": FP["kernel_symbol"], "kernel_code_sha256": FP["kernel_code_sha256"]} if FP else {}),
-             "command": "rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE (one pass each) -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extras"}
+             "command": "rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE (one pass each) -- python3 bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-extras"}
         json.dump(t, open(os.path.join(dst, f"{tag}_traffic.json"), "w"), indent=1)
         print(json.dumps(t, indent=1))
 # ---- traffic of the bilateral r=8 linear launch (`bench.py --workload bilateral`; north_star: "achieved HBM GB/s (bilateral)") ----
@@ -264,7 +264,7 @@ def pick(sub, grid=None, largest=False):
 
 util = {"date": __import__("time").strftime("%Y-%m-%d", __import__("time").gmtime()),
         "commands": "tools/run_profiles.sh " + tag + ": rocprofv3 --pmc passes (SQ pass 1, SQ pass 2 + GRBM_GUI_ACTIVE; each its own run, never with a trace "
-                    "domain) of `bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extras` (NLM bench kernel) and of tools/profile_kernels.py (the others)",
+                    "domain) of `bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-extras` (NLM bench kernel) and of tools/profile_kernels.py (the others)",
         "peaks": {"simds": N_SIMD, "cus": N_CU, "note": "utilisations are fractions of SIMD issue cycles / CU LDS cycles of the launch itself (cycles from "
                                                           "GRBM_GUI_ACTIVE, i.e. at the clock the chip actually held)"},
         "kernels": {}}
