@@ -3,6 +3,9 @@
 // (src/vk_utils.cpp:13-305, src/main.cpp:247-401) with plain HIP: a context is a device
 // plus its four streams (compute, a second compute stream for the frame pipeline, upload, download).
 #include "common.hpp"
+#include <algorithm>
+#include <new>
+#include <utility>
 
 namespace mid {
 
@@ -15,6 +18,31 @@ int set_error(int code, const char *fmt, ...)
     vsnprintf(g_err, sizeof g_err, fmt, ap);
     va_end(ap);
     return code;
+}
+
+int check_no_alias(const char *who, const char *input_is, const void *const *in, int n_in, const void *const *out, int n_out)
+{
+    int at_in = n_out, at_twice = n_out;        // first t whose out[t] is an input / repeats an earlier output
+    try {
+        std::vector<const void *> ins(in, in + n_in);
+        std::sort(ins.begin(), ins.end());
+        std::vector<std::pair<const void *, int>> outs;
+        outs.reserve(n_out);
+        for (int t = 0; t < n_out; ++t) {
+            if (!out[t]) continue;
+            if (at_in == n_out && std::binary_search(ins.begin(), ins.end(), out[t])) at_in = t;
+            outs.push_back({out[t], t});
+        }
+        std::sort(outs.begin(), outs.end());  // equal pointers adjacent, in index order: the second of a pair repeats the first
+        for (size_t i = 1; i < outs.size(); ++i)
+            if (outs[i].first == outs[i - 1].first && outs[i].second < at_twice) at_twice = outs[i].second;
+    } catch (const std::bad_alloc &) {
+        return set_error(MID_ERR_INVALID, "%s: no host memory for the alias check of %d outputs", who, n_out);
+    }
+    if (at_in < n_out && at_in <= at_twice)
+        return set_error(MID_ERR_INVALID, "%s: out[%d] is also %s (in-place / aliased filtering is not supported)", who, at_in, input_is);
+    if (at_twice < n_out) return set_error(MID_ERR_INVALID, "%s: out[%d] appears twice", who, at_twice);
+    return MID_OK;
 }
 
 Bind::Bind(mid_ctx *ctx, void *stream) : rc(MID_OK), s(nullptr)

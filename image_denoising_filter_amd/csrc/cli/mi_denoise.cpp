@@ -506,7 +506,7 @@ public:
         for (int g = 0; g < G; ++g)
             workers.emplace_back([&, g] {
                 try {
-                    const int q = n / G, r = n % G, start = g * q + std::min(g, r), count = q + (g < r ? 1 : 0);
+                    int start = 0, count = 0; MID_CHECK(mid_shard_block(n, G, g, &start, &count));     // this device's frames (cannot fail: g < G)
                     if (opt.halo_rccl) {
                         // GPU-resident variant: the block is uploaded once and stays in HBM; the k frames on either side come
                         // from the neighbouring devices over xGMI (ncclSend/ncclRecv, one group) while the interior frames are

@@ -68,6 +68,12 @@ int set_error(int code, const char *fmt, ...);
         if (!(cond)) return mid::set_error(MID_ERR_INVALID, __VA_ARGS__);               \
     } while (0)
 
+// The outputs of one launch are written while every workgroup of it still reads its inputs, so no output may be one of the
+// call's inputs nor be given twice.  Reports the first out[t] (t ascending; an input before a repeat) as MID_ERR_INVALID:
+// "<who>: out[t] is also <input_is> (...)" / "<who>: out[t] appears twice".  NULL outputs are skipped (the caller reports
+// them).  Sorted copies, no hash sets; a failed allocation is an error code too, never an exception through the C-ABI.
+int check_no_alias(const char *who, const char *input_is, const void *const *in, int n_in, const void *const *out, int n_out);
+
 // Binds the calling thread to the context's device and resolves the stream argument.
 struct Bind {
     int rc;

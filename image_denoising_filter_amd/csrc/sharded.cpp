@@ -25,9 +25,8 @@
 // GPU_MAX_HW_QUEUES=8 in the environment).  The lowest level is the library's alone: two boundary streams, two queues,
 // whatever the application created; and workgroups of that level are dispatched where no interior workgroup waits, which
 // is exactly the tail.  (ONE lowest-priority stream for both edges: 19.2 ms -- the second edge launch starts when the first
-// has drained and pays a tail of its own.)  The caller's stream joins both at the end.  The launch plan (which outputs are interior, which frame table each launch sees) is the one
-// image_denoising_filter_amd/sharding.py::block_launch_plan states and the gloo tests pin; mid_shard_* expose it as pure
-// host functions so that the C++ and Python statements are tested against each other on the CPU.
+// has drained and pays a tail of its own.)  The caller's stream joins both at the end.  The plan -- partition, halo exchange,
+// launches -- is stated here only; mid_shard_* expose it (sharding.py wraps them, tests/golden/shard_plans.json pins them).
 //
 // RCCL is bound at RUN time (dlopen of librccl.so.1 on the first mid_comm_* call): the library itself has no link-time
 // dependency on it, single-GPU users never load it, and inside a PyTorch process the dlopen resolves to the copy torch
@@ -172,7 +171,7 @@ void halo_plan(int n, int world, int k, int rank, std::vector<Xfer> &recv, std::
 
 struct Launch { int interior, w_lo, w_hi, first, count, off; };
 
-// sharding.py::block_launch_plan, statement for statement
+// interior outputs (window inside the block, table = the block), then the <= 2k boundary outputs of each edge (tables with halo)
 void launch_plan(int n, int world, int k, int rank, std::vector<Launch> &plan)
 {
     plan.clear();
@@ -474,6 +473,7 @@ extern "C" int mid_nlm_temporal_sharded(mid_comm *c, const mid_nlm_params *p, co
     MID_REQUIRE(count == 0 || (block && out), "nlm_temporal_sharded: NULL table");
     MID_REQUIRE(p->width > 0 && p->height > 0 && (p->format == MID_FMT_RGBA32F || p->format == MID_FMT_RGBA8), "nlm_temporal_sharded: bad params");
     for (int i = 0; i < count; ++i) MID_REQUIRE(block[i] && out[i], "nlm_temporal_sharded: frame %d of the block is NULL", i);
+    if (int rc = check_no_alias("nlm_temporal_sharded", "a frame of the block", block, count, (const void *const *)out, count)) return rc;   // once, for all launches
     const size_t frame_bytes = (size_t)p->width * p->height * (p->format == MID_FMT_RGBA8 ? 4 : 16);
 
     std::vector<Xfer> rv, sd;
@@ -541,7 +541,7 @@ extern "C" int mid_nlm_temporal_sharded(mid_comm *c, const mid_nlm_params *p, co
             tbl[f - L.w_lo] = frame_ptr(f);
             MID_REQUIRE(tbl[f - L.w_lo], "nlm_temporal_sharded: frame %d is neither in the block nor in the halo (plan error)", f);
         }
-        return mid_nlm_temporal(c->ctx, p, tbl.data(), (int)tbl.size(), k, L.first, L.count, out + L.off, ls);
+        return nlm_temporal_out(c->ctx, p, tbl.data(), (int)tbl.size(), k, L.first, L.count, (void *const *)(out + L.off), 0, ls, 0);
     };
     // interior launches first, on the caller's stream ...
     for (const Launch &L : plan) {

@@ -9,54 +9,39 @@ nothing from other ranks (replicas).  Temporal NLM needs the k frames on either 
 ONE exchange step -- each rank sends its first k frames to rank r-1 and its last k to rank r+1
 (point-to-point over xGMI with backend "nccl" = RCCL; "gloo" in the CPU tests) -- and no other
 collective.  Sequence ends are clipped, not wrapped.
+
+The plan -- partition, halo exchange, launches -- is stated once, in csrc/sharded.cpp (mid_shard_*, the plan
+mid_nlm_temporal_sharded executes); partition / halo_plan / block_launch_plan give it the shapes this module's
+torch.distributed transport uses.
 """
 from typing import List, Sequence, Tuple
 
 import torch
 import torch.distributed as dist
 
+from .api import shard_block, shard_halo_plan, shard_launch_plan
+
 
 def partition(n_frames: int, world: int) -> List[Tuple[int, int]]:
-    """Contiguous (start, count) per rank; the first n_frames % world ranks get one extra frame."""
+    """Contiguous (start, count) per rank; the first n_frames % world ranks get one extra frame (mid_shard_block)."""
     if n_frames < 0 or world < 1:
         raise ValueError("bad partition request")
-    q, r = divmod(n_frames, world)
-    out, s = [], 0
-    for i in range(world):
-        c = q + (1 if i < r else 0)
-        out.append((s, c))
-        s += c
-    return out
+    return [shard_block(n_frames, world, r) for r in range(world)]
 
 
 def halo_plan(n_frames: int, world: int, k: int, rank: int):
-    """Which global frame indices this rank receives from / sends to which rank.
-    Returns (recv, send): lists of (peer_rank, [global frame ids]).  Handles blocks shorter than k
-    (a halo may then span several ranks) and empty blocks."""
-    parts = partition(n_frames, world)
-    owner = {}
-    for r, (s, c) in enumerate(parts):
-        for f in range(s, s + c):
-            owner[f] = r
+    """Which global frame indices this rank receives from / sends to which rank (mid_shard_halo_plan).
+    Returns (recv, send): lists of (peer_rank, [global frame ids]), sorted by peer, frames ascending.  Handles blocks
+    shorter than k (a halo may then span several ranks) and empty blocks."""
+    recv, send = shard_halo_plan(n_frames, world, k, rank)
+    return _by_peer(recv), _by_peer(send)
 
-    def needs(r):
-        s, c = parts[r]
-        if c == 0:
-            return []
-        lo, hi = max(0, s - k), min(n_frames - 1, s + c - 1 + k)
-        return [f for f in range(lo, hi + 1) if not (s <= f < s + c)]
 
-    recv = {}
-    for f in needs(rank):
-        recv.setdefault(owner[f], []).append(f)
-    send = {}
-    for r in range(world):
-        if r == rank:
-            continue
-        for f in needs(r):
-            if owner[f] == rank:
-                send.setdefault(r, []).append(f)
-    return sorted(recv.items()), sorted(send.items())
+def _by_peer(xfers):
+    groups = {}
+    for peer, f in xfers:
+        groups.setdefault(peer, []).append(f)
+    return sorted(groups.items())
 
 
 def exchange_halo(local: Sequence[torch.Tensor], n_frames: int, k: int, group=None):
@@ -195,27 +180,14 @@ def temporal_block_overlapped(launch, local: Sequence[torch.Tensor], n_frames: i
 
 
 def block_launch_plan(n_frames: int, world: int, k: int, rank: int):
-    """The launches one rank makes for its block, as pure data: a list of
+    """The launches one rank makes for its block (mid_shard_launch_plan), as pure data: a list of
     (phase, w_lo, w_hi, first, count, out_offset) where frames w_lo..w_hi (global ids) form the table handed to
     mid_nlm_temporal, outputs are table entries [first, first+count), stored at block-relative out_offset.
     phase "interior": every window t-k..t+k (clipped at the SEQUENCE ends only) lies inside the rank's own block,
     so the launch needs no halo frame and can run while the halo is in flight; the table is restricted to the
     block so that clipping at the block edge can never stand in for a missing halo frame.
     phase "boundary": the <= 2k outputs next to a neighbouring block; their tables include the halo frames."""
-    start, count = partition(n_frames, world)[rank]
-    if count == 0:
-        return []
-    lo_int = start if start == 0 else start + k
-    hi_int = start + count if start + count == n_frames else start + count - k      # exclusive
-    plan = []
-    if hi_int > lo_int:
-        w_lo, w_hi = max(start, lo_int - k), min(start + count - 1, hi_int - 1 + k)
-        plan.append(("interior", w_lo, w_hi, lo_int - w_lo, hi_int - lo_int, lo_int - start))
-    for a, b in ((start, min(lo_int, start + count)), (max(hi_int, lo_int), start + count)):
-        if b > a:
-            w_lo, w_hi = max(0, a - k), min(n_frames - 1, b - 1 + k)
-            plan.append(("boundary", w_lo, w_hi, a - w_lo, b - a, a - start))
-    return plan
+    return shard_launch_plan(n_frames, world, k, rank)
 
 
 def window_for_block(have, n_frames: int, k: int, start: int, count: int):

@@ -10,6 +10,8 @@ Two kinds of fixture, kept apart by file name:
                            freeze the restatement so that an accidental edit of oracle.c, or a
                            compiler/libm change, is detected.
 A fixture is data (seeded inputs, expected outputs); no reference source text is stored.
+
+shard_plans.json is not rewritten by the run above: see save_shard_plans.
 """
 import os
 import sys
@@ -141,5 +143,23 @@ def main():
     print("wrote", sorted(os.listdir(OUT)))
 
 
+def save_shard_plans():
+    """tests/golden/shard_plans.json: a PINNED RECORD of the frame-block shard plan (csrc/sharded.cpp, through the wrappers of
+    image_denoising_filter_amd/sharding.py) for every (n, world, k, rank) of tests/test_shard_native_plan.py's CASES, one row
+    per line: [n, world, k, rank, partition(n, world), halo_plan(n, world, k, rank), block_launch_plan(n, world, k, rank)].
+    First written while an independent Python statement of the plan still agreed with the C++ one.  Regenerate it only on a
+    DELIBERATE plan change, never to make a failing test pass:   python tests/golden/make_golden.py shard_plans"""
+    import json
+    from image_denoising_filter_amd import sharding
+    from test_shard_native_plan import CASES
+    rows = [[n, world, k, rank, sharding.partition(n, world), sharding.halo_plan(n, world, k, rank),
+             sharding.block_launch_plan(n, world, k, rank)] for n, world, k in CASES for rank in range(world)]
+    with open(os.path.join(OUT, "shard_plans.json"), "w") as f:
+        f.write("[\n" + ",\n".join(json.dumps(r, separators=(",", ":")) for r in rows) + "\n]\n")
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["shard_plans"]:
+        save_shard_plans()
+    else:
+        main()

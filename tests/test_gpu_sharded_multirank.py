@@ -112,6 +112,71 @@ def test_sharded_temporal_nlm_with_two_to_four_ranks_is_bit_identical_to_one_lau
     assert len(rep["cases"]) == 12
 
 
+_ALIAS_WORKER = r'''
+import json, sys, threading
+sys.path.insert(0, sys.argv[1])
+import numpy as np
+import image_denoising_filter_amd as mid
+
+CFG = dict(search=(-10, 11), patch=(-3, 4))
+world, n, k, h, w = 2, 16, 1, 70, 130
+# rank 0 owns frames 0..7: interior launch outputs 0..6 over table 0..7, boundary launch output 7 over table 6..8.
+# rank 1 owns frames 8..15: interior outputs 9..15 over table 8..15, boundary output 8 over table 7..9.
+# Each rank makes the output of its boundary launch a block frame that is NOT in that launch's table but IS read by the interior
+# launch on the other stream: both ranks must refuse at entry, before anything is queued or sent.
+ALIASED = {0: (7, 2), 1: (0, 5)}                       # rank -> (output index, block index it aliases)
+ctxs = [mid.Context(0) for _ in range(world)]
+comms = mid.comm_create_all(ctxs)
+rep, errs = {}, []
+
+def rank_main(r):
+    try:
+        c, comm = ctxs[r], comms[r]
+        start, count = mid.shard_block(n, world, r)
+        d_in = [c.upload(np.full((h, w, 4), 0.25 + 0.01 * (start + i), np.float32)) for i in range(count)]
+        d_out = [c.alloc(h * w * 16) for _ in range(count)]
+        o, b = ALIASED[r]
+        outs = [d.ptr for d in d_out]
+        outs[o] = d_in[b].ptr
+        try:
+            comm.nlm_temporal_sharded_dev([d.ptr for d in d_in], outs, w, h, n, k, 0.5, CFG["search"], CFG["patch"], mid.FMT_RGBA32F)
+            refused = "accepted"
+        except mid.MidError as e:
+            refused = str(e)
+        rep[str(r)] = {"refused": refused, "order": comm.last_issue_order(), "exchange": list(comm.last_exchange()[:2])}
+        comm.nlm_temporal_sharded_dev([d.ptr for d in d_in], [d.ptr for d in d_out], w, h, n, k, 0.5, CFG["search"], CFG["patch"], mid.FMT_RGBA32F)
+        c.sync()
+        rep[str(r)]["then"] = comm.last_issue_order()
+    except Exception as e:  # noqa: BLE001
+        errs.append(f"rank {r}: {e!r}")
+
+th = [threading.Thread(target=rank_main, args=(r,), daemon=True) for r in range(world)]
+for t in th: t.start()
+for t in th: t.join(timeout=120)
+assert not any(t.is_alive() for t in th), "a rank hangs"
+assert not errs, errs
+for cm in comms: cm.close()
+print("ALIAS " + json.dumps(rep), flush=True)
+'''
+
+
+def test_an_output_that_is_a_block_frame_outside_its_launch_is_refused_before_the_exchange(tmp_path):
+    """The alias check of mid_nlm_temporal_sharded covers the whole block, once, at entry: an output of one launch that is a block
+    frame only ANOTHER launch reads (the interior launch, on another stream) is refused -- a check per launch against that launch's
+    own table let it through.  Nothing is queued or sent (issue order empty, no bytes), and the same communicators then run a
+    valid call."""
+    script = tmp_path / "worker.py"
+    script.write_text(_ALIAS_WORKER)
+    r = subprocess.run([sys.executable, str(script), ROOT], env=_env(), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    rep = json.loads([l for l in r.stdout.splitlines() if l.startswith("ALIAS ")][0][6:])
+    for rank, o in (("0", 7), ("1", 0)):
+        x = rep[rank]
+        assert "error 1" in x["refused"] and f"out[{o}] is also a frame of the block" in x["refused"], x
+        assert x["order"] == "" and x["exchange"] == [0, 0], x
+        assert x["then"].startswith("XI") and "B" in x["then"], x
+
+
 @pytest.mark.parametrize("hdr,gpus,k", [(True, 3, 2), (False, 4, 1), (True, 2, 3)])
 def test_cli_animation_on_n_ranks_sharing_the_device_equals_the_host_halo_run(tmp_path, hdr, gpus, k):
     import image_denoising_filter_amd as mid

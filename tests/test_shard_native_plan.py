@@ -1,9 +1,13 @@
-"""CPU suite: the C++ side of the frame-block sharding (csrc/sharded.cpp) as pure data -- partition, halo exchange plan
-and launch plan through the C-ABI (mid_shard_*), held against the Python statements the gloo tests pin
-(image_denoising_filter_amd/sharding.py) and against the properties RCCL needs: between any two ranks the sends of one
-are, in order, the receives of the other (RCCL matches a pair's sends and receives in issue order), every frame a rank
-needs arrives exactly once, and the launches cover every output exactly once using only frames the rank then holds."""
+"""CPU suite: the frame-block sharding plan (csrc/sharded.cpp) as pure data -- partition, halo exchange plan and launch plan
+through the C-ABI (mid_shard_*) and through the Python wrappers the gloo tests pin (image_denoising_filter_amd/sharding.py),
+held against the pinned record tests/golden/shard_plans.json (tests/golden/make_golden.py::save_shard_plans), which was
+written while sharding.py still held an independent Python statement of the plan, and against the properties RCCL needs:
+between any two ranks the sends of one are, in order, the receives of the other (RCCL matches a pair's sends and receives in
+issue order), every frame a rank needs arrives exactly once, and the launches cover every output exactly once using only
+frames the rank then holds."""
 import itertools
+import json
+import os
 
 import pytest
 
@@ -12,25 +16,40 @@ from image_denoising_filter_amd import sharding
 
 CASES = [(n, w, k) for n in (1, 2, 3, 5, 8, 11, 16, 23, 64) for w in (1, 2, 3, 4, 8) for k in (0, 1, 2, 3, 5)]
 
+with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "shard_plans.json")) as _f:
+    # (n, world, k, rank) -> (partition, (recv, send) grouped by peer, launch plan), in the shapes sharding.py returns
+    RECORDED = {tuple(r[:4]): ([tuple(p) for p in r[4]],
+                               tuple([(peer, ids) for peer, ids in side] for side in r[5]),
+                               [tuple(row) for row in r[6]]) for r in json.load(_f)}
+
+
+def test_the_record_covers_every_case():
+    assert sorted(RECORDED) == sorted((n, w, k, r) for n, w, k in CASES for r in range(w))
+
 
 def test_partition_matches_python_and_covers_the_sequence():
     for n, world in itertools.product(range(0, 70), (1, 2, 3, 4, 5, 8, 16)):
         parts = [mid.shard_block(n, world, r) for r in range(world)]
         assert parts == sharding.partition(n, world)
-        assert sum(c for _, c in parts) == n and all(parts[i][0] + parts[i][1] == parts[i + 1][0] for i in range(world - 1))
+        assert [c for _, c in parts] == [n // world + (r < n % world) for r in range(world)]   # the first n % world ranks get one more
+        assert parts[0][0] == 0 and all(parts[i][0] + parts[i][1] == parts[i + 1][0] for i in range(world - 1))
+        assert sum(c for _, c in parts) == n
+    with pytest.raises(ValueError):
+        sharding.partition(4, 0)
+    with pytest.raises(ValueError):
+        sharding.partition(-1, 2)
 
 
 @pytest.mark.parametrize("n,world,k", CASES)
 def test_halo_plan_matches_python_and_pairs_up_in_issue_order(n, world, k):
     plans = [mid.shard_halo_plan(n, world, k, r) for r in range(world)]
-    parts = sharding.partition(n, world)
+    parts = [mid.shard_block(n, world, r) for r in range(world)]
     for r, (recv, send) in enumerate(plans):
-        if world > 1 and k > 0 and parts[r][1] > 0:
-            precv, psend = sharding.halo_plan(n, world, k, r)
-            assert sorted(recv) == sorted((p, f) for p, ids in precv for f in ids)
-            assert sorted(send) == sorted((p, f) for p, ids in psend for f in ids)
-        else:
-            assert recv == [] and (send == [] or parts[r][1] > 0)
+        part, halo, _ = RECORDED[(n, world, k, r)]
+        assert parts == part == sharding.partition(n, world)
+        assert sharding.halo_plan(n, world, k, r) == halo
+        assert recv == [(p, f) for p, ids in halo[0] for f in ids]     # the C-ABI's flat lists, in issue order
+        assert send == [(p, f) for p, ids in halo[1] for f in ids]
         s, c = parts[r]
         need = [f for f in range(max(0, s - k), min(n - 1, s + c - 1 + k) + 1) if not s <= f < s + c] if c and world > 1 else []
         assert [f for _, f in recv] == need                      # every needed frame exactly once, ascending
@@ -46,7 +65,7 @@ def test_halo_plan_matches_python_and_pairs_up_in_issue_order(n, world, k):
 def test_launch_plan_matches_python_and_only_touches_resident_frames(n, world, k):
     for r in range(world):
         plan = mid.shard_launch_plan(n, world, k, r)
-        assert plan == [tuple(x) for x in sharding.block_launch_plan(n, world, k, r)]
+        assert plan == RECORDED[(n, world, k, r)][2] == sharding.block_launch_plan(n, world, k, r)
         s, c = mid.shard_block(n, world, r)
         held_after_halo = set(range(s, s + c)) | {f for _, f in mid.shard_halo_plan(n, world, k, r)[0]}
         covered = []
