@@ -83,6 +83,8 @@ _SIGNATURES = {
     "mid_normalize": (ctypes.c_int, [_P, ctypes.POINTER(NormalizeParams), _P, _P, _P]),
     "mid_unpack_u8": (ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_int, _P, _P]),
     "mid_pack_u8": (ctypes.c_int, [_P, _P, ctypes.c_size_t, _P, _P]),
+    "mid_unpack_f16": (ctypes.c_int, [_P, _P, ctypes.c_size_t, _P, _P]),
+    "mid_pack_f16": (ctypes.c_int, [_P, _P, ctypes.c_size_t, _P, _P]),
     "mid_sequence_nlm": (ctypes.c_int, [_P, ctypes.POINTER(NlmParams), c_void_pp, ctypes.c_int, ctypes.c_int,
                                         c_void_pp, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
     "mid_sequence_nlm_range": (ctypes.c_int, [_P, ctypes.POINTER(NlmParams), c_void_pp, ctypes.c_int, ctypes.c_int,
@@ -91,6 +93,9 @@ _SIGNATURES = {
     "mid_sequence_nlm_range_u8": (ctypes.c_int, [_P, ctypes.POINTER(NlmParams), c_void_pp, ctypes.c_int, ctypes.c_int,
                                                  ctypes.c_int, ctypes.c_int, c_void_pp, ctypes.c_int,
                                                  ctypes.POINTER(ctypes.c_float)]),
+    "mid_sequence_nlm_range_f16": (ctypes.c_int, [_P, ctypes.POINTER(NlmParams), c_void_pp, ctypes.c_int, ctypes.c_int,
+                                                  ctypes.c_int, ctypes.c_int, c_void_pp, ctypes.c_int,
+                                                  ctypes.POINTER(ctypes.c_float)]),
     "mid_nlm_multiframe": (ctypes.c_int, [_P, ctypes.POINTER(NlmParams), _P, c_void_pp, ctypes.c_int, _P, ctypes.c_int,
                                           ctypes.POINTER(ctypes.c_float)]),
     "mid_pipe_last_timeline": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int),
@@ -124,6 +129,7 @@ _SIGNATURES = {
     "mid_image_free": (None, [ctypes.POINTER(Image)]),
     "mid_image_load_pinned": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.POINTER(Image)]),
     "mid_image_free_pinned": (ctypes.c_int, [_P, ctypes.POINTER(Image)]),
+    "mid_image_load_f16": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.POINTER(Image)]),
     "mid_image_save": (ctypes.c_int, [ctypes.c_char_p, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     "mid_image_threads": (ctypes.c_int, [ctypes.c_int]),
     "mid_record_begin": (ctypes.c_int, [_P, _P]),

@@ -6,7 +6,8 @@ offers the same operators with the same argument meaning; every call goes throug
 libmi_denoise.so (ctypes) -- there is no NumPy/PyTorch compute path here, and a missing
 library or GPU is an error, not a fallback.
 
-NumPy arrays are (h, w, 4): float32 = RGBA32F (.exr path), uint8 = RGBA8 (.png path).
+NumPy arrays are (h, w, 4): float32 = RGBA32F (.exr path), uint8 = RGBA8 (.png path), float16 = RGBA16F (half-float
+frames: EXR HALF channels, a renderer's RGBA16F buffers).  Filters read RGBA16F exactly as the float32 frame it widens to.
 WeightInfo buffers are float32 (h, w, 8): [wc.r, wc.g, wc.b, wc.a, normWeight, pad, pad, pad].
 """
 import ctypes
@@ -16,7 +17,7 @@ import numpy as np
 
 from ._lib import BilateralParams, Image, NlmParams, NormalizeParams, c_void_pp, lib
 
-FMT_RGBA32F, FMT_RGBA8 = 0, 1
+FMT_RGBA32F, FMT_RGBA8, FMT_RGBA16F = 0, 1, 2
 LAYOUT_TEXTURE, LAYOUT_LINEAR = 0, 1
 
 # nonlocal.comp:5-6 as shipped, and the 21x21 / 7x7 benchmark configuration (half-open ranges)
@@ -36,23 +37,30 @@ def _check(code, where):
         raise MidError(code, where)
 
 
-def load_image(path):
+def load_image(path, dtype=None):
     """LoadImages (src/main.cpp:145-229): '.exr' -> float32 (h,w,4), anything else as PNG -> uint8 (h,w,4).
-    Host-only (no GPU)."""
+    dtype=np.float16: an .exr as RGBA16F (mid_image_load_f16: HALF channels bit for bit, FLOAT / UINT rounded to nearest
+    even); PNG files are refused.  Host-only (no GPU)."""
     img = Image()
-    _check(lib.mid_image_load(str(path).encode(), ctypes.byref(img)), "mid_image_load")
+    half = dtype is not None and np.dtype(dtype) == np.float16
+    if dtype is not None and not half:
+        raise TypeError(f"load_image: dtype must be None or float16, got {dtype}")
+    if half:
+        _check(lib.mid_image_load_f16(None, str(path).encode(), ctypes.byref(img)), "mid_image_load_f16")
+    else:
+        _check(lib.mid_image_load(str(path).encode(), ctypes.byref(img)), "mid_image_load")
     try:
-        dt = np.float32 if img.format == FMT_RGBA32F else np.uint8
+        dt = {FMT_RGBA32F: np.float32, FMT_RGBA8: np.uint8, FMT_RGBA16F: np.float16}[img.format]
         n = img.width * img.height * 4
-        arr = np.ctypeslib.as_array(ctypes.cast(img.data, ctypes.POINTER(ctypes.c_float if dt == np.float32 else ctypes.c_uint8)),
-                                    shape=(n,)).reshape(img.height, img.width, 4).copy()
+        raw = (ctypes.c_uint8 * (n * np.dtype(dt).itemsize)).from_address(img.data)
+        arr = np.frombuffer(raw, dtype=dt).reshape(img.height, img.width, 4).copy()
     finally:
         lib.mid_image_free(ctypes.byref(img))
     return arr
 
 
 def save_image(path, arr):
-    """SaveEXR(rgba,w,h,4,0) for float32, lodepng::encode for uint8 (src/main.cpp:1699,1717)."""
+    """SaveEXR(rgba,w,h,4,0) for float32, lodepng::encode for uint8 (src/main.cpp:1699,1717); float16 -> EXR with HALF channels."""
     arr = _img(arr)
     _check(lib.mid_image_save(str(path).encode(), arr.ctypes.data, arr.shape[1], arr.shape[0], _fmt_of(arr)),
            "mid_image_save")
@@ -86,7 +94,9 @@ def _fmt_of(a):
         return FMT_RGBA32F
     if a.dtype == np.uint8:
         return FMT_RGBA8
-    raise TypeError(f"image dtype must be float32 or uint8, got {a.dtype}")
+    if a.dtype == np.float16:
+        return FMT_RGBA16F
+    raise TypeError(f"image dtype must be float32, uint8 or float16, got {a.dtype}")
 
 
 def _img(a):
@@ -297,6 +307,22 @@ class Context:
         _check(lib.mid_pack_u8(self.handle, d_in.ptr, n, d_out.ptr, None), "mid_pack_u8")
         return self.download(d_out, f32.shape, np.uint8)
 
+    def unpack_f16(self, f16):
+        """binary16 -> float32, exact (mid_unpack_f16)."""
+        f16 = np.ascontiguousarray(f16, dtype=np.float16)
+        n = f16.size
+        d_in, d_out = self.upload(f16), self.alloc(max(n * 4, 16))
+        _check(lib.mid_unpack_f16(self.handle, d_in.ptr, n, d_out.ptr, None), "mid_unpack_f16")
+        return self.download(d_out, f16.shape, np.float32)
+
+    def pack_f16(self, f32):
+        """float32 -> binary16, round to nearest even: the bits of np.float16(f32) (mid_pack_f16)."""
+        f32 = np.ascontiguousarray(f32, dtype=np.float32)
+        n = f32.size
+        d_in, d_out = self.upload(f32), self.alloc(max(n * 2, 16))
+        _check(lib.mid_pack_f16(self.handle, d_in.ptr, n, d_out.ptr, None), "mid_pack_f16")
+        return self.download(d_out, f32.shape, np.float16)
+
     def nlm_multiframe(self, target, frames, overlap=True, hparam=0.5, search=(-7, 7), patch=(-3, 3)):
         """The reference's multi-frame mode: one target, neighbour frames streamed (mid_nlm_multiframe)."""
         target = _img(target)
@@ -311,16 +337,19 @@ class Context:
         return out, tuple(t)
 
     def sequence_nlm_pinned(self, hin, hout, w, h, fmt, k=2, first=0, count=None, overlap=True, hparam=0.5,
-                            search=(-7, 7), patch=(-3, 3), out_u8=False):
-        """mid_sequence_nlm_range[_u8] on host pointers the caller already holds (PinnedFrames.ptrs): nothing but the C call,
-        so a clock around it measures what a C caller sees.  Returns (wall_ms of the whole call, kernel_ms, copy_ms)."""
+                            search=(-7, 7), patch=(-3, 3), out_u8=False, out_dtype=None):
+        """mid_sequence_nlm_range[_u8|_f16] on host pointers the caller already holds (PinnedFrames.ptrs): nothing but the C call,
+        so a clock around it measures what a C caller sees.  out_dtype=np.float16 selects the RGBA16F outputs.
+        Returns (wall_ms of the whole call, kernel_ms, copy_ms)."""
         n = len(hin)
         count = n - first if count is None else count
         if len(hout) < count:
             raise ValueError(f"{count} outputs asked for, {len(hout)} output buffers given")
         prm = NlmParams(w, h, hparam, search[0], search[1], patch[0], patch[1], fmt)
         t = (ctypes.c_float * 3)()
-        entry = lib.mid_sequence_nlm_range_u8 if out_u8 else lib.mid_sequence_nlm_range
+        out_dtype = _out_dtype(out_u8, out_dtype)
+        entry = {np.dtype(np.uint8): lib.mid_sequence_nlm_range_u8, np.dtype(np.float16): lib.mid_sequence_nlm_range_f16,
+                 np.dtype(np.float32): lib.mid_sequence_nlm_range}[out_dtype]
         _check(entry(self.handle, ctypes.byref(prm), (ctypes.c_void_p * n)(*hin), n, k, first, count,
                      (ctypes.c_void_p * count)(*hout[:count]), 1 if overlap else 0, t), "mid_sequence_nlm_range")
         return tuple(t)
@@ -337,9 +366,11 @@ class Context:
                 [(fo.value + j, out[4 * j], out[4 * j + 1], out[4 * j + 2], out[4 * j + 3]) for j in range(no.value)])
 
     def sequence_nlm(self, frames, k=2, overlap=True, hparam=0.5, search=(-7, 7), patch=(-3, 3), pinned=True,
-                     first=0, count=None, out_u8=False, pinned_out=True):
-        """Host frames in, host frames out through the overlapped pipeline (mid_sequence_nlm_range[_u8]).
+                     first=0, count=None, out_u8=False, pinned_out=True, out_dtype=None):
+        """Host frames in, host frames out through the overlapped pipeline (mid_sequence_nlm_range[_u8|_f16]).
         out_u8: outputs converted to RGBA8 on the device like the reference's read-back (src/main.cpp:97-103).
+        out_dtype=np.float16: RGBA16F outputs, rounded to nearest even in the kernel's epilogue (the bits of np.float16 of the
+        float32 outputs).  Input frames may be float32, uint8 or float16.
         pinned / pinned_out = False: the NumPy arrays themselves (pageable memory) are the sources / destinations, which
         the library moves through its bounce buffers (csrc/hostcopy.cpp).
         Returns (outputs for frames first..first+count-1, (wall_ms, kernel_ms, copy_ms))."""
@@ -349,20 +380,32 @@ class Context:
         if not (0 <= first and count >= 1 and first + count <= n):
             raise ValueError(f"outputs [{first}, {first + count}) are not inside the {n} frames given")
         h, w = frames[0].shape[:2]
-        out_shape, out_dtype = (h, w, 4), (np.uint8 if out_u8 else np.float32)
+        out_shape, out_dtype = (h, w, 4), _out_dtype(out_u8, out_dtype)
         hin = PinnedFrames(self, frames) if pinned else None
-        hout = PinnedFrames(self, count, w * h * (4 if out_u8 else 16)) if pinned_out else None
+        hout = PinnedFrames(self, count, w * h * 4 * out_dtype.itemsize) if pinned_out else None
         outs = None if pinned_out else [np.empty(out_shape, out_dtype) for _ in range(count)]
         try:
             t = self.sequence_nlm_pinned(hin.ptrs if pinned else [f.ctypes.data for f in frames],
                                          hout.ptrs if pinned_out else [o.ctypes.data for o in outs], w, h, _fmt_of(frames[0]),
-                                         k, first, count, overlap, hparam, search, patch, out_u8)
+                                         k, first, count, overlap, hparam, search, patch, out_dtype=out_dtype)
             return (outs if outs is not None else [hout.array(i, out_shape, out_dtype) for i in range(count)]), t
         finally:
             if hin is not None:
                 hin.free()
             if hout is not None:
                 hout.free()
+
+
+def _out_dtype(out_u8, out_dtype):
+    """Output dtype of the frame pipeline: out_u8=True is uint8; otherwise out_dtype (None = float32; float16 allowed)."""
+    if out_u8:
+        if out_dtype is not None and np.dtype(out_dtype) != np.uint8:
+            raise ValueError(f"out_u8=True and out_dtype={out_dtype} contradict each other")
+        return np.dtype(np.uint8)
+    dt = np.dtype(np.float32 if out_dtype is None else out_dtype)
+    if dt not in (np.dtype(np.float32), np.dtype(np.float16), np.dtype(np.uint8)):
+        raise TypeError(f"sequence_nlm: out_dtype must be float32, float16 or uint8, got {dt}")
+    return dt
 
 
 class Recording:

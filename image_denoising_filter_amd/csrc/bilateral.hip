@@ -499,9 +499,18 @@ static int check_params(const mid_bilateral_params *p, const char *who)
     MID_REQUIRE((long)p->width * p->height < (1l << 30), "%s: image too large", who);
     MID_REQUIRE(p->spatialSigma > 0.f && p->colorSigma > 0.f, "%s: sigmas must be > 0", who);
     MID_REQUIRE(p->radius >= 1 && p->radius <= 24, "%s: radius %d outside 1..24", who, p->radius);
-    MID_REQUIRE(p->format == MID_FMT_RGBA32F || p->format == MID_FMT_RGBA8, "%s: unknown format %d", who, p->format);
+    MID_REQUIRE(fmt_known(p->format), "%s: unknown format %d", who, p->format);
     MID_REQUIRE(p->layout == MID_LAYOUT_TEXTURE || p->layout == MID_LAYOUT_LINEAR, "%s: unknown layout %d", who, p->layout);
     return MID_OK;
+}
+
+// The input's texel format as a template argument: one switch for every entry point (the guide layers are always RGBA8).
+template <bool LINEAR, int MODE, typename BT = BilOne>
+static int dispatch_format(mid_ctx *ctx, int format, int radius, BilArgs &a, hipStream_t s, const BT &bt = BT{}, int n_frames = 1)
+{
+    if (format == MID_FMT_RGBA8) return dispatch_radius<MID_FMT_RGBA8, LINEAR, MODE, BT>(ctx, radius, a, s, bt, n_frames);
+    if (format == MID_FMT_RGBA16F) return dispatch_radius<MID_FMT_RGBA16F, LINEAR, MODE, BT>(ctx, radius, a, s, bt, n_frames);
+    return dispatch_radius<MID_FMT_RGBA32F, LINEAR, MODE, BT>(ctx, radius, a, s, bt, n_frames);
 }
 
 static void fill_scales(const mid_bilateral_params *p, BilArgs &a)
@@ -525,14 +534,12 @@ extern "C" int mid_bilateral(mid_ctx *ctx, const mid_bilateral_params *p, const 
     if (int rc = check_params(p, "bilateral")) return rc;
     MID_REQUIRE(in && out, "bilateral: NULL image pointer");
     MID_REQUIRE((const void *)in != (const void *)out, "bilateral: in-place filtering is not supported");
+    MID_REQUIRE(fmt_aligned(p->format, in), "bilateral: RGBA16F input must be 8-byte aligned");
     BilArgs a{};
     fill_scales(p, a);
     a.in = in; a.out = (float4 *)out;
-    const bool lin = p->layout == MID_LAYOUT_LINEAR, u8 = p->format == MID_FMT_RGBA8;
-    if (lin) return u8 ? dispatch_radius<MID_FMT_RGBA8, true, 0>(ctx, p->radius, a, b.s)
-                       : dispatch_radius<MID_FMT_RGBA32F, true, 0>(ctx, p->radius, a, b.s);
-    return u8 ? dispatch_radius<MID_FMT_RGBA8, false, 0>(ctx, p->radius, a, b.s)
-              : dispatch_radius<MID_FMT_RGBA32F, false, 0>(ctx, p->radius, a, b.s);
+    if (p->layout == MID_LAYOUT_LINEAR) return dispatch_format<true, 0>(ctx, p->format, p->radius, a, b.s);
+    return dispatch_format<false, 0>(ctx, p->format, p->radius, a, b.s);
 }
 
 extern "C" int mid_bilateral_layers_accum(mid_ctx *ctx, const mid_bilateral_params *p, const void *in,
@@ -542,13 +549,13 @@ extern "C" int mid_bilateral_layers_accum(mid_ctx *ctx, const mid_bilateral_para
     if (b.rc) return b.rc;
     if (int rc = check_params(p, "bilateral_layers_accum")) return rc;
     MID_REQUIRE(in && layer && W, "bilateral_layers_accum: NULL pointer");
+    MID_REQUIRE(fmt_aligned(p->format, in), "bilateral_layers_accum: RGBA16F input must be 8-byte aligned");
     // NLM/layers are only ever bound to textures in the reference (src/main.cpp:1406-1428).
     MID_REQUIRE(p->layout == MID_LAYOUT_TEXTURE, "bilateral_layers_accum: layers exist for the texture layout only");
     BilArgs a{};
     fill_scales(p, a);
     a.in = in; a.W = W; a.n_layers = 1; a.layers[0] = layer;
-    return p->format == MID_FMT_RGBA8 ? dispatch_radius<MID_FMT_RGBA8, false, 1>(ctx, p->radius, a, b.s)
-                                      : dispatch_radius<MID_FMT_RGBA32F, false, 1>(ctx, p->radius, a, b.s);
+    return dispatch_format<false, 1>(ctx, p->format, p->radius, a, b.s);
 }
 
 extern "C" int mid_bilateral_layers(mid_ctx *ctx, const mid_bilateral_params *p, const void *in,
@@ -558,6 +565,7 @@ extern "C" int mid_bilateral_layers(mid_ctx *ctx, const mid_bilateral_params *p,
     if (b.rc) return b.rc;
     if (int rc = check_params(p, "bilateral_layers")) return rc;
     MID_REQUIRE(in && layers && out, "bilateral_layers: NULL pointer");
+    MID_REQUIRE(fmt_aligned(p->format, in), "bilateral_layers: RGBA16F input must be 8-byte aligned");
     MID_REQUIRE((const void *)out != in, "bilateral_layers: out is the input image (in-place filtering is not supported)");
     MID_REQUIRE(p->layout == MID_LAYOUT_TEXTURE, "bilateral_layers: layers exist for the texture layout only");
     MID_REQUIRE(n_layers >= 0 && n_layers <= 16, "bilateral_layers: n_layers %d outside 0..16", n_layers);
@@ -568,8 +576,7 @@ extern "C" int mid_bilateral_layers(mid_ctx *ctx, const mid_bilateral_params *p,
         MID_REQUIRE(layers[i] != nullptr, "bilateral_layers: layer %d is NULL", i);
         a.layers[i] = layers[i];
     }
-    return p->format == MID_FMT_RGBA8 ? dispatch_radius<MID_FMT_RGBA8, false, 2>(ctx, p->radius, a, b.s)
-                                      : dispatch_radius<MID_FMT_RGBA32F, false, 2>(ctx, p->radius, a, b.s);
+    return dispatch_format<false, 2>(ctx, p->format, p->radius, a, b.s);
 }
 
 extern "C" int mid_bilateral_batch(mid_ctx *ctx, const mid_bilateral_params *p, const void *const *in,
@@ -581,10 +588,11 @@ extern "C" int mid_bilateral_batch(mid_ctx *ctx, const mid_bilateral_params *p, 
     MID_REQUIRE(in && out, "bilateral_batch: NULL table");
     MID_REQUIRE(n_frames >= 1, "bilateral_batch: n_frames %d < 1", n_frames);
     for (int i = 0; i < n_frames; ++i) MID_REQUIRE(in[i] && out[i], "bilateral_batch: frame %d is NULL", i);
+    for (int i = 0; i < n_frames; ++i) MID_REQUIRE(fmt_aligned(p->format, in[i]), "bilateral_batch: RGBA16F frame %d is not 8-byte aligned", i);
     // All frames of a launch run concurrently: an output that is ANY frame's input (not only its own) would be written while
     // other workgroups still read it -- ping-pong tables shifted by one slot, say.
     if (int rc = check_no_alias("bilateral_batch", "an input frame of this call", in, n_frames, (const void *const *)out, n_frames)) return rc;
-    const bool lin = p->layout == MID_LAYOUT_LINEAR, u8 = p->format == MID_FMT_RGBA8;
+    const bool lin = p->layout == MID_LAYOUT_LINEAR;
     for (int c0 = 0; c0 < n_frames; c0 += kMaxFrames) {          // one launch per kMaxFrames frames
         const int cn = n_frames - c0 < kMaxFrames ? n_frames - c0 : kMaxFrames;
         BilArgs a{};
@@ -592,10 +600,8 @@ extern "C" int mid_bilateral_batch(mid_ctx *ctx, const mid_bilateral_params *p, 
         BilBatch bt{};
         for (int i = 0; i < cn; ++i) { bt.in.p[i] = in[c0 + i]; bt.out.p[i] = out[c0 + i]; }
         int rc;
-        if (lin) rc = u8 ? dispatch_radius<MID_FMT_RGBA8, true, 0, BilBatch>(ctx, p->radius, a, b.s, bt, cn)
-                         : dispatch_radius<MID_FMT_RGBA32F, true, 0, BilBatch>(ctx, p->radius, a, b.s, bt, cn);
-        else rc = u8 ? dispatch_radius<MID_FMT_RGBA8, false, 0, BilBatch>(ctx, p->radius, a, b.s, bt, cn)
-                     : dispatch_radius<MID_FMT_RGBA32F, false, 0, BilBatch>(ctx, p->radius, a, b.s, bt, cn);
+        if (lin) rc = dispatch_format<true, 0, BilBatch>(ctx, p->format, p->radius, a, b.s, bt, cn);
+        else rc = dispatch_format<false, 0, BilBatch>(ctx, p->format, p->radius, a, b.s, bt, cn);
         if (rc) return rc;
     }
     return MID_OK;

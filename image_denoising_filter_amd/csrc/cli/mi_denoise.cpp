@@ -66,6 +66,7 @@ struct Options {
     bool pageable_host = false;     // reference modes: keep decoded images and results in ordinary memory (the C-ABI bounces them)
     long pinned_mb = 16384;         // animation mode: at most this much page-locked host memory (inputs + outputs); the rest is pageable
     int io_threads = 0;             // animation mode: files decoded / encoded at a time (0 = min(16, hardware threads))
+    bool half = false;              // GPU modes and animation, .exr inputs: frames as RGBA16F (mid_image_load_f16), HALF EXR outputs
 };
 
 #define MID_CHECK(call)                                                                          \
@@ -146,16 +147,20 @@ class DenoiseApplication {
             img.data = nullptr;
         }
         ~HostImage() { release(); }
-        size_t size() const { return (size_t)w * h * (format == MID_FMT_RGBA32F ? 16 : 4); }
+        size_t size() const { return (size_t)w * h * (format == MID_FMT_RGBA32F ? 16 : format == MID_FMT_RGBA16F ? 8 : 4); }
         const uint8_t *data() const { return (const uint8_t *)img.data; }
     };
 
-    static HostImage load(const std::string &path, bool force_png, mid_ctx *ctx = nullptr)
+    // half: an .exr as RGBA16F (--half): HALF channels bit for bit, FLOAT ones rounded to nearest even
+    static HostImage load(const std::string &path, bool force_png, mid_ctx *ctx = nullptr, bool half = false)
     {
         // layers are always decoded as PNG (src/main.cpp:1396 passes a_isHDR=false)
         if (force_png && is_hdr(path)) throw std::runtime_error("layer " + path + " is not a PNG");
         HostImage h;
-        if (ctx && mid_image_load_pinned(ctx, path.c_str(), &h.img) == MID_OK) h.pin_ctx = ctx;
+        if (half) {
+            if (ctx && mid_image_load_f16(ctx, path.c_str(), &h.img) == MID_OK) h.pin_ctx = ctx;
+            else if (mid_image_load_f16(nullptr, path.c_str(), &h.img)) throw std::runtime_error(mid_last_error());
+        } else if (ctx && mid_image_load_pinned(ctx, path.c_str(), &h.img) == MID_OK) h.pin_ctx = ctx;
         else if (mid_image_load(path.c_str(), &h.img))
             throw std::runtime_error(mid_last_error());        // lodepng error -> runtime_error, src/main.cpp:202
         h.w = h.img.width; h.h = h.img.height; h.format = h.img.format;
@@ -242,9 +247,10 @@ public:
         std::vector<std::string> frameNames, layerNames;
         discover(frameNames, layerNames, multiframe, useLayers);
         const bool hdr = is_hdr(opt.image);
+        const bool half = hdr && opt.half;                               // --half: RGBA16F frames in, HALF EXR out
         mid_ctx *pin = opt.pageable_host ? nullptr : ctx;              // where decoded images live
         if (opt.pageable_host) std::cout << "\thost buffers: pageable (bounced inside the library)\n";
-        HostImage target = [&] { TraceRange r("decode target"); return load(opt.image, false, pin); }();
+        HostImage target = [&] { TraceRange r("decode target"); return load(opt.image, false, pin, half); }();
         const int w = target.w, h = target.h;
         const size_t npix = (size_t)w * h, out_bytes = npix * sizeof(Pixel);
         const int fmt = target.format;
@@ -294,7 +300,7 @@ public:
             }
             std::vector<HostImage> frames(list.size());
             for_each_file(0, (int)list.size(), [&](int i) {
-                frames[i] = load(list[i], false, pin);
+                frames[i] = load(list[i], false, pin, half);
                 check_dims(frames[i], list[i]);
             });
             std::vector<const void *> ptrs;
@@ -355,7 +361,19 @@ public:
         outputFileName += multiframe ? "-multiframe" : "";
         outputFileName += execAndCopyOverlap ? "-overlap" : "";
         outputFileName += useLayers ? "-layers" : "";
-        { TraceRange r("encode + write " + outputFileName); save(outputFileName, result.data(), w, h, hdr); }
+        if (half) {   // --half: the fp32 result rounded to RGBA16F on the device (mid_pack_f16), written as HALF EXR
+            std::vector<uint16_t> px(npix * 4);
+            void *dF = nullptr, *dH = nullptr;
+            MID_CHECK(mid_alloc(ctx, out_bytes, &dF));
+            MID_CHECK(mid_alloc(ctx, npix * 8, &dH));
+            MID_CHECK(mid_memcpy_h2d(ctx, dF, result.data(), out_bytes, nullptr));
+            MID_CHECK(mid_pack_f16(ctx, (const float *)dF, npix * 4, (uint16_t *)dH, nullptr));
+            MID_CHECK(mid_memcpy_d2h(ctx, px.data(), dH, npix * 8, nullptr));
+            MID_CHECK(mid_stream_sync(ctx, nullptr));
+            mid_free(ctx, dF); mid_free(ctx, dH);
+            TraceRange r("encode + write " + outputFileName);
+            MID_CHECK(mid_image_save(out_path(outputFileName + ".exr").c_str(), px.data(), w, h, MID_FMT_RGBA16F));
+        } else { TraceRange r("encode + write " + outputFileName); save(outputFileName, result.data(), w, h, hdr); }
         std::cout << "\tcleaning up\n";
     }
 
@@ -411,15 +429,26 @@ public:
         // by frame, input i is pinned only if output i can be as well); the others are decoded concurrently (for_each_file).
         pin.frames.assign(n, mid_image{});
         pin.frame_pinned.assign(n, 0);
+        // --half: .exr frames as RGBA16F (mid_image_load_f16), filtered as such, written back as HALF EXR from the kernel's epilogue
+        const bool half = opt.half && is_hdr(frameNames[0]);
+        if (half && opt.halo_rccl) throw std::runtime_error("--half is not available with --halo rccl (its outputs are RGBA32F)");
         auto decode = [&](int i, bool pinned) {            // throws on a bad file; falls back to pageable memory when no pinned memory is left
             mid_image img{};
+            if (half) {
+                if (pinned && mid_image_load_f16(io, frameNames[i].c_str(), &img)) pinned = false;
+                if (!pinned && mid_image_load_f16(nullptr, frameNames[i].c_str(), &img)) throw std::runtime_error(mid_last_error());
+                pin.frames[i] = img;
+                pin.frame_pinned[i] = pinned ? 1 : 0;
+                return;
+            }
             if (pinned && mid_image_load_pinned(io, frameNames[i].c_str(), &img)) pinned = false;
             if (!pinned && mid_image_load(frameNames[i].c_str(), &img)) throw std::runtime_error(mid_last_error());
             pin.frames[i] = img;
             pin.frame_pinned[i] = pinned ? 1 : 0;
         };
         decode(0, pinned_budget > 0);                       // (the first frame's size is not known yet: any non-zero budget admits it)
-        frame_bytes_guess = (size_t)pin.frames[0].width * pin.frames[0].height * (pin.frames[0].format == MID_FMT_RGBA32F ? 16 : 4);
+        frame_bytes_guess = (size_t)pin.frames[0].width * pin.frames[0].height *
+                            (pin.frames[0].format == MID_FMT_RGBA32F ? 16 : pin.frames[0].format == MID_FMT_RGBA16F ? 8 : 4);
         const size_t n_pin = pinned_budget / (2 * frame_bytes_guess);     // frames whose input AND output fit the budget
         const int io_threads = files_at_a_time(n);
         for_each_file(1, n, [&](int i) {
@@ -433,8 +462,8 @@ public:
         const int w = pin.frames[0].width, h = pin.frames[0].height, fmt = pin.frames[0].format;
         // LDR frames come back as RGBA8: the read-back conversion of GetImageFromGPU (:97-103) runs on the device
         // (mid_sequence_nlm_range_u8), a quarter of the download
-        const bool hdr = fmt == MID_FMT_RGBA32F;
-        const size_t out_bytes = (size_t)w * h * (hdr ? 16 : 4), in_bytes = out_bytes;
+        const bool hdr = fmt == MID_FMT_RGBA32F;           // (--half: fmt is RGBA16F, `half` set, `hdr` false)
+        const size_t out_bytes = (size_t)w * h * (hdr ? 16 : half ? 8 : 4), in_bytes = out_bytes;
         std::vector<const void *> in(n);
         for (int i = 0; i < n; ++i) {
             in[i] = pin.frames[i].data;
@@ -469,6 +498,7 @@ public:
             std::vector<unsigned char> a((size_t)ww * wh * 16, 0), o((size_t)ww * wh * 16);
             const void *wi[2] = {a.data(), a.data()};
             if (hdr) { mid_pixel *wo[2] = {(mid_pixel *)o.data(), (mid_pixel *)o.data()}; MID_CHECK(mid_sequence_nlm_range(ctxs[g], &wp, wi, 2, k > 0 ? 1 : 0, 0, 1, wo, 1, nullptr)); }
+            else if (half) { uint16_t *wo[2] = {(uint16_t *)o.data(), (uint16_t *)o.data()}; MID_CHECK(mid_sequence_nlm_range_f16(ctxs[g], &wp, wi, 2, k > 0 ? 1 : 0, 0, 1, wo, 1, nullptr)); }
             else { uint8_t *wo[2] = {o.data(), o.data()}; MID_CHECK(mid_sequence_nlm_range_u8(ctxs[g], &wp, wi, 2, k > 0 ? 1 : 0, 0, 1, wo, 1, nullptr)); }
             // (b) the pinned-memory DMA path in both directions at the real frame size (its first use in a process
             // costs several ms): frame 0 up into a scratch buffer, and back down into the first result buffer
@@ -566,6 +596,10 @@ public:
                         std::vector<mid_pixel *> o(count);
                         for (int i = 0; i < count; ++i) o[i] = (mid_pixel *)pin.outs[start + i];
                         MID_CHECK(mid_sequence_nlm_range(ctx, &p, in.data(), n, k, start, count, o.data(), 1, t));
+                    } else if (half) {
+                        std::vector<uint16_t *> o(count);
+                        for (int i = 0; i < count; ++i) o[i] = (uint16_t *)pin.outs[start + i];
+                        MID_CHECK(mid_sequence_nlm_range_f16(ctx, &p, in.data(), n, k, start, count, o.data(), 1, t));
                     } else {
                         std::vector<uint8_t *> o(count);
                         for (int i = 0; i < count; ++i) o[i] = (uint8_t *)pin.outs[start + i];
@@ -585,10 +619,11 @@ public:
         // SaveEXR :1699 / lodepng::encode :1717, straight from the pinned results -- one file per worker thread, like the decode
         const auto te0 = std::chrono::steady_clock::now();
         for_each_file(0, n, [&](int i) {
-            const std::string name = "output-animation-" + fs::path(frameNames[i]).stem().string() + (hdr ? ".exr" : ".png");
-            if (mid_image_save(out_path(name).c_str(), pin.outs[i], w, h, hdr ? MID_FMT_RGBA32F : MID_FMT_RGBA8)) throw std::runtime_error(mid_last_error());
+            const std::string name = "output-animation-" + fs::path(frameNames[i]).stem().string() + (hdr || half ? ".exr" : ".png");
+            if (mid_image_save(out_path(name).c_str(), pin.outs[i], w, h, hdr ? MID_FMT_RGBA32F : half ? MID_FMT_RGBA16F : MID_FMT_RGBA8))
+                throw std::runtime_error(mid_last_error());
         });
-        if (!hdr) for (int i = 0; i < n; ++i) std::cout << "\t\tencoding png\n";
+        if (!hdr && !half) for (int i = 0; i < n; ++i) std::cout << "\t\tencoding png\n";
         std::cout << "\tencoded " << n << " frames in " << std::chrono::duration<double>(std::chrono::steady_clock::now() - te0).count()
                   << " sec (" << io_threads << " file(s) at a time)\n";
     }
@@ -665,6 +700,9 @@ static void usage()
         "  --pinned-mb M             animation mode: page-lock at most M MiB of host memory for frames in and out (default 16384);\n"
         "                            frames beyond that, or whose page-locked allocation fails, use pageable memory\n"
         "  --io-threads T            animation mode: decode / encode T files at a time, one per host thread (default min(16, hardware threads))\n"
+        "  --half                    .exr inputs of the GPU modes and of --animation: load the frames as RGBA16F (half float: HALF\n"
+        "                            channels bit for bit), filter them as such and write HALF EXR outputs (the fp32 result rounded\n"
+        "                            to nearest even).  PNG inputs and the CPU runs ignore it; not with --halo rccl\n"
         "  --cpu-radius R --cpu-sigma-s S --cpu-sigma-c C   CPU path (default 10 10.0 0.2)\n"
         "  --cpu-threads A,B         thread counts of the CPU runs (default 1,8)\n"
         "  --cpu-fix-blue            use the blue channel in the CPU range distance (the reference does not)\n";
@@ -693,6 +731,7 @@ int main(int argc, char **argv)
         else if (a == "--patch") { if (!pair_arg(next(), opt.patch_lo, opt.patch_hi)) { usage(); return EXIT_FAILURE; } }
         else if (a == "--temporal-k") opt.temporal_k = atoi(next());
         else if (a == "--animation") opt.animation = true;
+        else if (a == "--half") opt.half = true;
         else if (a == "--gpus") opt.gpus = atoi(next());
         else if (a == "--share-device") opt.share_device = true;
         else if (a == "--pinned-mb") opt.pinned_mb = atol(next());

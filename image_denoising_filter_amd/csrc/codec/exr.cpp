@@ -10,12 +10,15 @@
 // rejected with a message naming the feature.
 // Write: channels A,B,G,R as FLOAT, ZIP blocks of 16 lines (NONE when the image is smaller than
 // 16x16), the attribute set tinyexr's SaveEXR(data, w, h, 4, 0, ...) emits.
+// RGBA16F (exr_decode_half_to / exr_encode_half): the same reader and writer with binary16 pixels -- HALF channels are
+// copied bit for bit, FLOAT and UINT ones rounded to nearest even (float_to_half); written as HALF channels.
 #include "image_io.hpp"
 
 #include <zlib.h>
 
 #include <algorithm>
 #include <cstdio>
+#include <type_traits>
 #include <cstring>
 
 namespace mid {
@@ -61,6 +64,35 @@ static float half_to_float(uint16_t h)
     float f;
     memcpy(&f, &u, 4);
     return f;
+}
+
+// fp32 -> binary16, round to nearest even, in integer arithmetic: the bits numpy.float16(x) has (overflow -> +-Inf, NaN ->
+// NaN with the payload's top bits kept, results below 2^-14 as subnormals).
+uint16_t float_to_half(float f)
+{
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    const uint32_t sign = (u >> 16) & 0x8000u, a = u & 0x7fffffffu;
+    if (a >= 0x7f800000u) {                                   // Inf / NaN
+        if (a == 0x7f800000u) return (uint16_t)(sign | 0x7c00u);
+        uint32_t h = 0x7c00u + ((a & 0x7fffffu) >> 13);
+        if (h == 0x7c00u) ++h;                                // a NaN whose payload sits in the low bits stays a NaN
+        return (uint16_t)(sign | h);
+    }
+    if (a >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);  // >= 65520: rounds to Inf
+    if (a < 0x38800000u) {                                    // below 2^-14: an f16 subnormal (or zero)
+        if (a <= 0x33000000u) return (uint16_t)sign;          // <= 2^-25: the tie with 2^-24 goes to the even zero
+        const uint32_t e = a >> 23, m = (a & 0x7fffffu) | 0x800000u, sh = 126 - e;   // value / 2^-24 = m >> sh
+        uint32_t r = m >> sh;
+        const uint32_t rem = m & ((1u << sh) - 1), half = 1u << (sh - 1);
+        if (rem > half || (rem == half && (r & 1u))) ++r;
+        return (uint16_t)(sign | r);
+    }
+    const uint32_t b = a - 0x38000000u;                       // exponent rebiased 127 -> 15
+    uint32_t h = b >> 13;
+    const uint32_t rem = b & 0x1fffu;
+    if (rem > 0x1000u || (rem == 0x1000u && (h & 1u))) ++h;   // a carry into the exponent is the correct result
+    return (uint16_t)(sign | h);
 }
 
 struct Reader {
@@ -151,8 +183,25 @@ bool exr_decode(const std::vector<uint8_t> &file, int &w, int &h, std::vector<fl
     return exr_decode_to(file, w, h, [&](size_t n) { rgba.assign(n, 0.f); return rgba.data(); }, err);
 }
 
-bool exr_decode_to(const std::vector<uint8_t> &file, int &w, int &h, const FloatAlloc &alloc, std::string &err)
+// One channel value of the file as an output element: float (mid_image_load) or binary16 bits (mid_image_load_f16).
+template <class T> static T exr_value(int type, const uint8_t *q);
+template <> float exr_value<float>(int type, const uint8_t *q)
 {
+    if (type == 1) { uint16_t hv; memcpy(&hv, q, 2); return half_to_float(hv); }
+    if (type == 2) { float v; memcpy(&v, q, 4); return v; }
+    uint32_t u; memcpy(&u, q, 4); return (float)u;
+}
+template <> uint16_t exr_value<uint16_t>(int type, const uint8_t *q)
+{
+    if (type == 1) { uint16_t hv; memcpy(&hv, q, 2); return hv; }     // HALF: bit for bit
+    if (type == 2) { float v; memcpy(&v, q, 4); return float_to_half(v); }
+    uint32_t u; memcpy(&u, q, 4); return float_to_half((float)u);      // UINT: through float, like the RGBA32F load
+}
+
+template <class T>
+static bool exr_decode_impl(const std::vector<uint8_t> &file, int &w, int &h, const std::function<T *(size_t)> &alloc, std::string &err)
+{
+    const T one = std::is_same<T, float>::value ? (T)1.0f : (T)0x3c00u;   // missing alpha = 1.0
     Reader r{file.data(), file.data() + file.size()};
     if (file.size() < 8 || r.i32() != 20000630) { err = "exr: not an OpenEXR file"; return false; }
     const int32_t ver = r.i32();
@@ -241,9 +290,9 @@ bool exr_decode_to(const std::vector<uint8_t> &file, int &w, int &h, const Float
     for (auto &o : offsets) o = r.u64();
     if (!r.ok) { err = "exr: truncated offset table"; return false; }
 
-    float *const rgba = alloc((size_t)W * H * 4);
+    T *const rgba = alloc((size_t)W * H * 4);
     if (!rgba) { err = "exr: out of memory"; return false; }
-    for (size_t i = 0; i < (size_t)W * H; ++i) { rgba[i * 4] = rgba[i * 4 + 1] = rgba[i * 4 + 2] = 0.f; rgba[i * 4 + 3] = 1.0f; }   // missing alpha = 1
+    for (size_t i = 0; i < (size_t)W * H; ++i) { rgba[i * 4] = rgba[i * 4 + 1] = rgba[i * 4 + 2] = (T)0; rgba[i * 4 + 3] = one; }   // missing alpha = 1
     std::vector<std::string> errs(nblocks);
     parallel_for(nblocks, [&](size_t b) {
         std::string &err = errs[b];
@@ -302,14 +351,12 @@ bool exr_decode_to(const std::vector<uint8_t> &file, int &w, int &h, const Float
         }
         for (long l = 0; l < nl; ++l) {
             const uint8_t *line = data + (size_t)l * line_bytes;
-            float *out = rgba + ((size_t)(y0 + l) * W + (size_t)x0) * 4;
+            T *out = rgba + ((size_t)(y0 + l) * W + (size_t)x0) * 4;
             auto read_ch = [&](int ch, int dst_lo, int dst_hi) {
                 const uint8_t *q = line + chpre[ch] * (size_t)bw;
+                const int type = chans[ch].type;
                 for (long x = 0; x < bw; ++x) {
-                    float v;
-                    if (chans[ch].type == 1) { uint16_t hv; memcpy(&hv, q + 2 * x, 2); v = half_to_float(hv); }
-                    else if (chans[ch].type == 2) memcpy(&v, q + 4 * x, 4);
-                    else { uint32_t u; memcpy(&u, q + 4 * x, 4); v = (float)u; }
+                    const T v = exr_value<T>(type, q + (type == 1 ? 2 : 4) * x);
                     for (int k = dst_lo; k <= dst_hi; ++k) out[x * 4 + k] = v;
                 }
             };
@@ -326,6 +373,16 @@ bool exr_decode_to(const std::vector<uint8_t> &file, int &w, int &h, const Float
     return true;
 }
 
+bool exr_decode_to(const std::vector<uint8_t> &file, int &w, int &h, const FloatAlloc &alloc, std::string &err)
+{
+    return exr_decode_impl<float>(file, w, h, alloc, err);
+}
+
+bool exr_decode_half_to(const std::vector<uint8_t> &file, int &w, int &h, const HalfAlloc &alloc, std::string &err)
+{
+    return exr_decode_impl<uint16_t>(file, w, h, alloc, err);
+}
+
 static void put_bytes(std::vector<uint8_t> &v, const void *p, size_t n) { v.insert(v.end(), (const uint8_t *)p, (const uint8_t *)p + n); }
 static void put_str(std::vector<uint8_t> &v, const char *s) { put_bytes(v, s, strlen(s) + 1); }
 static void put_i32(std::vector<uint8_t> &v, int32_t x) { put_bytes(v, &x, 4); }
@@ -335,8 +392,11 @@ static void put_attr(std::vector<uint8_t> &v, const char *name, const char *type
     put_str(v, name); put_str(v, type); put_i32(v, (int32_t)val.size()); put_bytes(v, val.data(), val.size());
 }
 
-bool exr_encode(const float *rgba, int w, int h, std::vector<uint8_t> &file, std::string &err)
+// T = float: FLOAT channels; T = uint16_t (binary16 bits): HALF channels.  Same layout, attributes and compression.
+template <class T>
+static bool exr_encode_impl(const T *rgba, int w, int h, std::vector<uint8_t> &file, std::string &err)
 {
+    constexpr int32_t kType = sizeof(T) == 2 ? 1 /*HALF*/ : 2 /*FLOAT*/;
     if (w <= 0 || h <= 0 || !rgba) { err = "exr: bad image"; return false; }
     const bool zip = !(w < 16 && h < 16);
     file.clear();
@@ -345,7 +405,7 @@ bool exr_encode(const float *rgba, int w, int h, std::vector<uint8_t> &file, std
     {   // header
         std::vector<uint8_t> ch;
         for (const char *n : {"A", "B", "G", "R"}) {
-            put_str(ch, n); put_i32(ch, 2 /*FLOAT*/); ch.insert(ch.end(), 4, 0); put_i32(ch, 1); put_i32(ch, 1);
+            put_str(ch, n); put_i32(ch, kType); ch.insert(ch.end(), 4, 0); put_i32(ch, 1); put_i32(ch, 1);
         }
         ch.push_back(0);
         put_attr(file, "channels", "chlist", ch);
@@ -366,7 +426,7 @@ bool exr_encode(const float *rgba, int w, int h, std::vector<uint8_t> &file, std
     const size_t nblocks = (size_t)((h + lpb - 1) / lpb);
     const size_t table = file.size();
     file.resize(table + nblocks * 8);
-    const size_t line_bytes = (size_t)w * 16;
+    const size_t line_bytes = (size_t)w * 4 * sizeof(T);
     static const int order[4] = {3, 2, 1, 0};   // A, B, G, R from RGBA
     std::vector<std::vector<uint8_t>> payload(nblocks);
     std::vector<std::string> errs(nblocks);
@@ -377,8 +437,8 @@ bool exr_encode(const float *rgba, int w, int h, std::vector<uint8_t> &file, std
             raw.resize(line_bytes * nl);
             for (int l = 0; l < nl; ++l)
                 for (int c = 0; c < 4; ++c) {
-                    float *dst = (float *)(raw.data() + (size_t)l * line_bytes + (size_t)c * w * 4);
-                    const float *src = rgba + (size_t)(y0 + l) * w * 4 + order[c];
+                    T *dst = (T *)(raw.data() + (size_t)l * line_bytes + (size_t)c * w * sizeof(T));
+                    const T *src = rgba + (size_t)(y0 + l) * w * 4 + order[c];
                     for (int x = 0; x < w; ++x) dst[x] = src[(size_t)x * 4];
                 }
             if (zip) {
@@ -407,6 +467,16 @@ bool exr_encode(const float *rgba, int w, int h, std::vector<uint8_t> &file, std
         put_bytes(file, payload[b].data(), payload[b].size());
     }
     return true;
+}
+
+bool exr_encode(const float *rgba, int w, int h, std::vector<uint8_t> &file, std::string &err)
+{
+    return exr_encode_impl<float>(rgba, w, h, file, err);
+}
+
+bool exr_encode_half(const uint16_t *rgba, int w, int h, std::vector<uint8_t> &file, std::string &err)
+{
+    return exr_encode_impl<uint16_t>(rgba, w, h, file, err);
 }
 
 }  // namespace codec

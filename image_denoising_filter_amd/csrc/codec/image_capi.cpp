@@ -17,12 +17,14 @@ static bool has_ext(const std::string &p, const char *ext)
 }
 
 // Shared body of mid_image_load / mid_image_load_pinned: `get(bytes)` provides the pixel memory (called once, after
-// the header checks), `drop(ptr)` takes it back when decoding fails afterwards.
+// the header checks), `drop(ptr)` takes it back when decoding fails afterwards.  half: an .exr as RGBA16F (mid_image_load_f16;
+// anything else is refused before the file is read).
 template <class Get, class Drop>
-static int load_impl(const char *path, mid_image *out, Get get, Drop drop)
+static int load_impl(const char *path, mid_image *out, Get get, Drop drop, bool half = false)
 {
     MID_REQUIRE(path && out, "image_load: NULL argument");
     out->width = out->height = 0; out->format = 0; out->data = nullptr;
+    MID_REQUIRE(!half || has_ext(path, ".exr"), "image_load_f16: %s is not an .exr (RGBA16F frames come from EXR files only)", path);
     std::vector<uint8_t> file;
     std::string err;
     if (!codec::read_file(path, file, err)) return set_error(MID_ERR_IO, "%s", err.c_str());
@@ -30,7 +32,10 @@ static int load_impl(const char *path, mid_image *out, Get get, Drop drop)
     void *mem = nullptr;
     bool ok = false;
     try {   // a corrupt header can ask for an absurd allocation: no exception may cross the C ABI
-        if (has_ext(path, ".exr")) {                      // m_isHDR = extension == ".exr", src/main.cpp:1380
+        if (half) {
+            ok = codec::exr_decode_half_to(file, w, h, [&](size_t n) { mem = get(n * sizeof(uint16_t)); return (uint16_t *)mem; }, err);
+            out->format = MID_FMT_RGBA16F;
+        } else if (has_ext(path, ".exr")) {               // m_isHDR = extension == ".exr", src/main.cpp:1380
             ok = codec::exr_decode_to(file, w, h, [&](size_t n) { mem = get(n * sizeof(float)); return (float *)mem; }, err);
             out->format = MID_FMT_RGBA32F;
         } else {
@@ -64,6 +69,16 @@ extern "C" int mid_image_load_pinned(mid_ctx *ctx, const char *path, mid_image *
                      [](void *p) { (void)hipHostFree(p); });
 }
 
+extern "C" int mid_image_load_f16(mid_ctx *ctx, const char *path, mid_image *out)
+{
+    if (!ctx) return load_impl(path, out, [](size_t bytes) { return malloc(bytes ? bytes : 1); }, [](void *p) { free(p); }, true);
+    Bind b(ctx, nullptr);
+    if (b.rc) return b.rc;
+    return load_impl(path, out,
+                     [](size_t bytes) { void *p = nullptr; return hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocDefault) == hipSuccess ? p : nullptr; },
+                     [](void *p) { (void)hipHostFree(p); }, true);
+}
+
 extern "C" int mid_image_free_pinned(mid_ctx *ctx, mid_image *img)
 {
     Bind b(ctx, nullptr);
@@ -94,6 +109,7 @@ extern "C" int mid_image_save(const char *path, const void *data, int32_t w, int
     try {
     if (format == MID_FMT_RGBA32F) ok = codec::exr_encode((const float *)data, w, h, file, err);
     else if (format == MID_FMT_RGBA8) ok = codec::png_encode((const uint8_t *)data, w, h, file, err);
+    else if (format == MID_FMT_RGBA16F) ok = codec::exr_encode_half((const uint16_t *)data, w, h, file, err);
     else return set_error(MID_ERR_INVALID, "image_save: unknown format %d", format);
     if (!ok) return set_error(MID_ERR_IO, "%s: %s", path, err.c_str());
     if (!codec::write_file(path, file, err)) return set_error(MID_ERR_IO, "%s", err.c_str());

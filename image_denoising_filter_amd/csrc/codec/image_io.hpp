@@ -53,8 +53,12 @@ inline void parallel_for(size_t n, const std::function<void(size_t)> &fn)
 // straight into its mapped staging buffer (src/main.cpp:1105-1142), with no intermediate copy.
 using ByteAlloc = std::function<uint8_t *(size_t)>;
 using FloatAlloc = std::function<float *(size_t)>;
+using HalfAlloc = std::function<uint16_t *(size_t)>;
 bool png_decode_to(const std::vector<uint8_t> &file, int &w, int &h, const ByteAlloc &alloc, std::string &err);
 bool exr_decode_to(const std::vector<uint8_t> &file, int &w, int &h, const FloatAlloc &alloc, std::string &err);
+// The same decode into RGBA16F (binary16 bits): HALF channels bit for bit, FLOAT / UINT channels through float_to_half,
+// missing alpha = 0x3C00.
+bool exr_decode_half_to(const std::vector<uint8_t> &file, int &w, int &h, const HalfAlloc &alloc, std::string &err);
 
 bool png_decode(const std::vector<uint8_t> &file, int &w, int &h, std::vector<uint8_t> &rgba, std::string &err);
 bool png_encode(const uint8_t *rgba, int w, int h, std::vector<uint8_t> &file, std::string &err);
@@ -64,6 +68,10 @@ bool png_encode(const uint8_t *rgba, int w, int h, std::vector<uint8_t> &file, s
 bool exr_decode(const std::vector<uint8_t> &file, int &w, int &h, std::vector<float> &rgba, std::string &err);
 // 4 x FLOAT channels (A,B,G,R), ZIP (NONE below 16x16), like tinyexr's SaveEXR(data,w,h,4,0,...).
 bool exr_encode(const float *rgba, int w, int h, std::vector<uint8_t> &file, std::string &err);
+// The same file with 4 x HALF channels from RGBA16F pixels.
+bool exr_encode_half(const uint16_t *rgba, int w, int h, std::vector<uint8_t> &file, std::string &err);
+// fp32 -> binary16, round to nearest even (numpy.float16's bits).
+uint16_t float_to_half(float f);
 
 // One PIZ chunk -> nl scanlines, scanline-interleaved (see piz.cpp for the verification status).
 bool piz_decode_block(const uint8_t *comp, size_t ncomp, int width, int nl, const std::vector<int> &chan_size,

@@ -55,12 +55,16 @@ namespace mid {
 
 int set_error(int code, const char *fmt, ...);
 
+// (a failed call is reported once: the runtime's per-thread last error is cleared, so that the NEXT entry point's
+// hipGetLastError after its launch does not report this failure again as its own)
 #define MID_HIP(call)                                                                   \
     do {                                                                                \
         hipError_t e__ = (call);                                                        \
-        if (e__ != hipSuccess)                                                          \
+        if (e__ != hipSuccess) {                                                        \
+            (void)hipGetLastError();                                                    \
             return mid::set_error(MID_ERR_HIP, "%s failed: %s (%s:%d)", #call,          \
                                   hipGetErrorString(e__), __FILE__, __LINE__);          \
+        }                                                                               \
     } while (0)
 
 #define MID_REQUIRE(cond, ...)                                                          \
@@ -104,6 +108,10 @@ void pipe_cache_release(mid_ctx *ctx);
 // call is asynchronous on `s`; anything else goes through the context's page-locked bounce buffers in chunks: copy_h2d
 // returns when the source has been consumed (the last DMAs may still be in flight on `s`), copy_d2h when the data is in dst.
 bool host_is_pinned(const void *p, size_t bytes);
+// Stronger than host_is_pinned, for memory the GPU will STORE into directly: [p, p+bytes) is mapped into the current device's
+// address space as ONE contiguous range that lies inside ONE allocation or registration (hipHostGetDevicePointer of both ends,
+// hipMemGetAddressRange of both mappings).  Any failed query answers false: the caller then takes a copy path instead.
+bool host_range_in_one_mapping(const void *p, size_t bytes);
 int copy_h2d(mid_ctx *ctx, void *dst, const void *src, size_t bytes, hipStream_t s);
 int copy_d2h(mid_ctx *ctx, void *dst, const void *src, size_t bytes, hipStream_t s);
 void bounce_release(mid_ctx *ctx);     // waits for the last chunks and frees both bounce sets
@@ -117,12 +125,13 @@ inline bool stream_is_recording(hipStream_t s)
     return st != hipStreamCaptureStatusNone;
 }
 
-// mid_nlm_temporal with the output format as an argument: out_u8 != 0 writes RGBA8 frames (pack_rgba8 of the
-// normalized pixel) instead of float4 ones -- used by the frame pipeline's u8 variant, not exported.
+// mid_nlm_temporal with the output format as an argument: out_fmt = MID_FMT_RGBA8 writes RGBA8 frames (pack_rgba8 of the
+// normalized pixel), MID_FMT_RGBA16F half frames (pack_rgba16f), MID_FMT_RGBA32F float4 ones -- used by the frame pipeline's
+// u8 / f16 variants, not exported.
 // `corunning` != 0: the caller keeps launches on two streams in flight (the frame pipeline), so the last round of one launch
 // overlaps the first of the next -- the HALF launch shape for a small launch's last round (nlm.hip, tail_split) is not used.
 int nlm_temporal_out(mid_ctx *ctx, const mid_nlm_params *p, const void *const *frames, int n_frames, int k,
-                     int first, int count, void *const *out, int out_u8, void *stream, int corunning = 0);
+                     int first, int count, void *const *out, int out_fmt, void *stream, int corunning = 0);
 
 // ROCTx ranges (csrc/markers.cpp): no-ops unless the process already holds a ROCTx (rocprofv3 --marker-trace preloads one).
 bool markers_active();
@@ -182,6 +191,30 @@ __device__ __forceinline__ uint32_t pack_rgba8(float4 p)
     return pack1(p.x) | (pack1(p.y) << 8) | (pack1(p.z) << 16) | (pack1(p.w) << 24);
 }
 
+// RGBA16F texel: four IEEE binary16 values (R, G, B, A) in one 8-byte load.  The widening to fp32 is exact for every
+// non-NaN half code -- subnormals, +-0, +-Inf -- so an RGBA16F frame without NaN texels filters to the bits of the RGBA32F frame
+// it widens to (v_cvt_f32_f16; a NaN stays a NaN, quieted: a signalling NaN's payload bits are not kept).
+__device__ __forceinline__ float half_lo(uint32_t v) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(v & 0xffffu)); }
+__device__ __forceinline__ float half_hi(uint32_t v) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(v >> 16)); }
+__device__ __forceinline__ float4 decode_rgba16f(uint2 v)
+{
+    return make_float4(half_lo(v.x), half_hi(v.x), half_lo(v.y), half_hi(v.y));
+}
+// fp32 -> binary16, round to nearest even (v_cvt_f16_f32 in the default rounding mode -- never the round-toward-zero
+// packing instructions): overflow gives +-Inf, NaN stays NaN, results below the normal range are f16 subnormals.
+__device__ __forceinline__ uint32_t pack_half2(float lo, float hi)
+{
+    return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)lo) | ((uint32_t)__builtin_bit_cast(uint16_t, (_Float16)hi) << 16);
+}
+__device__ __forceinline__ uint2 pack_rgba16f(float4 p) { return make_uint2(pack_half2(p.x, p.y), pack_half2(p.z, p.w)); }
+
+// Bytes of one texel of a MID_FMT_* (host side: buffer sizes of the frame pipeline and the sharded exchange).
+inline size_t fmt_bytes(int fmt) { return fmt == MID_FMT_RGBA8 ? 4 : fmt == MID_FMT_RGBA16F ? 8 : 16; }
+// Output formats the fused NLM epilogue writes (NlmArgs::out_fmt): the input formats, RGBA8 = pack_rgba8, RGBA16F = pack_rgba16f.
+inline bool fmt_known(int fmt) { return fmt == MID_FMT_RGBA32F || fmt == MID_FMT_RGBA8 || fmt == MID_FMT_RGBA16F; }
+// Device pointers of RGBA16F images are read 8 bytes per texel: they must be 8-byte aligned (hipMalloc'd buffers are).
+inline bool fmt_aligned(int fmt, const void *p) { return fmt != MID_FMT_RGBA16F || ((uintptr_t)p & 7u) == 0; }
+
 // 2-D fetch with the zero-texel policy for out-of-image coordinates (texelFetch of the
 // sampler2D shaders; SURVEY.md 8a: OOB = vec4(0)).
 template <int FMT>
@@ -190,6 +223,7 @@ __device__ __forceinline__ float4 fetch_texture(const void *img, int w, int h, i
     if ((unsigned)x >= (unsigned)w || (unsigned)y >= (unsigned)h) return make_float4(0.f, 0.f, 0.f, 0.f);
     const size_t idx = (size_t)y * w + x;
     if (FMT == MID_FMT_RGBA8) return decode_rgba8(((const uint32_t *)img)[idx]);
+    if (FMT == MID_FMT_RGBA16F) return decode_rgba16f(((const uint2 *)img)[idx]);
     return ((const float4 *)img)[idx];
 }
 
@@ -201,11 +235,12 @@ __device__ __forceinline__ float4 fetch_linear(const void *img, int w, int h, in
     const long idx = (long)y * w + x;
     if (idx < 0 || idx >= (long)w * h) return make_float4(0.f, 0.f, 0.f, 0.f);
     if (FMT == MID_FMT_RGBA8) return decode_rgba8(((const uint32_t *)img)[idx]);
+    if (FMT == MID_FMT_RGBA16F) return decode_rgba16f(((const uint2 *)img)[idx]);
     return ((const float4 *)img)[idx];
 }
 
 // Cooperative fill of an LDS tile of tw x th texels whose top-left texel is image (x0,y0).
-// Consecutive threads take consecutive texels of a tile row: 16 B/lane coalesced HBM reads.
+// Consecutive threads take consecutive texels of a tile row: 16 B/lane (RGBA16F 8 B, RGBA8 4 B) coalesced HBM reads.
 template <int FMT, bool LINEAR>
 __device__ __forceinline__ void fill_tile(float4 *lds, int tw, int th, const void *img, int w, int h,
                                           int x0, int y0, int tid, int nthreads, float rgb_scale = 1.0f, bool *opaque = nullptr)

@@ -97,6 +97,22 @@ bool host_is_pinned(const void *p, size_t bytes)
     return kind_of(p) == Kind::Pinned && kind_of((const char *)p + bytes - 1) == Kind::Pinned;
 }
 
+bool host_range_in_one_mapping(const void *p, size_t bytes)
+{
+    if (!p || bytes == 0) return false;
+    void *d0 = nullptr, *d1 = nullptr;
+    char *last = (char *)const_cast<void *>(p) + bytes - 1;
+    if (hipHostGetDevicePointer(&d0, const_cast<void *>(p), 0) != hipSuccess || !d0 ||
+        hipHostGetDevicePointer(&d1, last, 0) != hipSuccess || !d1) { (void)hipGetLastError(); return false; }
+    if ((char *)d1 - (char *)d0 != (ptrdiff_t)(bytes - 1)) return false;         // both ends mapped, but not as one contiguous range
+    hipDeviceptr_t b0 = nullptr, b1 = nullptr;
+    size_t s0 = 0, s1 = 0;
+    if (hipMemGetAddressRange(&b0, &s0, (hipDeviceptr_t)d0) != hipSuccess ||
+        hipMemGetAddressRange(&b1, &s1, (hipDeviceptr_t)d1) != hipSuccess) { (void)hipGetLastError(); return false; }
+    // the same allocation / registration holds the first and the last byte, and the whole range lies inside it
+    return b0 && b0 == b1 && s0 == s1 && (char *)d0 >= (char *)b0 && (size_t)((char *)d0 - (char *)b0) + bytes <= s0;
+}
+
 int copy_h2d(mid_ctx *ctx, void *dst, const void *src, size_t bytes, hipStream_t s)
 {
     if (bytes == 0) return MID_OK;

@@ -74,7 +74,8 @@ __global__ __launch_bounds__(256) void nlm_generic_kernel(const NlmArgs a, int s
             float4 o;
             if (totw == 0.0f) o = make_float4(1.f, 0.f, 1.f, 1.f);
             else o = make_float4(tot.x / totw, tot.y / totw, tot.z / totw, tot.w / totw);
-            if (a.out_u8) ((uint32_t *)a.outs.p[fz])[idx] = pack_rgba8(o);
+            if (a.out_fmt == MID_FMT_RGBA8) ((uint32_t *)a.outs.p[fz])[idx] = pack_rgba8(o);
+            else if (a.out_fmt == MID_FMT_RGBA16F) ((uint2 *)a.outs.p[fz])[idx] = pack_rgba16f(o);
             else ((float4 *)a.outs.p[fz])[idx] = o;
         } else {
             float4 *wp = (float4 *)(a.W + idx);
@@ -135,7 +136,7 @@ static int check_params(const mid_nlm_params *p)
     MID_REQUIRE(p->search_lo <= 0 && p->search_hi >= 1 && p->patch_lo <= 0 && p->patch_hi >= 1,
                 "nlm: half-open ranges [lo,hi) must contain 0");
     MID_REQUIRE(p->search_hi - p->search_lo <= 64 && p->patch_hi - p->patch_lo <= 16, "nlm: window too large");
-    MID_REQUIRE(p->format == MID_FMT_RGBA32F || p->format == MID_FMT_RGBA8, "nlm: unknown format %d", p->format);
+    MID_REQUIRE(fmt_known(p->format), "nlm: unknown format %d", p->format);
     return MID_OK;
 }
 
@@ -162,11 +163,13 @@ extern "C" int mid_nlm_accum(mid_ctx *ctx, const mid_nlm_params *p, const void *
     if (b.rc) return b.rc;
     if (int rc = check_params(p)) return rc;
     MID_REQUIRE(target && neighbour && W, "nlm_accum: NULL image pointer");
+    MID_REQUIRE(fmt_aligned(p->format, target) && fmt_aligned(p->format, neighbour), "nlm_accum: RGBA16F images must be 8-byte aligned");
     NlmArgs a{};
     a.w = p->width; a.h = p->height; set_scales(a, p->filteringParameter);
     a.target = target; a.neighbour = neighbour; a.W = W;
     a.n_frames = 1; a.k = 0; a.first = 0; a.count = 1;
     if (p->format == MID_FMT_RGBA8) return dispatch_ranges<MID_FMT_RGBA8, false>(ctx, p, a, b.s);
+    if (p->format == MID_FMT_RGBA16F) return dispatch_ranges<MID_FMT_RGBA16F, false>(ctx, p, a, b.s);
     return dispatch_ranges<MID_FMT_RGBA32F, false>(ctx, p, a, b.s);
 }
 
@@ -183,12 +186,13 @@ extern "C" int mid_nlm_temporal(mid_ctx *ctx, const mid_nlm_params *p, const voi
 }
 
 int mid::nlm_temporal_out(mid_ctx *ctx, const mid_nlm_params *p, const void *const *frames, int n_frames, int k,
-                          int first, int count, void *const *out, int out_u8, void *stream, int corunning)
+                          int first, int count, void *const *out, int out_fmt, void *stream, int corunning)
 {
     Bind b(ctx, stream);
     if (b.rc) return b.rc;
     if (int rc = check_params(p)) return rc;
     MID_REQUIRE(frames && out, "nlm_temporal: NULL table");
+    MID_REQUIRE(fmt_known(out_fmt), "nlm_temporal: unknown output format %d", out_fmt);
     MID_REQUIRE(n_frames >= 1 && k >= 0 && count >= 1 && first >= 0 && first + count <= n_frames,
                 "nlm_temporal: bad frame range (n=%d k=%d first=%d count=%d)", n_frames, k, first, count);
     // Output frames are processed in chunks so that chunk + halo fits the by-value frame table.
@@ -200,16 +204,19 @@ int mid::nlm_temporal_out(mid_ctx *ctx, const mid_nlm_params *p, const void *con
         const int hi = c0 + cn - 1 + k > n_frames - 1 ? n_frames - 1 : c0 + cn - 1 + k;
         NlmArgs a{};
         a.w = p->width; a.h = p->height; set_scales(a, p->filteringParameter);
-        a.n_frames = hi - lo + 1; a.k = k; a.first = c0 - lo; a.count = cn; a.out_u8 = out_u8; a.corunning = corunning;
+        a.n_frames = hi - lo + 1; a.k = k; a.first = c0 - lo; a.count = cn; a.out_fmt = out_fmt; a.corunning = corunning;
         for (int f = lo; f <= hi; ++f) {
             MID_REQUIRE(frames[f] != nullptr, "nlm_temporal: frame %d is NULL", f);
+            MID_REQUIRE(fmt_aligned(p->format, frames[f]), "nlm_temporal: frame %d is not 8-byte aligned (RGBA16F)", f);
             a.frames.p[f - lo] = frames[f];
         }
         for (int t = 0; t < cn; ++t) {
             MID_REQUIRE(out[c0 - first + t] != nullptr, "nlm_temporal: out %d is NULL", c0 - first + t);
+            MID_REQUIRE(fmt_aligned(out_fmt, out[c0 - first + t]), "nlm_temporal: out %d is not 8-byte aligned (RGBA16F)", c0 - first + t);
             a.outs.p[t] = out[c0 - first + t];
         }
-        int rc = (p->format == MID_FMT_RGBA8) ? dispatch_ranges<MID_FMT_RGBA8, true>(ctx, p, a, b.s)
+        int rc = p->format == MID_FMT_RGBA8   ? dispatch_ranges<MID_FMT_RGBA8, true>(ctx, p, a, b.s)
+               : p->format == MID_FMT_RGBA16F ? dispatch_ranges<MID_FMT_RGBA16F, true>(ctx, p, a, b.s)
                                               : dispatch_ranges<MID_FMT_RGBA32F, true>(ctx, p, a, b.s);
         if (rc) return rc;
     }

@@ -40,6 +40,8 @@ static int small_window(mid_ctx *ctx, NlmArgs &a, hipStream_t s, int fmt, bool f
 {
     if (fmt == MID_FMT_RGBA8) return fused ? small_launch<SLO, SHI, PLO, PHI, MID_FMT_RGBA8, true>(ctx, a, s, slots, nwg)
                                            : small_launch<SLO, SHI, PLO, PHI, MID_FMT_RGBA8, false>(ctx, a, s, slots, nwg);
+    if (fmt == MID_FMT_RGBA16F) return fused ? small_launch<SLO, SHI, PLO, PHI, MID_FMT_RGBA16F, true>(ctx, a, s, slots, nwg)
+                                             : small_launch<SLO, SHI, PLO, PHI, MID_FMT_RGBA16F, false>(ctx, a, s, slots, nwg);
     return fused ? small_launch<SLO, SHI, PLO, PHI, MID_FMT_RGBA32F, true>(ctx, a, s, slots, nwg)
                  : small_launch<SLO, SHI, PLO, PHI, MID_FMT_RGBA32F, false>(ctx, a, s, slots, nwg);
 }

@@ -28,7 +28,7 @@ struct NlmArgs {
     int slo, shi;          // run-time search range of the RTS instantiations
     // fused temporal mode
     int n_frames, k, first, count;
-    int out_u8;            // fused mode: outputs are RGBA8 frames (pack_rgba8) instead of float4
+    int out_fmt;           // fused mode: MID_FMT_* of the outputs -- float4, RGBA8 (pack_rgba8) or RGBA16F (pack_rgba16f)
     int corunning;         // host side only: launches of the frame pipeline overlap each other (no HALF tail, nlm.hip)
     int fmt;               // MID_FMT_* of the frames, read by the kFmtRuntime instantiations only
     FrameTable frames;
@@ -177,6 +177,12 @@ void nlm_strip_kernel(const NlmArgs a)
                 const float4 t = fetch_texture<MID_FMT_RGBA8>(target, w, h, gx, yb + PLO + m);
                 Tr[m] = t.x * a.sk; Tg[m] = t.y * a.sk; Tb[m] = t.z * a.sk;
             }
+        } else if (a.fmt == MID_FMT_RGBA16F) {
+#pragma unroll
+            for (int m = 0; m < DR; ++m) {
+                const float4 t = fetch_texture<MID_FMT_RGBA16F>(target, w, h, gx, yb + PLO + m);
+                Tr[m] = t.x * a.sk; Tg[m] = t.y * a.sk; Tb[m] = t.z * a.sk;
+            }
         } else {
 #pragma unroll
             for (int m = 0; m < DR; ++m) {
@@ -194,6 +200,7 @@ void nlm_strip_kernel(const NlmArgs a)
     auto fill = [&](const void *nb, bool *opaque) {
         if constexpr (FMT == kFmtRuntime) {
             if (a.fmt == MID_FMT_RGBA8) fill_tile<MID_FMT_RGBA8, false>(lds, LW, LH, nb, w, h, X0 + PLO + slo, Y0 + PLO + slo, tid, NW * 64, a.sk, opaque);
+            else if (a.fmt == MID_FMT_RGBA16F) fill_tile<MID_FMT_RGBA16F, false>(lds, LW, LH, nb, w, h, X0 + PLO + slo, Y0 + PLO + slo, tid, NW * 64, a.sk, opaque);
             else fill_tile<MID_FMT_RGBA32F, false>(lds, LW, LH, nb, w, h, X0 + PLO + slo, Y0 + PLO + slo, tid, NW * 64, a.sk, opaque);
         } else {
             fill_tile<FMT, false>(lds, LW, LH, nb, w, h, X0 + PLO + slo, Y0 + PLO + slo, tid, NW * 64, a.sk, opaque);
@@ -356,7 +363,8 @@ void nlm_strip_kernel(const NlmArgs a)
                 float4 o;
                 if (totw[k] == 0.0f) o = make_float4(1.f, 0.f, 1.f, 1.f);       // normalize.comp:36-38
                 else o = make_float4(tot[k].x / totw[k], tot[k].y / totw[k], tot[k].z / totw[k], tot[k].w / totw[k]);
-                if (a.out_u8) ((uint32_t *)a.outs.p[fz])[idx] = pack_rgba8(o);
+                if (a.out_fmt == MID_FMT_RGBA8) ((uint32_t *)a.outs.p[fz])[idx] = pack_rgba8(o);
+                else if (a.out_fmt == MID_FMT_RGBA16F) ((uint2 *)a.outs.p[fz])[idx] = pack_rgba16f(o);
                 else ((float4 *)a.outs.p[fz])[idx] = o;
             } else {
                 float4 *wp = (float4 *)(a.W + idx);

@@ -7,9 +7,10 @@
 //
 //   upload   : hipMemcpyAsync host frame f -> device ring slot f % RING
 //   compute  : temporal NLM of output frame t over ring slots t-k..t+k (two kernel streams, frames alternate)
-//   download : hipMemcpyAsync device out slot t % 4 -> host   (RGBA32F outputs, and RGBA8 outputs in pageable memory)
+//   download : hipMemcpyAsync device out slot t % 4 -> host   (RGBA32F and RGBA16F outputs, and RGBA8 outputs in pageable memory)
 //              RGBA8 outputs in page-locked memory have NO download stage: the kernel's epilogue stores the packed pixels
-//              straight into the caller's buffer (4 B per pixel = 17-19 GB/s at the kernel's frame rate, a third of the link)
+//              straight into the caller's buffer (4 B per pixel = 17-19 GB/s at the kernel's frame rate, a third of the link);
+//              nor have RGBA16F outputs that lie inside one page-locked allocation each (8 B per pixel)
 //
 // joined only by events: compute(t) waits for upload(t+k); upload(f) waits for the last
 // compute that still reads the slot it overwrites; download(t) waits for compute(t);
@@ -94,7 +95,7 @@ void mid::pipe_cache_release(mid_ctx *ctx)
 // Outputs [first, first+count) of an n-frame host sequence; frames outside that range are only
 // uploaded as far as the temporal window needs them (the halo of a frame block).
 static int sequence_impl(mid_ctx *ctx, const mid_nlm_params *p, const void *const *host_frames,
-                         int n, int k, int first, int count, void *const *host_out, bool out_u8,
+                         int n, int k, int first, int count, void *const *host_out, int out_fmt,
                          int overlap, float *timings_ms)
 {
     Bind b(ctx, nullptr);
@@ -104,14 +105,15 @@ static int sequence_impl(mid_ctx *ctx, const mid_nlm_params *p, const void *cons
     MID_REQUIRE(n >= 1 && k >= 0 && 2 * k + 2 <= kMaxFrames, "sequence_nlm: bad n=%d k=%d", n, k);
     MID_REQUIRE(first >= 0 && count >= 1 && first + count <= n, "sequence_nlm: bad range first=%d count=%d n=%d", first, count, n);
     MID_REQUIRE(p->width > 0 && p->height > 0, "sequence_nlm: bad size");
+    MID_REQUIRE(fmt_known(p->format), "sequence_nlm: unknown format %d", p->format);
     const int f_lo = first - k < 0 ? 0 : first - k;                                  // first frame ever uploaded
     const int f_hi = first + count - 1 + k > n - 1 ? n - 1 : first + count - 1 + k;  // last one
     for (int i = f_lo; i <= f_hi; ++i) MID_REQUIRE(host_frames[i], "sequence_nlm: frame %d is NULL", i);
     for (int i = 0; i < count; ++i) MID_REQUIRE(host_out[i], "sequence_nlm: output %d is NULL", i);
 
     const size_t npix = (size_t)p->width * p->height;
-    const size_t in_bytes = npix * (p->format == MID_FMT_RGBA8 ? 4 : 16);
-    const size_t dl_bytes = npix * (out_u8 ? 4 : 16);            // one output frame, as it is written and downloaded
+    const size_t in_bytes = npix * fmt_bytes(p->format);
+    const size_t dl_bytes = npix * fmt_bytes(out_fmt);            // one output frame, as it is written and downloaded
     const int n_up = f_hi - f_lo + 1;
     // Outputs could be filtered in batches of B frames per launch.  Measured on MI355X (16 x 1080p, 21x21/7x7):
     // B=1 2084 Mpixel/s, B=2 1341, B=4 1472, B=8 1403 -- coarser batches bunch the copies and lose overlap
@@ -127,7 +129,8 @@ static int sequence_impl(mid_ctx *ctx, const mid_nlm_params *p, const void *cons
     // and the events live in the context and are only allocated when a call needs more or larger ones than any call before
     // it (the first call of a context, a larger frame size, a wider window): in a steady stream of sequences nothing is.
     const auto wall0 = std::chrono::steady_clock::now();
-    Range call_range("mid_sequence_nlm frames=%d k=%d outputs=[%d,%d)%s", n, k, first, first + count, out_u8 ? " u8" : "");
+    Range call_range("mid_sequence_nlm frames=%d k=%d outputs=[%d,%d)%s", n, k, first, first + count,
+                          out_fmt == MID_FMT_RGBA8 ? " u8" : out_fmt == MID_FMT_RGBA16F ? " f16" : "");
     std::lock_guard<std::mutex> pipe_lock(ctx->pipe.mu);
     DrainOnExit drain{ctx};
     // Where do the outputs go?  RGBA8 outputs in page-locked memory are written by the kernel itself (`direct`): a pinned buffer is
@@ -137,9 +140,17 @@ static int sequence_impl(mid_ctx *ctx, const mid_nlm_params *p, const void *cons
     // went from 0.19 to 0.67 ms per frame part way into a call and the four output slots then gated every launch (3230-3590
     // Mpixel/s, 5-10 % spread); direct 4040-4080, spread 1-3 %.  RGBA32F outputs (16 B per pixel: more than the link carries at the
     // kernel's rate) and pageable outputs keep the staged download.
+    // RGBA16F outputs (8 B per pixel, about 31 GB/s of posted writes at the kernel's frame rate) are stored directly too, but only
+    // when every output is PROVEN to lie inside one page-locked allocation or registration mapped for this device
+    // (host_range_in_one_mapping): a range whose two ends are pinned but which spans two registrations would fault the GPU.
+    // Measured on 64 x 1080p (profiles/r07_half_rates.txt): the staged download ran at a fraction of the link part way into the call.
     bool out_pinned = true;
     for (int i = 0; i < count; ++i) out_pinned = out_pinned && host_is_pinned(host_out[i], dl_bytes);
-    bool direct = out_u8 && out_pinned;
+    bool direct = out_fmt == MID_FMT_RGBA8 && out_pinned;
+    if (out_fmt == MID_FMT_RGBA16F) {
+        direct = true;
+        for (int i = 0; direct && i < count; ++i) direct = host_range_in_one_mapping(host_out[i], dl_bytes);
+    }
     for (int i = 0; direct && i < count; ++i) {
         void *dp = nullptr;
         if (hipHostGetDevicePointer(&dp, host_out[i], 0) != hipSuccess || !dp) { (void)hipGetLastError(); direct = false; }
@@ -272,9 +283,9 @@ static int sequence_impl(mid_ctx *ctx, const mid_nlm_params *p, const void *cons
         {
             Range nlm_range("nlm %d", b0);
             MID_HIP(hipEventRecord(c0.ev[bi], cs));
-            // out_u8: GetImageFromGPU's u8 conversion (src/main.cpp:97-103) in the kernel's epilogue -- a quarter of the
-            // bytes to write and to download
-            if (int rc = nlm_temporal_out(ctx, p, tbl, need - lo + 1, k, b0 - lo, bn, (void *const *)o, out_u8 ? 1 : 0, cs, 1)) return rc;
+            // RGBA8 outputs: GetImageFromGPU's u8 conversion (src/main.cpp:97-103) in the kernel's epilogue -- a quarter of the
+            // bytes to write and to download; RGBA16F outputs: round to nearest even there -- half of them
+            if (int rc = nlm_temporal_out(ctx, p, tbl, need - lo + 1, k, b0 - lo, bn, (void *const *)o, out_fmt, cs, 1)) return rc;
             MID_HIP(hipEventRecord(c1.ev[bi], cs));
         }
 
@@ -359,14 +370,21 @@ extern "C" int mid_sequence_nlm_range(mid_ctx *ctx, const mid_nlm_params *p, con
                                       int n, int k, int first, int count, mid_pixel *const *host_out,
                                       int overlap, float *timings_ms)
 {
-    return sequence_impl(ctx, p, host_frames, n, k, first, count, (void *const *)host_out, false, overlap, timings_ms);
+    return sequence_impl(ctx, p, host_frames, n, k, first, count, (void *const *)host_out, MID_FMT_RGBA32F, overlap, timings_ms);
 }
 
 extern "C" int mid_sequence_nlm_range_u8(mid_ctx *ctx, const mid_nlm_params *p, const void *const *host_frames,
                                          int n, int k, int first, int count, uint8_t *const *host_out,
                                          int overlap, float *timings_ms)
 {
-    return sequence_impl(ctx, p, host_frames, n, k, first, count, (void *const *)host_out, true, overlap, timings_ms);
+    return sequence_impl(ctx, p, host_frames, n, k, first, count, (void *const *)host_out, MID_FMT_RGBA8, overlap, timings_ms);
+}
+
+extern "C" int mid_sequence_nlm_range_f16(mid_ctx *ctx, const mid_nlm_params *p, const void *const *host_frames,
+                                          int n, int k, int first, int count, uint16_t *const *host_out,
+                                          int overlap, float *timings_ms)
+{
+    return sequence_impl(ctx, p, host_frames, n, k, first, count, (void *const *)host_out, MID_FMT_RGBA16F, overlap, timings_ms);
 }
 
 extern "C" int mid_sequence_nlm(mid_ctx *ctx, const mid_nlm_params *p, const void *const *host_frames,
@@ -385,9 +403,10 @@ extern "C" int mid_nlm_multiframe(mid_ctx *ctx, const mid_nlm_params *p, const v
     if (int rc = refuse_if_recording(ctx->compute, "mid_nlm_multiframe (three streams, host-side waits)")) return rc;
     MID_REQUIRE(p && host_target && host_frames && host_out, "nlm_multiframe: NULL argument");
     MID_REQUIRE(n >= 1 && p->width > 0 && p->height > 0, "nlm_multiframe: bad n=%d or size", n);
+    MID_REQUIRE(fmt_known(p->format), "nlm_multiframe: unknown format %d", p->format);
     for (int i = 0; i < n; ++i) MID_REQUIRE(host_frames[i], "nlm_multiframe: frame %d is NULL", i);
     const size_t npix = (size_t)p->width * p->height;
-    const size_t in_bytes = npix * (p->format == MID_FMT_RGBA8 ? 4 : 16), out_bytes = npix * 16;
+    const size_t in_bytes = npix * fmt_bytes(p->format), out_bytes = npix * 16;
 
     // (clock and cached buffers as in sequence_impl: timings_ms[0] covers the whole call)
     const auto wall0 = std::chrono::steady_clock::now();

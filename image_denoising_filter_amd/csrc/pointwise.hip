@@ -1,6 +1,7 @@
-// pointwise.hip -- the streaming passes: normalize (shaders/normalize.comp:29-44) and the
-// u8 <-> float conversions (src/main.cpp:97-103, :1804-1807; UNORM decode src/texture.cpp:16).
-// All three are HBM-bound: one pixel (16 B of float / 4 B of u8) per lane, grid-stride.
+// pointwise.hip -- the streaming passes: normalize (shaders/normalize.comp:29-44), the
+// u8 <-> float conversions (src/main.cpp:97-103, :1804-1807; UNORM decode src/texture.cpp:16) and the
+// half <-> float conversions of RGBA16F frames (IEEE binary16, round to nearest even).
+// All are HBM-bound: one pixel (16 B of float / 8 B of half / 4 B of u8) per lane, grid-stride.
 #include "common.hpp"
 
 namespace mid {
@@ -52,6 +53,25 @@ __global__ __launch_bounds__(256) void pack_tail_kernel(const float *in, uint8_t
 {
     const size_t i = n0 + threadIdx.x;
     if (i < n) out[i] = (uint8_t)pack1(in[i]);
+}
+
+__global__ __launch_bounds__(256) void unpack_f16_kernel(const uint2 *__restrict__ in, float4 *__restrict__ out, size_t npix)
+{
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < npix; i += (size_t)gridDim.x * 256) out[i] = decode_rgba16f(in[i]);
+}
+
+__global__ __launch_bounds__(256) void pack_f16_kernel(const float4 *__restrict__ in, uint2 *__restrict__ out, size_t npix)
+{
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < npix; i += (size_t)gridDim.x * 256) out[i] = pack_rgba16f(in[i]);
+}
+
+// the last n & 3 values, one per lane
+__global__ __launch_bounds__(256) void f16_tail_kernel(const void *in, void *out, size_t n0, size_t n, int pack)
+{
+    const size_t i = n0 + threadIdx.x;
+    if (i >= n) return;
+    if (pack) ((uint16_t *)out)[i] = __builtin_bit_cast(uint16_t, (_Float16)((const float *)in)[i]);
+    else ((float *)out)[i] = (float)__builtin_bit_cast(_Float16, ((const uint16_t *)in)[i]);
 }
 
 // mid_memset INSIDE A RECORDING (csrc/recording.cpp) is this kernel, not a captured hipMemsetAsync.  With one build of the library the
@@ -140,6 +160,34 @@ extern "C" int mid_pack_u8(mid_ctx *ctx, const float *in, size_t n_values, uint8
     const size_t npix = n_values / 4;
     if (npix) hipLaunchKernelGGL(pack_kernel, dim3(stream_grid(ctx, npix)), dim3(256), 0, b.s, (const float4 *)in, (uint32_t *)out, npix);
     if (n_values & 3) hipLaunchKernelGGL(pack_tail_kernel, dim3(1), dim3(256), 0, b.s, in, out, npix * 4, n_values);
+    MID_HIP(hipGetLastError());
+    return MID_OK;
+}
+
+extern "C" int mid_unpack_f16(mid_ctx *ctx, const uint16_t *in, size_t n_values, float *out, void *stream)
+{
+    Bind b(ctx, stream);
+    if (b.rc) return b.rc;
+    MID_REQUIRE(in && out, "unpack_f16: NULL pointer");
+    MID_REQUIRE(n_values == 0 || (const void *)in != (const void *)out, "unpack_f16: in == out (the conversion is not in place)");
+    MID_REQUIRE(((uintptr_t)in & 7u) == 0 && ((uintptr_t)out & 15u) == 0, "unpack_f16: in must be 8-byte and out 16-byte aligned");
+    const size_t npix = n_values / 4;
+    if (npix) hipLaunchKernelGGL(unpack_f16_kernel, dim3(stream_grid(ctx, npix)), dim3(256), 0, b.s, (const uint2 *)in, (float4 *)out, npix);
+    if (n_values & 3) hipLaunchKernelGGL(f16_tail_kernel, dim3(1), dim3(256), 0, b.s, (const void *)in, (void *)out, npix * 4, n_values, 0);
+    MID_HIP(hipGetLastError());
+    return MID_OK;
+}
+
+extern "C" int mid_pack_f16(mid_ctx *ctx, const float *in, size_t n_values, uint16_t *out, void *stream)
+{
+    Bind b(ctx, stream);
+    if (b.rc) return b.rc;
+    MID_REQUIRE(in && out, "pack_f16: NULL pointer");
+    MID_REQUIRE(n_values == 0 || (const void *)in != (const void *)out, "pack_f16: in == out (the conversion is not in place)");
+    MID_REQUIRE(((uintptr_t)out & 7u) == 0 && ((uintptr_t)in & 15u) == 0, "pack_f16: out must be 8-byte and in 16-byte aligned");
+    const size_t npix = n_values / 4;
+    if (npix) hipLaunchKernelGGL(pack_f16_kernel, dim3(stream_grid(ctx, npix)), dim3(256), 0, b.s, (const float4 *)in, (uint2 *)out, npix);
+    if (n_values & 3) hipLaunchKernelGGL(f16_tail_kernel, dim3(1), dim3(256), 0, b.s, (const void *)in, (void *)out, npix * 4, n_values, 1);
     MID_HIP(hipGetLastError());
     return MID_OK;
 }

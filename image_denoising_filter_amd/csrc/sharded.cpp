@@ -471,10 +471,11 @@ extern "C" int mid_nlm_temporal_sharded(mid_comm *c, const mid_nlm_params *p, co
     int start, count;
     block_of(n_frames, c->world, c->rank, start, count);
     MID_REQUIRE(count == 0 || (block && out), "nlm_temporal_sharded: NULL table");
-    MID_REQUIRE(p->width > 0 && p->height > 0 && (p->format == MID_FMT_RGBA32F || p->format == MID_FMT_RGBA8), "nlm_temporal_sharded: bad params");
+    MID_REQUIRE(p->width > 0 && p->height > 0 && fmt_known(p->format), "nlm_temporal_sharded: bad params");
     for (int i = 0; i < count; ++i) MID_REQUIRE(block[i] && out[i], "nlm_temporal_sharded: frame %d of the block is NULL", i);
+    for (int i = 0; i < count; ++i) MID_REQUIRE(fmt_aligned(p->format, block[i]), "nlm_temporal_sharded: RGBA16F frame %d of the block is not 8-byte aligned", i);
     if (int rc = check_no_alias("nlm_temporal_sharded", "a frame of the block", block, count, (const void *const *)out, count)) return rc;   // once, for all launches
-    const size_t frame_bytes = (size_t)p->width * p->height * (p->format == MID_FMT_RGBA8 ? 4 : 16);
+    const size_t frame_bytes = (size_t)p->width * p->height * fmt_bytes(p->format);   // RGBA16F: half the wire bytes of RGBA32F
 
     std::vector<Xfer> rv, sd;
     if (c->world > 1) halo_plan(n_frames, c->world, k, c->rank, rv, sd);
@@ -541,7 +542,7 @@ extern "C" int mid_nlm_temporal_sharded(mid_comm *c, const mid_nlm_params *p, co
             tbl[f - L.w_lo] = frame_ptr(f);
             MID_REQUIRE(tbl[f - L.w_lo], "nlm_temporal_sharded: frame %d is neither in the block nor in the halo (plan error)", f);
         }
-        return nlm_temporal_out(c->ctx, p, tbl.data(), (int)tbl.size(), k, L.first, L.count, (void *const *)(out + L.off), 0, ls, 0);
+        return nlm_temporal_out(c->ctx, p, tbl.data(), (int)tbl.size(), k, L.first, L.count, (void *const *)(out + L.off), MID_FMT_RGBA32F, ls, 0);
     };
     // interior launches first, on the caller's stream ...
     for (const Launch &L : plan) {

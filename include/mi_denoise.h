@@ -53,8 +53,14 @@ typedef struct mid_weightinfo {
 } mid_weightinfo;
 
 /* Texel format of an input image: the reference creates RGBA32F textures for .exr and
- * RGBA8_UNORM for .png (src/texture.cpp:16, src/main.cpp:333-346). */
-enum { MID_FMT_RGBA32F = 0, MID_FMT_RGBA8 = 1 };
+ * RGBA8_UNORM for .png (src/texture.cpp:16, src/main.cpp:333-346).
+ * MID_FMT_RGBA16F: four IEEE binary16 values in R, G, B, A order, 8 B per pixel -- the buffers renderers and HDR frame
+ * sequences hand over (EXR HALF channels).  Device pointers to RGBA16F images must be 8-byte aligned (MID_ERR_INVALID
+ * otherwise).  Kernels widen each texel exactly (subnormals, +-0, +-Inf), so for frames without NaN texels every filter gives
+ * the bits of the same call with MID_FMT_RGBA32F on the widened frame.  A NaN texel stays a NaN but is quieted by the widening
+ * (v_cvt_f32_f16), so a signalling NaN's bits may differ from a host widening that keeps them.  Accepted wherever a
+ * params.format is read. */
+enum { MID_FMT_RGBA32F = 0, MID_FMT_RGBA8 = 1, MID_FMT_RGBA16F = 2 };
 
 /* Addressing of the bilateral input: bialteral.comp (sampler2D, 2-D texelFetch, out-of-image
  * texel = 0) vs bialteral_linear.comp (samplerBuffer, flat index c + j + i*width: columns wrap
@@ -72,7 +78,7 @@ typedef struct mid_bilateral_params {
     float   colorSigma;
     int32_t radius;   /* window is (2*radius+1)^2; kernels exist for 1..24 */
     int32_t layout;   /* MID_LAYOUT_* (ignored by the layers kernels: always texture) */
-    int32_t format;   /* MID_FMT_* of `in` */
+    int32_t format;   /* MID_FMT_* of `in` (RGBA32F, RGBA8 or RGBA16F; guide layers are always RGBA8) */
 } mid_bilateral_params;
 
 /* Push-constant block of nonlocal.comp (shaders/nonlocal.comp:16-22: {int width; int height;
@@ -90,7 +96,7 @@ typedef struct mid_nlm_params {
     float   filteringParameter;
     int32_t search_lo, search_hi;
     int32_t patch_lo, patch_hi;
-    int32_t format;   /* MID_FMT_* of target and neighbour images */
+    int32_t format;   /* MID_FMT_* of target and neighbour images (RGBA32F, RGBA8 or RGBA16F) */
 } mid_nlm_params;
 
 /* Push-constant block of normalize.comp (shaders/normalize.comp:19-24), 8 B. */
@@ -240,6 +246,11 @@ int mid_normalize(mid_ctx *ctx, const mid_normalize_params *p,
  * The u8 buffer must be 4-byte aligned and the float buffer 16-byte aligned (hipMalloc'd buffers are). */
 int mid_unpack_u8(mid_ctx *ctx, const uint8_t *in, size_t n_values, int flavour, float *out, void *stream);
 int mid_pack_u8(mid_ctx *ctx, const float *in, size_t n_values, uint8_t *out, void *stream);
+/* RGBA16F <-> float: unpack widens each binary16 value exactly; pack rounds to nearest even (overflow -> +-Inf, NaN stays
+ * NaN, f16 subnormals kept) -- the bits of numpy.float16(x).  n_values counts channels.  The half buffer must be 8-byte and the
+ * float buffer 16-byte aligned; in-place is refused (MID_ERR_INVALID); n_values = 0 is a no-op. */
+int mid_unpack_f16(mid_ctx *ctx, const uint16_t *in, size_t n_values, float *out, void *stream);
+int mid_pack_f16(mid_ctx *ctx, const float *in, size_t n_values, uint16_t *out, void *stream);
 
 /* ---- a8: frame pipeline -----------------------------------------------------------------
  * Replaces RecordCommandsOfOverlappingNLM + the ping-pong loop (src/main.cpp:889-989,
@@ -248,8 +259,8 @@ int mid_pack_u8(mid_ctx *ctx, const float *in, size_t n_values, uint8_t *out, vo
  * t-1 is downloaded on a third stream; a device ring keeps 2k+4 frames and four
  * output slots in flight, so each stage may run up to three frames away from its neighbours, and
  * consecutive frames are filtered on two alternating kernel streams (one launch's tail overlaps the next one's head).
- * host_frames/host_out are arrays of n_frames HOST pointers (RGBA32F or RGBA8 per p->format;
- * output always RGBA32F).  Synchronous: returns when every output is on the host.
+ * host_frames/host_out are arrays of n_frames HOST pointers (RGBA32F, RGBA8 or RGBA16F per p->format;
+ * output RGBA32F here, RGBA8 / RGBA16F from the _u8 / _f16 variants).  Synchronous: returns when every output is on the host.
  * The device ring, the output slots and the events are kept in the context between calls (grown when a call needs more
  * or larger ones; mid_ctx_release_cached / mid_ctx_destroy free them), so only a context's first call -- or the first
  * at a larger frame size -- allocates.  Calls on one context are serialised (they share its four streams).
@@ -267,6 +278,14 @@ int mid_sequence_nlm_range(mid_ctx *ctx, const mid_nlm_params *p, const void *co
 int mid_sequence_nlm_range_u8(mid_ctx *ctx, const mid_nlm_params *p, const void *const *host_frames,
                               int n_frames, int k, int first, int count, uint8_t *const *host_out,
                               int overlap, float *timings_ms);
+/* Same, with RGBA16F outputs: the kernel's epilogue rounds each normalized pixel to binary16 (nearest even; the bits of
+ * numpy.float16 of mid_sequence_nlm_range's output) and host_out receives 8 B per pixel -- half the PCIe bytes of RGBA32F.
+ * Input frames may be in any of the three formats.  An output that lies inside ONE page-locked allocation or registration of
+ * this device (mid_alloc_host, mid_host_register, mid_image_load_pinned; checked per output with hipMemGetAddressRange) is
+ * stored by the kernel itself, with no download stage; any other output is downloaded from device slots. */
+int mid_sequence_nlm_range_f16(mid_ctx *ctx, const mid_nlm_params *p, const void *const *host_frames,
+                               int n_frames, int k, int first, int count, uint16_t *const *host_out,
+                               int overlap, float *timings_ms);
 
 /* Debug export: the DEVICE timeline of this context's last mid_sequence_nlm* call, from the events the call recorded on
  * its streams (no profiler: the call ran at its own pace).  All times in ms from the start of the call's first upload.
@@ -281,7 +300,7 @@ int mid_pipe_last_timeline(mid_ctx *ctx, int cap, float *upload_ms /* cap x 2 */
  * streamed from the host.  W = sum over frames of one nonlocal.comp dispatch each (target fixed), then
  * normalize.  overlap != 0 replaces RecordCommandsOfOverlappingNLM (:889-989): frame i+1 is uploaded on
  * the upload stream into the other of two device slots while frame i is being accumulated.
- * host_frames: n_frames HOST pointers (format p->format); host_out: w*h RGBA32F on the host.
+ * host_frames: n_frames HOST pointers (format p->format, any of the three); host_out: w*h RGBA32F on the host.
  * timings_ms (optional, 3 floats): wall, kernel sum, copy sum. */
 int mid_nlm_multiframe(mid_ctx *ctx, const mid_nlm_params *p, const void *host_target,
                        const void *const *host_frames, int n_frames, mid_pixel *host_out,
@@ -306,7 +325,8 @@ int mid_nlm_multiframe(mid_ctx *ctx, const mid_nlm_params *p, const void *host_t
  *   MID_RCCL_LIBRARY (read once, on the first mid_comm_* call) names the library to load instead.
  * mid_nlm_temporal_sharded: `block` = this rank's `count` device frames in order, `out` = `count` device outputs.
  *   Asynchronous on `stream`.  COLLECTIVE: every rank of the communicator must call it, with the same n_frames, k and
- *   frame size -- also a rank that owns no frame.  Everything that can fail locally (arguments, the stream rule below,
+ *   frame size -- also a rank that owns no frame.  Blocks may be RGBA32F, RGBA8 or RGBA16F (p->format; halo frames travel
+ *   at that size, so RGBA16F halves the wire bytes of RGBA32F); outputs are RGBA32F.  Everything that can fail locally (arguments, the stream rule below,
  *   receive-buffer allocation) is checked before the first RCCL call, so a rank that returns an error there has not
  *   entered the exchange; its peers then wait for it, and the caller must mid_comm_abort (or destroy) the communicator
  *   on EVERY rank -- there is no other way out of a half-entered collective.
@@ -368,7 +388,8 @@ int mid_comm_rccl_info(mid_comm *comm, int *nranks, int *user_rank, int *version
  * mid_image_load = LoadImages (src/main.cpp:145-229): ".exr" -> RGBA32F (tinyexr LoadEXR: missing
  * alpha = 1), anything else is decoded as PNG -> RGBA8 (lodepng::decode).  `data` is host memory
  * owned by the library until mid_image_free.  mid_image_save = SaveEXR(rgba,w,h,4,0) (:1699) for
- * MID_FMT_RGBA32F, lodepng::encode (:1717) for MID_FMT_RGBA8.  Host-only: no GPU needed. */
+ * MID_FMT_RGBA32F, lodepng::encode (:1717) for MID_FMT_RGBA8; MID_FMT_RGBA16F writes channels A,B,G,R as HALF with
+ * the FLOAT writer's compression.  Host-only: no GPU needed. */
 typedef struct mid_image {
     int32_t width, height;
     int32_t format;   /* MID_FMT_* */
@@ -382,6 +403,11 @@ void mid_image_free(mid_image *img);
  * src/main.cpp:1105-1142).  Release with mid_image_free_pinned (never mid_image_free). */
 int  mid_image_load_pinned(mid_ctx *ctx, const char *path, mid_image *out);
 int  mid_image_free_pinned(mid_ctx *ctx, mid_image *img);
+/* An .exr as MID_FMT_RGBA16F: HALF channels are copied bit for bit, FLOAT and UINT channels are rounded to nearest even on
+ * the host (overflow -> +-Inf, NaN stays NaN, subnormals kept; UINT through float first), a missing alpha is 1.0 (0x3C00).
+ * PNG files are refused (MID_ERR_INVALID).  ctx == NULL: host memory, released by mid_image_free; otherwise pinned memory of
+ * ctx's device, released by mid_image_free_pinned.  mid_image_load itself still returns RGBA32F for an .exr. */
+int  mid_image_load_f16(mid_ctx *ctx, const char *path, mid_image *out);
 int  mid_image_save(const char *path, const void *data, int32_t width, int32_t height, int32_t format);
 /* The codecs work on the independent blocks of a file in parallel (EXR chunks; PNG: filter rows and 1 MiB deflate segments on
  * encode -- the inflate of a PNG is one serial stream): by default on up to min(16, hardware threads) host threads per call.
