@@ -96,6 +96,8 @@ _SIGNATURES = {
     "mid_sequence_nlm_range_f16": (ctypes.c_int, [_P, ctypes.POINTER(NlmParams), c_void_pp, ctypes.c_int, ctypes.c_int,
                                                   ctypes.c_int, ctypes.c_int, c_void_pp, ctypes.c_int,
                                                   ctypes.POINTER(ctypes.c_float)]),
+    "mid_sequence_bilateral": (ctypes.c_int, [_P, ctypes.POINTER(BilateralParams), c_void_pp, ctypes.c_int, c_void_pp, ctypes.c_int,
+                                              c_void_pp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
     "mid_nlm_multiframe": (ctypes.c_int, [_P, ctypes.POINTER(NlmParams), _P, c_void_pp, ctypes.c_int, _P, ctypes.c_int,
                                           ctypes.POINTER(ctypes.c_float)]),
     "mid_pipe_last_timeline": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int),

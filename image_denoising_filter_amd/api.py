@@ -355,7 +355,8 @@ class Context:
         return tuple(t)
 
     def pipe_last_timeline(self, cap=4096):
-        """mid_pipe_last_timeline: the device timeline of this context's last mid_sequence_nlm* call, from its own events.
+        """mid_pipe_last_timeline: the device timeline of this context's last mid_sequence_nlm* / mid_sequence_bilateral call,
+        from its own events.
         Returns (uploads, outputs): uploads = [(frame, start_ms, end_ms)], outputs = [(frame, kernel_start, kernel_end,
         download_start, download_end)], ms from the start of the call's first upload."""
         up, out = (ctypes.c_float * (2 * cap))(), (ctypes.c_float * (4 * cap))()
@@ -394,6 +395,72 @@ class Context:
                 hin.free()
             if hout is not None:
                 hout.free()
+
+    def sequence_bilateral_pinned(self, hin, hout, w, h, fmt, radius, sigma_s=2.0, sigma_c=0.2, layout="texture", hlayers=None,
+                                  n_layers=0, overlap=True, out_dtype=None):
+        """mid_sequence_bilateral on host pointers the caller already holds: nothing but the C call, so a clock around it
+        measures what a C caller sees.  hlayers: None (plain bilateral) or len(hin) * n_layers RGBA8 host pointers, frame-major.
+        Returns (wall_ms of the whole call, kernel_ms, copy_ms)."""
+        n = len(hin)
+        if len(hout) < n:
+            raise ValueError(f"{n} frames, {len(hout)} output buffers given")
+        lay = {"texture": LAYOUT_TEXTURE, "linear": LAYOUT_LINEAR}[layout]
+        prm = BilateralParams(w, h, sigma_s, sigma_c, radius, lay, fmt)
+        out_fmt = {np.dtype(np.uint8): FMT_RGBA8, np.dtype(np.float16): FMT_RGBA16F,
+                   np.dtype(np.float32): FMT_RGBA32F}[_out_dtype(False, out_dtype)]
+        tl = None
+        if hlayers is not None:
+            if len(hlayers) != n * n_layers:
+                raise ValueError(f"{n} frames x {n_layers} layers, {len(hlayers)} layer pointers given")
+            tl = (ctypes.c_void_p * max(len(hlayers), 1))(*hlayers)
+        t = (ctypes.c_float * 3)()
+        _check(lib.mid_sequence_bilateral(self.handle, ctypes.byref(prm), (ctypes.c_void_p * n)(*hin), n, tl, n_layers,
+                                          (ctypes.c_void_p * n)(*hout[:n]), out_fmt, 1 if overlap else 0, t),
+               "mid_sequence_bilateral")
+        return tuple(t)
+
+    def sequence_bilateral(self, frames, radius, sigma_s=2.0, sigma_c=0.2, layout="texture", layers=None, overlap=True,
+                           pinned=True, pinned_out=True, out_dtype=None):
+        """A whole animation through the overlapped pipeline with the bilateral as its compute stage (mid_sequence_bilateral):
+        output i is ctx.bilateral(frames[i]) -- or, with `layers`, ctx.bilateral_layers(frames[i], layers[i]) -- packed to
+        out_dtype (None = float32; uint8 = the reference's read-back conversion, float16 = round to nearest even) by the kernel.
+        layers: None, or one list per frame of equally many uint8 (h, w, 4) guide layers (texture layout only).
+        pinned / pinned_out = False: the NumPy arrays themselves (pageable memory) are the sources / destinations.
+        Returns (outputs, (wall_ms, kernel_ms, copy_ms))."""
+        frames = _same_frames(frames, "sequence_bilateral")
+        n = len(frames)
+        h, w = frames[0].shape[:2]
+        n_layers, flat = 0, None
+        if layers is not None:
+            if len(layers) != n:
+                raise ValueError(f"sequence_bilateral: {len(layers)} layer lists for {n} frames")
+            n_layers = len(layers[0])
+            flat = []
+            for i, ls in enumerate(layers):
+                if len(ls) != n_layers:
+                    raise ValueError(f"sequence_bilateral: frame {i} has {len(ls)} layers, frame 0 has {n_layers}")
+                for lyr in ls:
+                    lyr = _img(lyr)
+                    if lyr.dtype != np.uint8 or lyr.shape != (h, w, 4):
+                        raise ValueError(f"sequence_bilateral: the layers of frame {i} must be uint8 {(h, w, 4)}, got {lyr.dtype} {lyr.shape}")
+                    flat.append(lyr)
+        out_shape, out_dtype = (h, w, 4), _out_dtype(False, out_dtype)
+        hin = hlay = hout = None
+        try:
+            hin = PinnedFrames(self, frames) if pinned else None
+            hlay = PinnedFrames(self, flat) if pinned and flat else None
+            hout = PinnedFrames(self, n, w * h * 4 * out_dtype.itemsize) if pinned_out else None
+            outs = None if pinned_out else [np.empty(out_shape, out_dtype) for _ in range(n)]
+            lptr = None if flat is None else (hlay.ptrs if hlay is not None else [lyr.ctypes.data for lyr in flat])
+            t = self.sequence_bilateral_pinned(hin.ptrs if pinned else [f.ctypes.data for f in frames],
+                                               hout.ptrs if pinned_out else [o.ctypes.data for o in outs], w, h,
+                                               _fmt_of(frames[0]), radius, sigma_s, sigma_c, layout, lptr, n_layers,
+                                               overlap, out_dtype)
+            return (outs if outs is not None else [hout.array(i, out_shape, out_dtype) for i in range(n)]), t
+        finally:
+            for b in (hin, hlay, hout):
+                if b is not None:
+                    b.free()
 
 
 def _out_dtype(out_u8, out_dtype):

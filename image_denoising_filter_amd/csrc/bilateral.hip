@@ -26,11 +26,21 @@ struct BilArgs {
     float sc, inv_sc;      // sqrt(-kc) and its reciprocal: the tiled kernels carry the range scale in the guide colours
     int tiles_x, tiles_y;
     const void *in;
-    float4 *out;           // plain / fused-layers output
+    void *out;             // plain / fused-layers output, written as out_fmt
     mid_weightinfo *W;     // layers accumulate mode
     int n_layers;
+    int out_fmt;           // MID_FMT_* of `out`: float4, RGBA8 (pack_rgba8) or RGBA16F (pack_rgba16f); a kernarg, so wave-uniform
     const uint32_t *layers[16];
 };
+
+// The plain / fused-layers epilogue: one pixel in the output format of the launch (the frame pipeline's packed outputs; every
+// single-frame entry point passes MID_FMT_RGBA32F).  The same rounding as mid_pack_u8 / mid_pack_f16 of the float4 result.
+__device__ __forceinline__ void store_out(void *out, size_t idx, int fmt, float4 o)
+{
+    if (fmt == MID_FMT_RGBA8) ((uint32_t *)out)[idx] = pack_rgba8(o);
+    else if (fmt == MID_FMT_RGBA16F) ((uint2 *)out)[idx] = pack_rgba16f(o);
+    else ((float4 *)out)[idx] = o;
+}
 
 // Frame tables of the batched plain bilateral (mid_bilateral_batch): passed by value in kernarg space like the NLM
 // kernels' tables.  Single-frame launches pass the empty BilOne instead, so their kernarg block stays small.
@@ -61,14 +71,14 @@ __global__ __launch_bounds__(NW * 64) void bilateral_kernel(const BilArgs a, con
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     unsigned flat;
     const void *in = a.in;
-    float4 *out = a.out;
+    void *out = a.out;
     if constexpr (BATCH) {
         // frames in launch order, tiles remapped inside their frame (every XCD gets a contiguous run of each frame)
         const unsigned tiles = (unsigned)(a.tiles_x * a.tiles_y);
         const unsigned fz = blockIdx.x / tiles;
         flat = xcd_remap_in_frame(blockIdx.x - fz * tiles, tiles, fz);
         in = bt.in.p[fz];
-        out = (float4 *)bt.out.p[fz];
+        out = bt.out.p[fz];
     } else {
         flat = xcd_remap_b(blockIdx.x, gridDim.x);
     }
@@ -255,12 +265,12 @@ __global__ __launch_bounds__(NW * 64) void bilateral_kernel(const BilArgs a, con
         if (gy >= h) break;
         const size_t idx = (size_t)gy * w + gx;
         if (MODE == 0) {
-            out[idx] = make_float4(tot[k].x / totw[k], tot[k].y / totw[k], tot[k].z / totw[k], tot[k].w / totw[k]);
+            store_out(out, idx, a.out_fmt, make_float4(tot[k].x / totw[k], tot[k].y / totw[k], tot[k].z / totw[k], tot[k].w / totw[k]));
         } else if (MODE == 2) {
             float4 o;
             if (totw[k] == 0.0f) o = make_float4(1.f, 0.f, 1.f, 1.f);
             else o = make_float4(tot[k].x / totw[k], tot[k].y / totw[k], tot[k].z / totw[k], tot[k].w / totw[k]);
-            out[idx] = o;
+            store_out(out, idx, a.out_fmt, o);
         } else {
             float4 *wp = (float4 *)(a.W + idx);
             float4 wc = wp[0], nw = wp[1];
@@ -285,13 +295,13 @@ __global__ __launch_bounds__(512) void bilateral_rt_kernel(const BilArgs a, cons
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     unsigned flat;
     const void *in = a.in;
-    float4 *out = a.out;
+    void *out = a.out;
     if constexpr (BATCH) {
         const unsigned tiles = (unsigned)(a.tiles_x * a.tiles_y);
         const unsigned fz = blockIdx.x / tiles;
         flat = xcd_remap_in_frame(blockIdx.x - fz * tiles, tiles, fz);
         in = bt.in.p[fz];
-        out = (float4 *)bt.out.p[fz];
+        out = bt.out.p[fz];
     } else {
         flat = xcd_remap_b(blockIdx.x, gridDim.x);
     }
@@ -386,7 +396,7 @@ __global__ __launch_bounds__(512) void bilateral_rt_kernel(const BilArgs a, cons
             float4 o;
             if (MODE == 2 && totw[k] == 0.0f) o = make_float4(1.f, 0.f, 1.f, 1.f);
             else o = make_float4(tot[k].x / totw[k], tot[k].y / totw[k], tot[k].z / totw[k], tot[k].w / totw[k]);
-            out[idx] = o;
+            store_out(out, idx, a.out_fmt, o);
         }
     }
 }
@@ -437,7 +447,7 @@ __global__ __launch_bounds__(256) void bilateral_generic_kernel(const BilArgs a,
         float4 o;
         if (MODE == 2 && totw == 0.0f) o = make_float4(1.f, 0.f, 1.f, 1.f);
         else o = make_float4(tot.x / totw, tot.y / totw, tot.z / totw, tot.w / totw);
-        a.out[idx] = o;
+        store_out(a.out, idx, a.out_fmt, o);
     }
 }
 
@@ -522,6 +532,21 @@ static void fill_scales(const mid_bilateral_params *p, BilArgs &a)
     a.inv_sc = (float)(1.0 / (double)a.sc);
 }
 
+int bilateral_out(mid_ctx *ctx, const mid_bilateral_params *p, const void *in, const uint32_t *const *layers, int n_layers,
+                  void *out, int out_fmt, hipStream_t s)
+{
+    BilArgs a{};
+    fill_scales(p, a);
+    a.in = in; a.out = out; a.out_fmt = out_fmt;
+    if (!layers) {
+        if (p->layout == MID_LAYOUT_LINEAR) return dispatch_format<true, 0>(ctx, p->format, p->radius, a, s);
+        return dispatch_format<false, 0>(ctx, p->format, p->radius, a, s);
+    }
+    a.n_layers = n_layers;
+    for (int i = 0; i < n_layers; ++i) a.layers[i] = layers[i];
+    return dispatch_format<false, 2>(ctx, p->format, p->radius, a, s);
+}
+
 }  // namespace mid
 
 using namespace mid;
@@ -535,11 +560,7 @@ extern "C" int mid_bilateral(mid_ctx *ctx, const mid_bilateral_params *p, const 
     MID_REQUIRE(in && out, "bilateral: NULL image pointer");
     MID_REQUIRE((const void *)in != (const void *)out, "bilateral: in-place filtering is not supported");
     MID_REQUIRE(fmt_aligned(p->format, in), "bilateral: RGBA16F input must be 8-byte aligned");
-    BilArgs a{};
-    fill_scales(p, a);
-    a.in = in; a.out = (float4 *)out;
-    if (p->layout == MID_LAYOUT_LINEAR) return dispatch_format<true, 0>(ctx, p->format, p->radius, a, b.s);
-    return dispatch_format<false, 0>(ctx, p->format, p->radius, a, b.s);
+    return bilateral_out(ctx, p, in, nullptr, 0, out, MID_FMT_RGBA32F, b.s);
 }
 
 extern "C" int mid_bilateral_layers_accum(mid_ctx *ctx, const mid_bilateral_params *p, const void *in,
@@ -569,14 +590,8 @@ extern "C" int mid_bilateral_layers(mid_ctx *ctx, const mid_bilateral_params *p,
     MID_REQUIRE((const void *)out != in, "bilateral_layers: out is the input image (in-place filtering is not supported)");
     MID_REQUIRE(p->layout == MID_LAYOUT_TEXTURE, "bilateral_layers: layers exist for the texture layout only");
     MID_REQUIRE(n_layers >= 0 && n_layers <= 16, "bilateral_layers: n_layers %d outside 0..16", n_layers);
-    BilArgs a{};
-    fill_scales(p, a);
-    a.in = in; a.out = (float4 *)out; a.n_layers = n_layers;
-    for (int i = 0; i < n_layers; ++i) {
-        MID_REQUIRE(layers[i] != nullptr, "bilateral_layers: layer %d is NULL", i);
-        a.layers[i] = layers[i];
-    }
-    return dispatch_format<false, 2>(ctx, p->format, p->radius, a, b.s);
+    for (int i = 0; i < n_layers; ++i) MID_REQUIRE(layers[i] != nullptr, "bilateral_layers: layer %d is NULL", i);
+    return bilateral_out(ctx, p, in, layers, n_layers, out, MID_FMT_RGBA32F, b.s);
 }
 
 extern "C" int mid_bilateral_batch(mid_ctx *ctx, const mid_bilateral_params *p, const void *const *in,

@@ -60,6 +60,7 @@ struct Options {
     bool run_gpu = true, run_cpu = true;
     std::string modes = "all";      // comma list of: bilateral,layers,linear,nlm,multiframe,overlap
     bool animation = false;         // new capability: temporal NLM of EVERY frame of the sequence
+    std::string animation_filter = "nlm";   // animation mode: nlm | bilateral | linear | layers (the bilateral of every frame)
     int gpus = 1;                   // animation mode: frame blocks over this many devices
     bool share_device = false;      // animation mode: every block on --device (rehearsal of --gpus N on fewer devices)
     bool halo_rccl = false;         // animation mode: blocks resident in HBM, halo frames GPU to GPU over RCCL (mid_nlm_temporal_sharded)
@@ -206,7 +207,13 @@ public:
     // 4-character frame id comes from the file name's stem (the reference's find(".") breaks on "./x").
     void discover(std::vector<std::string> &frames, std::vector<std::string> &layers, bool want_frames, bool want_layers) const
     {
-        const fs::path target(opt.image);
+        discover_for(opt.image, frames, layers, want_frames, want_layers);
+    }
+    // The same rule for any frame of the sequence: its siblings and ITS OWN layers (the layer files whose path holds its id).
+    void discover_for(const std::string &image, std::vector<std::string> &frames, std::vector<std::string> &layers, bool want_frames,
+                      bool want_layers) const
+    {
+        const fs::path target(image);
         fs::path parent = target.parent_path();
         if (parent.empty()) parent = ".";
         const std::string stem = target.stem().string();
@@ -384,12 +391,35 @@ public:
     // the halo is simply uploaded twice and needs no device-to-device exchange.  With --halo rccl every block is
     // uploaded once, stays resident in its GPU's HBM, and the halo frames travel GPU to GPU over RCCL/xGMI
     // (mid_nlm_temporal_sharded, csrc/sharded.cpp).  Outputs: output-animation-<frame file name>.
+    // --animation-filter bilateral | linear | layers runs the bilateral of every frame instead (mid_sequence_bilateral: the same
+    // pipeline with window k = 0, so blocks have no halo); `layers` guides each frame with its OWN RenderElements layers, found
+    // by the discover rule with that frame's id and uploaded beside it.  Outputs: output-animation-<mode name>-<frame file name>,
+    // the single-frame modes' names (nonlinear-bialteral, linear-bialteral, nonlinear-bialteral-layers).
     void RunAnimation()
     {
         std::vector<std::string> frameNames, layerNames;
         discover(frameNames, layerNames, true, false);
         if (frameNames.empty()) throw std::runtime_error("no frames next to " + opt.image);
         const int n = (int)frameNames.size(), k = opt.temporal_k < 0 ? 2 : opt.temporal_k;
+        const bool bil = opt.animation_filter != "nlm", use_layers = opt.animation_filter == "layers";
+        const bool linear = opt.animation_filter == "linear";
+        if (bil && opt.halo_rccl)
+            throw std::runtime_error("--halo rccl is not available with --animation-filter " + opt.animation_filter +
+                                     ": a bilateral frame reads no other frame, there is no halo to exchange");
+        // every frame's own layers, all of them checked before anything is decoded: 1..16 per frame, the same count for all
+        std::vector<std::vector<std::string>> frameLayers(use_layers ? n : 0);
+        int L = 0;
+        for (int i = 0; i < (int)frameLayers.size(); ++i) {
+            std::vector<std::string> none;
+            discover_for(frameNames[i], none, frameLayers[i], false, true);
+            const int li = (int)frameLayers[i].size();
+            if (li < 1 || li > 16)
+                throw std::runtime_error(frameNames[i] + ": " + std::to_string(li) + " layer file(s) found, --animation-filter layers needs 1..16 per frame");
+            if (i > 0 && li != L)
+                throw std::runtime_error(frameNames[i] + ": " + std::to_string(li) + " layer file(s), but " + frameNames[0] + " has " +
+                                         std::to_string(L) + ": every frame needs the same layers");
+            L = li;
+        }
         std::cout << "\tloading " << n << " frames\n";
         // Frames are decoded STRAIGHT INTO pinned host memory (mid_image_load_pinned) and the results land in pinned
         // buffers too, so every copy of the pipeline is a true asynchronous DMA -- the reference memcpy's its decoded
@@ -449,7 +479,9 @@ public:
         decode(0, pinned_budget > 0);                       // (the first frame's size is not known yet: any non-zero budget admits it)
         frame_bytes_guess = (size_t)pin.frames[0].width * pin.frames[0].height *
                             (pin.frames[0].format == MID_FMT_RGBA32F ? 16 : pin.frames[0].format == MID_FMT_RGBA16F ? 8 : 4);
-        const size_t n_pin = pinned_budget / (2 * frame_bytes_guess);     // frames whose input AND output fit the budget
+        const size_t layer_bytes = (size_t)pin.frames[0].width * pin.frames[0].height * 4;       // (RGBA8; checked against the frame below)
+        // frames whose input AND output -- and their layers -- fit the budget
+        const size_t n_pin = pinned_budget / (2 * frame_bytes_guess + (size_t)L * layer_bytes);
         const int io_threads = files_at_a_time(n);
         for_each_file(1, n, [&](int i) {
             decode(i, (size_t)i < n_pin);
@@ -457,7 +489,18 @@ public:
             if (a.width != b.width || a.height != b.height || a.format != b.format)
                 throw std::runtime_error(frameNames[i] + ": size/format differs from the first frame");
         });
-        for (int i = 0; i < n; ++i) { if (pin.frame_pinned[i]) pinned_bytes += 2 * frame_bytes_guess; else ++n_pageable; }
+        // --animation-filter layers: PNG layers decoded as RGBA8 like the single-frame mode, page-locked with their frame
+        std::vector<HostImage> layerImgs((size_t)n * L);             // (released before `pin` and its context)
+        for_each_file(0, (int)layerImgs.size(), [&](int j) {
+            const int i = j / L;
+            layerImgs[j] = load(frameLayers[i][j % L], true, (size_t)i < n_pin ? io : nullptr);
+            const HostImage &l = layerImgs[j];
+            if (l.w != pin.frames[0].width || l.h != pin.frames[0].height || l.format != MID_FMT_RGBA8)
+                throw std::runtime_error(frameNames[i] + ": layer " + frameLayers[i][j % L] + " is not an RGBA8 image of the frame's size");
+        });
+        std::vector<const void *> layer_ptrs(layerImgs.size());
+        for (size_t j = 0; j < layerImgs.size(); ++j) layer_ptrs[j] = layerImgs[j].data();
+        for (int i = 0; i < n; ++i) { if (pin.frame_pinned[i]) pinned_bytes += 2 * frame_bytes_guess + (size_t)L * layer_bytes; else ++n_pageable; }
         const double load_sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - tl0).count();
         const int w = pin.frames[0].width, h = pin.frames[0].height, fmt = pin.frames[0].format;
         // LDR frames come back as RGBA8: the read-back conversion of GetImageFromGPU (:97-103) runs on the device
@@ -488,6 +531,8 @@ public:
         std::vector<mid_ctx *> ctxs(G, nullptr);
         struct CtxGuard { std::vector<mid_ctx *> &v; ~CtxGuard() { for (auto c : v) if (c) mid_ctx_destroy(c); } } guard{ctxs};
         const mid_nlm_params p{w, h, opt.nlm_h, opt.search_lo, opt.search_hi, opt.patch_lo, opt.patch_hi, fmt};
+        const mid_bilateral_params bp{w, h, opt.sigma_s, opt.sigma_c, opt.radius, linear ? MID_LAYOUT_LINEAR : MID_LAYOUT_TEXTURE, fmt};
+        const int out_fmt = hdr ? MID_FMT_RGBA32F : half ? MID_FMT_RGBA16F : MID_FMT_RGBA8;
         const auto tw0 = std::chrono::steady_clock::now();
         for (int g = 0; g < G; ++g) {
             MID_CHECK(mid_ctx_create(opt.share_device ? opt.device : opt.device + g, &ctxs[g]));
@@ -497,7 +542,15 @@ public:
             wp.width = ww; wp.height = wh;
             std::vector<unsigned char> a((size_t)ww * wh * 16, 0), o((size_t)ww * wh * 16);
             const void *wi[2] = {a.data(), a.data()};
-            if (hdr) { mid_pixel *wo[2] = {(mid_pixel *)o.data(), (mid_pixel *)o.data()}; MID_CHECK(mid_sequence_nlm_range(ctxs[g], &wp, wi, 2, k > 0 ? 1 : 0, 0, 1, wo, 1, nullptr)); }
+            if (bil) {
+                mid_bilateral_params wbp = bp;
+                wbp.width = ww; wbp.height = wh;
+                std::vector<unsigned char> lz((size_t)ww * wh * 4, 0);
+                const void *wl[16];
+                for (int l = 0; l < L; ++l) wl[l] = lz.data();
+                void *wo[1] = {o.data()};
+                MID_CHECK(mid_sequence_bilateral(ctxs[g], &wbp, wi, 1, use_layers ? wl : nullptr, L, wo, out_fmt, 1, nullptr));
+            } else if (hdr) { mid_pixel *wo[2] = {(mid_pixel *)o.data(), (mid_pixel *)o.data()}; MID_CHECK(mid_sequence_nlm_range(ctxs[g], &wp, wi, 2, k > 0 ? 1 : 0, 0, 1, wo, 1, nullptr)); }
             else if (half) { uint16_t *wo[2] = {(uint16_t *)o.data(), (uint16_t *)o.data()}; MID_CHECK(mid_sequence_nlm_range_f16(ctxs[g], &wp, wi, 2, k > 0 ? 1 : 0, 0, 1, wo, 1, nullptr)); }
             else { uint8_t *wo[2] = {o.data(), o.data()}; MID_CHECK(mid_sequence_nlm_range_u8(ctxs[g], &wp, wi, 2, k > 0 ? 1 : 0, 0, 1, wo, 1, nullptr)); }
             // (b) the pinned-memory DMA path in both directions at the real frame size (its first use in a process
@@ -592,7 +645,10 @@ public:
                     if (count == 0) return;
                     mid_ctx *ctx = ctxs[g];
                     float t[3] = {0, 0, 0};
-                    if (hdr) {
+                    if (bil) {            // frames are independent: this device's block is a sub-array of frames, layers and outputs
+                        const void *const *lp = use_layers ? layer_ptrs.data() + (size_t)start * L : nullptr;
+                        MID_CHECK(mid_sequence_bilateral(ctx, &bp, in.data() + start, count, lp, L, pin.outs.data() + start, out_fmt, 1, t));
+                    } else if (hdr) {
                         std::vector<mid_pixel *> o(count);
                         for (int i = 0; i < count; ++i) o[i] = (mid_pixel *)pin.outs[start + i];
                         MID_CHECK(mid_sequence_nlm_range(ctx, &p, in.data(), n, k, start, count, o.data(), 1, t));
@@ -614,12 +670,14 @@ public:
         m_execMs = *std::max_element(kern.begin(), kern.end());
         m_transferMs = *std::max_element(copy.begin(), copy.end());
         std::cout << "\tdecoded " << n << " frames into pinned memory in " << load_sec << " sec (" << io_threads << " file(s) at a time); device set-up + warm-up " << warm_sec << " sec\n";
-        std::cout << "\t" << n << " frames, k=" << k << ", " << G << " device(s): " << sec << " sec, "
+        std::cout << "\t" << n << " frames, " << (bil ? opt.animation_filter + " bilateral r=" + std::to_string(opt.radius) : "k=" + std::to_string(k))
+                  << ", " << G << " device(s): " << sec << " sec, "
                   << (double)n * w * h / 1e6 / sec << " Mpixel/s end to end (host frames in -> host frames out)\n";
         // SaveEXR :1699 / lodepng::encode :1717, straight from the pinned results -- one file per worker thread, like the decode
+        const std::string mode_name = !bil ? "" : linear ? "linear-bialteral-" : use_layers ? "nonlinear-bialteral-layers-" : "nonlinear-bialteral-";
         const auto te0 = std::chrono::steady_clock::now();
         for_each_file(0, n, [&](int i) {
-            const std::string name = "output-animation-" + fs::path(frameNames[i]).stem().string() + (hdr || half ? ".exr" : ".png");
+            const std::string name = "output-animation-" + mode_name + fs::path(frameNames[i]).stem().string() + (hdr || half ? ".exr" : ".png");
             if (mid_image_save(out_path(name).c_str(), pin.outs[i], w, h, hdr ? MID_FMT_RGBA32F : half ? MID_FMT_RGBA16F : MID_FMT_RGBA8))
                 throw std::runtime_error(mid_last_error());
         });
@@ -688,6 +746,10 @@ static void usage()
         "  --search LO,HI --patch LO,HI   half-open NLM ranges (default -7,7 and -3,3; 21x21/7x7 is -10,11 and -3,4)\n"
         "  --temporal-k K            multiframe: frames t-K..t+K of the sorted sequence instead of the reference's list\n"
         "  --animation               denoise EVERY sibling frame with temporal NLM (window +-K, default 2) instead of the mode list\n"
+        "  --animation-filter F      animation mode: nlm (default: temporal NLM), or the bilateral of every frame -- bilateral\n"
+        "                            (texture addressing), linear (linear addressing) or layers (guided by each frame's own\n"
+        "                            RenderElements layers, 1..16 per frame, the same count for all); --radius / --sigma-s / --sigma-c\n"
+        "                            apply; outputs output-animation-{nonlinear-bialteral,linear-bialteral,nonlinear-bialteral-layers}-*\n"
         "  --gpus N                  animation mode: split the sequence into N frame blocks, one per device\n"
         "  --halo host|rccl          animation mode with --gpus N: 'host' (default) streams every block plus its K halo frames from host\n"
         "                            memory through the overlapped pipeline; 'rccl' keeps each block resident in its GPU's HBM and\n"
@@ -731,6 +793,11 @@ int main(int argc, char **argv)
         else if (a == "--patch") { if (!pair_arg(next(), opt.patch_lo, opt.patch_hi)) { usage(); return EXIT_FAILURE; } }
         else if (a == "--temporal-k") opt.temporal_k = atoi(next());
         else if (a == "--animation") opt.animation = true;
+        else if (a == "--animation-filter") {
+            opt.animation_filter = next();
+            const std::string &f = opt.animation_filter;
+            if (f != "nlm" && f != "bilateral" && f != "linear" && f != "layers") { std::cerr << "unknown --animation-filter " << f << "\n"; usage(); return EXIT_FAILURE; }
+        }
         else if (a == "--half") opt.half = true;
         else if (a == "--gpus") opt.gpus = atoi(next());
         else if (a == "--share-device") opt.share_device = true;
@@ -759,8 +826,11 @@ int main(int argc, char **argv)
             std::cout << FOREGROUND_COLOR << BACKGROUND_COLOR << "transfer time: " << (unsigned long long)(app.GetTransferMs() * 1e6) << "ns; "
                       << "execution time: " << (unsigned long long)(app.GetExecMs() * 1e6) << "ns\n\n" << CLEAR_COLOR;
         };
+        if (!opt.animation && opt.animation_filter != "nlm") { std::cerr << "--animation-filter needs --animation\n"; return EXIT_FAILURE; }
         if (opt.animation) {
-            std::cout << "######\nRunning on GPU (animation, temporal nonlocal)\n######\n";
+            const std::string &f = opt.animation_filter;
+            std::cout << "######\nRunning on GPU (animation, " << (f == "nlm" ? "temporal nonlocal" : f == "linear" ? "linear bialteral" :
+                                                                 f == "layers" ? "nonlinear bialteral + layers" : "nonlinear bialteral") << ")\n######\n";
             app.RunAnimation();
             print_time();
             return EXIT_SUCCESS;

@@ -12,10 +12,11 @@
 // Device buffers and events of the frame pipeline (csrc/pipeline.cpp), kept from call to call so that a steady stream of
 // sequences pays for hipMalloc / hipEventCreate once: grown on demand, released by mid_ctx_release_cached and mid_ctx_destroy.
 struct mid_pipe_set { std::vector<void *> p; size_t bytes = 0; };
-struct mid_pipe_last { int n_up = 0, nb = 0, f_lo = 0, first = 0, batch = 1; bool direct = false; };   // event layout of the last mid_sequence_nlm* call
+struct mid_pipe_last { int n_up = 0, nb = 0, f_lo = 0, first = 0, batch = 1; bool direct = false; };   // event layout of the last mid_sequence_nlm* / mid_sequence_bilateral call
 struct mid_pipe_cache {
     std::mutex mu;                      // one pipeline call per context at a time: the calls share the context's four streams
-    mid_pipe_set ring, out;             // mid_sequence_nlm*: uploaded frames (2k + 4), output slots (4)
+    mid_pipe_set ring, out;             // mid_sequence_nlm* / mid_sequence_bilateral: uploaded frames (2k + 4), output slots (4)
+    mid_pipe_set layers;                // mid_sequence_bilateral with guide layers: n_layers per ring slot
     mid_pipe_set target, slots, weights, result;   // mid_nlm_multiframe
     std::vector<hipEvent_t> ev;
     mid_pipe_last last;                 // mid_pipe_last_timeline reads the events of the last call back
@@ -113,7 +114,9 @@ bool host_is_pinned(const void *p, size_t bytes);
 // hipMemGetAddressRange of both mappings).  Any failed query answers false: the caller then takes a copy path instead.
 bool host_range_in_one_mapping(const void *p, size_t bytes);
 int copy_h2d(mid_ctx *ctx, void *dst, const void *src, size_t bytes, hipStream_t s);
-int copy_d2h(mid_ctx *ctx, void *dst, const void *src, size_t bytes, hipStream_t s);
+// bounce = true: through the bounce buffers even when both ends of dst are page-locked (a range that spans two registrations,
+// which the runtime's DMA refuses).
+int copy_d2h(mid_ctx *ctx, void *dst, const void *src, size_t bytes, hipStream_t s, bool bounce = false);
 void bounce_release(mid_ctx *ctx);     // waits for the last chunks and frees both bounce sets
 
 // memset as a kernel launch (pointwise.hip): what mid_memset enqueues while its stream records -- see there why.
@@ -132,6 +135,12 @@ inline bool stream_is_recording(hipStream_t s)
 // overlaps the first of the next -- the HALF launch shape for a small launch's last round (nlm.hip, tail_split) is not used.
 int nlm_temporal_out(mid_ctx *ctx, const mid_nlm_params *p, const void *const *frames, int n_frames, int k,
                      int first, int count, void *const *out, int out_fmt, void *stream, int corunning = 0);
+
+// mid_bilateral (layers == nullptr) / mid_bilateral_layers (layers: n_layers RGBA8 guides, texture layout) with the output format as
+// an argument, as nlm_temporal_out: out_fmt = MID_FMT_RGBA8 / MID_FMT_RGBA16F writes pack_rgba8 / pack_rgba16f of the float4 result.
+// No checks: the caller has made those of the public entry points.  Used by the frame pipeline (mid_sequence_bilateral), not exported.
+int bilateral_out(mid_ctx *ctx, const mid_bilateral_params *p, const void *in, const uint32_t *const *layers, int n_layers,
+                  void *out, int out_fmt, hipStream_t s);
 
 // ROCTx ranges (csrc/markers.cpp): no-ops unless the process already holds a ROCTx (rocprofv3 --marker-trace preloads one).
 bool markers_active();

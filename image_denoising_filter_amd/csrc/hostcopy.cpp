@@ -138,12 +138,12 @@ int copy_h2d(mid_ctx *ctx, void *dst, const void *src, size_t bytes, hipStream_t
     return MID_OK;                                                   // src is consumed; the halves stay guarded by their events
 }
 
-int copy_d2h(mid_ctx *ctx, void *dst, const void *src, size_t bytes, hipStream_t s)
+int copy_d2h(mid_ctx *ctx, void *dst, const void *src, size_t bytes, hipStream_t s, bool bounce)
 {
     if (bytes == 0) return MID_OK;
     bool pinned = false;
     if (int rc = classify(dst, bytes, "device-to-host copy", &pinned)) return rc;
-    if (pinned) {
+    if (pinned && !bounce) {
         MID_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s));
         return MID_OK;
     }

@@ -5,12 +5,15 @@
 // followed, without a barrier, by "copy staging -> texture B", descriptor sets swapped by
 // parity, and a fence wait after every submit).  Here the stages run concurrently on their own HIP streams:
 //
-//   upload   : hipMemcpyAsync host frame f -> device ring slot f % RING
-//   compute  : temporal NLM of output frame t over ring slots t-k..t+k (two kernel streams, frames alternate)
+//   upload   : hipMemcpyAsync host frame f -> device ring slot f % RING (mid_sequence_bilateral with guide layers: and frame f's
+//              layers -> the layer ring's slot f % RING, in the same upload interval)
+//   compute  : temporal NLM of output frame t over ring slots t-k..t+k (two kernel streams, frames alternate), or -- for
+//              mid_sequence_bilateral, window k = 0 -- the bilateral (plain, or guided by the layers) of ring slot t alone
 //   download : hipMemcpyAsync device out slot t % 4 -> host   (RGBA32F and RGBA16F outputs, and RGBA8 outputs in pageable memory)
 //              RGBA8 outputs in page-locked memory have NO download stage: the kernel's epilogue stores the packed pixels
 //              straight into the caller's buffer (4 B per pixel = 17-19 GB/s at the kernel's frame rate, a third of the link);
-//              nor have RGBA16F outputs that lie inside one page-locked allocation each (8 B per pixel)
+//              nor have RGBA16F outputs that lie inside one page-locked allocation each (8 B per pixel); the bilateral's RGBA8 and
+//              RGBA16F outputs are stored by the kernel only under that stronger rule, for both formats
 //
 // joined only by events: compute(t) waits for upload(t+k); upload(f) waits for the last
 // compute that still reads the slot it overwrites; download(t) waits for compute(t);
@@ -82,7 +85,7 @@ struct DrainOnExit {
 void mid::pipe_cache_release(mid_ctx *ctx)
 {
     mid_pipe_cache &c = ctx->pipe;
-    for (mid_pipe_set *s : {&c.ring, &c.out, &c.target, &c.slots, &c.weights, &c.result}) {
+    for (mid_pipe_set *s : {&c.ring, &c.out, &c.layers, &c.target, &c.slots, &c.weights, &c.result}) {
         for (void *q : s->p) (void)hipFree(q);
         s->p.clear();
         s->bytes = 0;
@@ -92,27 +95,28 @@ void mid::pipe_cache_release(mid_ctx *ctx)
     c.last = mid_pipe_last{};
 }
 
+// What the compute stage of one pipeline call runs: temporal NLM of output t over ring slots t-k..t+k, or the bilateral of
+// ring slot t alone (k = 0) with, if it has any, the guide layers uploaded beside frame t into the layer ring.
+struct Stage {
+    const char *who;                          // the entry point, for ranges and messages
+    int width, height, format;                // the input frames
+    const mid_nlm_params *nlm;                // temporal NLM, or
+    const mid_bilateral_params *bil;          // bilateral (plain, or layer-guided when host_layers is set)
+    const void *const *host_layers;           // n_layers RGBA8 host layers per frame, frame-major; NULL: plain bilateral
+    int n_layers;
+};
+
 // Outputs [first, first+count) of an n-frame host sequence; frames outside that range are only
-// uploaded as far as the temporal window needs them (the halo of a frame block).
-static int sequence_impl(mid_ctx *ctx, const mid_nlm_params *p, const void *const *host_frames,
-                         int n, int k, int first, int count, void *const *host_out, int out_fmt,
-                         int overlap, float *timings_ms)
+// uploaded as far as the temporal window needs them (the halo of a frame block).  The caller has checked every argument.
+static int run_pipeline(mid_ctx *ctx, const Stage &st, const void *const *host_frames,
+                        int n, int k, int first, int count, void *const *host_out, int out_fmt,
+                        int overlap, float *timings_ms)
 {
-    Bind b(ctx, nullptr);
-    if (b.rc) return b.rc;
-    if (int rc = refuse_if_recording(ctx->compute, "mid_sequence_nlm (four streams, host-side waits)")) return rc;
-    MID_REQUIRE(p && host_frames && host_out, "sequence_nlm: NULL argument");
-    MID_REQUIRE(n >= 1 && k >= 0 && 2 * k + 2 <= kMaxFrames, "sequence_nlm: bad n=%d k=%d", n, k);
-    MID_REQUIRE(first >= 0 && count >= 1 && first + count <= n, "sequence_nlm: bad range first=%d count=%d n=%d", first, count, n);
-    MID_REQUIRE(p->width > 0 && p->height > 0, "sequence_nlm: bad size");
-    MID_REQUIRE(fmt_known(p->format), "sequence_nlm: unknown format %d", p->format);
     const int f_lo = first - k < 0 ? 0 : first - k;                                  // first frame ever uploaded
     const int f_hi = first + count - 1 + k > n - 1 ? n - 1 : first + count - 1 + k;  // last one
-    for (int i = f_lo; i <= f_hi; ++i) MID_REQUIRE(host_frames[i], "sequence_nlm: frame %d is NULL", i);
-    for (int i = 0; i < count; ++i) MID_REQUIRE(host_out[i], "sequence_nlm: output %d is NULL", i);
-
-    const size_t npix = (size_t)p->width * p->height;
-    const size_t in_bytes = npix * fmt_bytes(p->format);
+    const size_t npix = (size_t)st.width * st.height;
+    const size_t in_bytes = npix * fmt_bytes(st.format), layer_bytes = npix * 4;
+    const int n_layers = st.host_layers ? st.n_layers : 0;
     const size_t dl_bytes = npix * fmt_bytes(out_fmt);            // one output frame, as it is written and downloaded
     const int n_up = f_hi - f_lo + 1;
     // Outputs could be filtered in batches of B frames per launch.  Measured on MI355X (16 x 1080p, 21x21/7x7):
@@ -129,7 +133,7 @@ static int sequence_impl(mid_ctx *ctx, const mid_nlm_params *p, const void *cons
     // and the events live in the context and are only allocated when a call needs more or larger ones than any call before
     // it (the first call of a context, a larger frame size, a wider window): in a steady stream of sequences nothing is.
     const auto wall0 = std::chrono::steady_clock::now();
-    Range call_range("mid_sequence_nlm frames=%d k=%d outputs=[%d,%d)%s", n, k, first, first + count,
+    Range call_range("mid_%s frames=%d k=%d outputs=[%d,%d)%s", st.who, n, k, first, first + count,
                           out_fmt == MID_FMT_RGBA8 ? " u8" : out_fmt == MID_FMT_RGBA16F ? " f16" : "");
     std::lock_guard<std::mutex> pipe_lock(ctx->pipe.mu);
     DrainOnExit drain{ctx};
@@ -144,10 +148,22 @@ static int sequence_impl(mid_ctx *ctx, const mid_nlm_params *p, const void *cons
     // when every output is PROVEN to lie inside one page-locked allocation or registration mapped for this device
     // (host_range_in_one_mapping): a range whose two ends are pinned but which spans two registrations would fault the GPU.
     // Measured on 64 x 1080p (profiles/r07_half_rates.txt): the staged download ran at a fraction of the link part way into the call.
+    // The bilateral takes the proven rule for BOTH packed formats: its outputs are stored by the kernel only when every one lies
+    // inside one page-locked allocation or registration; otherwise they are downloaded, and an output that is not inside one
+    // mapping goes through the bounce buffers (`bounced`) even where both of its ends are page-locked.
     bool out_pinned = true;
-    for (int i = 0; i < count; ++i) out_pinned = out_pinned && host_is_pinned(host_out[i], dl_bytes);
+    std::vector<char> bounced(count, 0);
+    if (st.bil) {
+        for (int i = 0; i < count; ++i) { bounced[i] = !host_range_in_one_mapping(host_out[i], dl_bytes); out_pinned = out_pinned && !bounced[i]; }
+    } else {
+        for (int i = 0; i < count; ++i) out_pinned = out_pinned && host_is_pinned(host_out[i], dl_bytes);
+    }
     bool direct = out_fmt == MID_FMT_RGBA8 && out_pinned;
-    if (out_fmt == MID_FMT_RGBA16F) {
+    if (st.bil) {                                 // (and aligned for the kernel's 4 B / 8 B stores)
+        direct = out_fmt != MID_FMT_RGBA32F && out_pinned;
+        for (int i = 0; direct && i < count; ++i) direct = ((uintptr_t)host_out[i] & (fmt_bytes(out_fmt) - 1)) == 0;
+    }
+    else if (out_fmt == MID_FMT_RGBA16F) {
         direct = true;
         for (int i = 0; direct && i < count; ++i) direct = host_range_in_one_mapping(host_out[i], dl_bytes);
     }
@@ -155,13 +171,15 @@ static int sequence_impl(mid_ctx *ctx, const mid_nlm_params *p, const void *cons
         void *dp = nullptr;
         if (hipHostGetDevicePointer(&dp, host_out[i], 0) != hipSuccess || !dp) { (void)hipGetLastError(); direct = false; }
     }
-    mid_pipe_set &dring = ctx->pipe.ring, &dout = ctx->pipe.out;
+    mid_pipe_set &dring = ctx->pipe.ring, &dout = ctx->pipe.out, &dlayers = ctx->pipe.layers;
     if (int rc = reserve(dring, ring, in_bytes)) return rc;
+    if (n_layers) { if (int rc = reserve(dlayers, (size_t)ring * n_layers, layer_bytes)) return rc; }
     if (!direct) { if (int rc = reserve(dout, DEPTH * B, dl_bytes)) return rc; }
     if (int rc = reserve_events(ctx->pipe, 2 * (size_t)n_up + 4 * (size_t)nb)) return rc;
     ctx->pipe.last = mid_pipe_last{};
     struct Events { hipEvent_t *ev; } up0{ctx->pipe.ev.data()}, up1{up0.ev + n_up}, c0{up1.ev + n_up}, c1{c0.ev + nb}, d0{c1.ev + nb}, d1{d0.ev + nb};
     auto slot = [&](int f) { return dring.p[(f - f_lo) % ring]; };
+    auto layer_slot = [&](int f, int l) { return dlayers.p[((f - f_lo) % ring) * n_layers + l]; };   // frame f's layer l
 
     int next_upload = f_lo;
     auto upload = [&](int f) -> int {
@@ -181,6 +199,8 @@ static int sequence_impl(mid_ctx *ctx, const mid_nlm_params *p, const void *cons
         }
         MID_HIP(hipEventRecord(up0.ev[f - f_lo], ctx->upload));
         if (int rc = copy_h2d(ctx, slot(f), host_frames[f], in_bytes, ctx->upload)) return rc;
+        for (int l = 0; l < n_layers; ++l)      // (its guide layers ride in the same upload interval: they share the slot's lifetime)
+            if (int rc = copy_h2d(ctx, layer_slot(f, l), st.host_layers[(size_t)f * n_layers + l], layer_bytes, ctx->upload)) return rc;
         MID_HIP(hipEventRecord(up1.ev[f - f_lo], ctx->upload));
         return MID_OK;
     };
@@ -196,7 +216,8 @@ static int sequence_impl(mid_ctx *ctx, const mid_nlm_params *p, const void *cons
         MID_HIP(hipStreamWaitEvent(ctx->download, c1.ev[bi], 0));
         MID_HIP(hipEventRecord(d0.ev[bi], ctx->download));
         for (int i = 0; i < bn; ++i)
-            if (int rc = copy_d2h(ctx, host_out[b0 - first + i], dout.p[(bi % DEPTH) * B + i], dl_bytes, ctx->download)) return rc;
+            if (int rc = copy_d2h(ctx, host_out[b0 - first + i], dout.p[(bi % DEPTH) * B + i], dl_bytes, ctx->download,
+                                  bounced[b0 - first + i] != 0)) return rc;
         MID_HIP(hipEventRecord(d1.ev[bi], ctx->download));
         return MID_OK;
     };
@@ -280,12 +301,21 @@ static int sequence_impl(mid_ctx *ctx, const mid_nlm_params *p, const void *cons
             if (direct) MID_HIP(hipHostGetDevicePointer((void **)&o[i], host_out[b0 - first + i], 0));
             else o[i] = (mid_pixel *)dout.p[(bi % DEPTH) * B + i];
         }
-        {
+        if (st.nlm) {
             Range nlm_range("nlm %d", b0);
             MID_HIP(hipEventRecord(c0.ev[bi], cs));
             // RGBA8 outputs: GetImageFromGPU's u8 conversion (src/main.cpp:97-103) in the kernel's epilogue -- a quarter of the
             // bytes to write and to download; RGBA16F outputs: round to nearest even there -- half of them
-            if (int rc = nlm_temporal_out(ctx, p, tbl, need - lo + 1, k, b0 - lo, bn, (void *const *)o, out_fmt, cs, 1)) return rc;
+            if (int rc = nlm_temporal_out(ctx, st.nlm, tbl, need - lo + 1, k, b0 - lo, bn, (void *const *)o, out_fmt, cs, 1)) return rc;
+            MID_HIP(hipEventRecord(c1.ev[bi], cs));
+        } else {
+            Range bil_range("bilateral %d", b0);
+            MID_HIP(hipEventRecord(c0.ev[bi], cs));
+            for (int i = 0; i < bn; ++i) {        // (k = 0: output b0 + i reads ring slot b0 + i and its layers only)
+                const uint32_t *lt[16];
+                for (int l = 0; l < n_layers; ++l) lt[l] = (const uint32_t *)layer_slot(b0 + i, l);
+                if (int rc = bilateral_out(ctx, st.bil, slot(b0 + i), st.host_layers ? lt : nullptr, n_layers, o[i], out_fmt, cs)) return rc;
+            }
             MID_HIP(hipEventRecord(c1.ev[bi], cs));
         }
 
@@ -336,7 +366,66 @@ static int sequence_impl(mid_ctx *ctx, const mid_nlm_params *p, const void *cons
     return MID_OK;
 }
 
-// Device timeline of the context's last mid_sequence_nlm* call, read back from the events the call left in the context's
+static int sequence_impl(mid_ctx *ctx, const mid_nlm_params *p, const void *const *host_frames,
+                         int n, int k, int first, int count, void *const *host_out, int out_fmt,
+                         int overlap, float *timings_ms)
+{
+    Bind b(ctx, nullptr);
+    if (b.rc) return b.rc;
+    if (int rc = refuse_if_recording(ctx->compute, "mid_sequence_nlm (four streams, host-side waits)")) return rc;
+    MID_REQUIRE(p && host_frames && host_out, "sequence_nlm: NULL argument");
+    MID_REQUIRE(n >= 1 && k >= 0 && 2 * k + 2 <= kMaxFrames, "sequence_nlm: bad n=%d k=%d", n, k);
+    MID_REQUIRE(first >= 0 && count >= 1 && first + count <= n, "sequence_nlm: bad range first=%d count=%d n=%d", first, count, n);
+    MID_REQUIRE(p->width > 0 && p->height > 0, "sequence_nlm: bad size");
+    MID_REQUIRE(fmt_known(p->format), "sequence_nlm: unknown format %d", p->format);
+    const int f_lo = first - k < 0 ? 0 : first - k;
+    const int f_hi = first + count - 1 + k > n - 1 ? n - 1 : first + count - 1 + k;
+    for (int i = f_lo; i <= f_hi; ++i) MID_REQUIRE(host_frames[i], "sequence_nlm: frame %d is NULL", i);
+    for (int i = 0; i < count; ++i) MID_REQUIRE(host_out[i], "sequence_nlm: output %d is NULL", i);
+    const Stage st{"sequence_nlm", p->width, p->height, p->format, p, nullptr, nullptr, 0};
+    return run_pipeline(ctx, st, host_frames, n, k, first, count, host_out, out_fmt, overlap, timings_ms);
+}
+
+// Frames are independent (k = 0), so a frame block is a sub-array: no _range variant.  Every check comes before anything is
+// queued; an output that is also an input frame or layer would be overwritten by a direct store while uploads that run ahead
+// (or the kernel of another stream) still read it.
+extern "C" int mid_sequence_bilateral(mid_ctx *ctx, const mid_bilateral_params *p, const void *const *host_frames, int n_frames,
+                                      const void *const *host_layers, int n_layers, void *const *host_out, int out_format,
+                                      int overlap, float *timings_ms)
+{
+    Bind b(ctx, nullptr);
+    if (b.rc) return b.rc;
+    if (int rc = refuse_if_recording(ctx->compute, "mid_sequence_bilateral (four streams, host-side waits)")) return rc;
+    MID_REQUIRE(p && host_frames && host_out, "sequence_bilateral: NULL argument");
+    MID_REQUIRE(n_frames >= 1, "sequence_bilateral: n_frames %d < 1", n_frames);
+    MID_REQUIRE(p->width > 0 && p->height > 0, "sequence_bilateral: bad size %dx%d", p->width, p->height);
+    MID_REQUIRE((long)p->width * p->height < (1l << 30), "sequence_bilateral: image too large");
+    MID_REQUIRE(p->spatialSigma > 0.f && p->colorSigma > 0.f, "sequence_bilateral: sigmas must be > 0");
+    MID_REQUIRE(p->radius >= 1 && p->radius <= 24, "sequence_bilateral: radius %d outside 1..24", p->radius);
+    MID_REQUIRE(fmt_known(p->format), "sequence_bilateral: unknown format %d", p->format);
+    MID_REQUIRE(p->layout == MID_LAYOUT_TEXTURE || p->layout == MID_LAYOUT_LINEAR, "sequence_bilateral: unknown layout %d", p->layout);
+    MID_REQUIRE(fmt_known(out_format), "sequence_bilateral: unknown output format %d", out_format);
+    MID_REQUIRE(n_layers >= 0 && n_layers <= 16, "sequence_bilateral: n_layers %d outside 0..16", n_layers);
+    MID_REQUIRE(!host_layers || p->layout == MID_LAYOUT_TEXTURE, "sequence_bilateral: layers exist for the texture layout only");
+    for (int i = 0; i < n_frames; ++i) MID_REQUIRE(host_frames[i], "sequence_bilateral: frame %d is NULL", i);
+    const int n_in = host_layers ? n_frames * n_layers : 0;
+    for (int i = 0; i < n_in; ++i)
+        MID_REQUIRE(host_layers[i], "sequence_bilateral: layer %d of frame %d is NULL", i % n_layers, i / n_layers);
+    for (int i = 0; i < n_frames; ++i) MID_REQUIRE(host_out[i], "sequence_bilateral: output %d is NULL", i);
+    std::vector<const void *> inputs;
+    try {
+        inputs.assign(host_frames, host_frames + n_frames);
+        if (n_in) inputs.insert(inputs.end(), host_layers, host_layers + n_in);
+    } catch (...) {
+        return set_error(MID_ERR_INVALID, "sequence_bilateral: no host memory for the alias check");
+    }
+    if (int rc = check_no_alias("sequence_bilateral", "an input frame or layer of this call", inputs.data(), (int)inputs.size(),
+                                (const void *const *)host_out, n_frames)) return rc;
+    const Stage st{"sequence_bilateral", p->width, p->height, p->format, nullptr, p, host_layers, n_layers};
+    return run_pipeline(ctx, st, host_frames, n_frames, 0, 0, n_frames, host_out, out_format, overlap, timings_ms);
+}
+
+// Device timeline of the context's last mid_sequence_nlm* or mid_sequence_bilateral call, read back from the events the call left in the context's
 // cache (valid until the next pipeline call on this context; no profiler involved, so the call ran at its own pace).
 extern "C" int mid_pipe_last_timeline(mid_ctx *ctx, int cap, float *upload_ms, int *n_uploads, int *first_upload_frame,
                                       float *output_ms, int *n_outputs, int *first_output_frame)
@@ -347,7 +436,7 @@ extern "C" int mid_pipe_last_timeline(mid_ctx *ctx, int cap, float *upload_ms, i
                 "pipe_last_timeline: bad argument");
     std::lock_guard<std::mutex> pipe_lock(ctx->pipe.mu);
     const mid_pipe_last &L = ctx->pipe.last;
-    MID_REQUIRE(L.n_up > 0, "pipe_last_timeline: no mid_sequence_nlm* call has completed on this context");
+    MID_REQUIRE(L.n_up > 0, "pipe_last_timeline: no mid_sequence_nlm* or mid_sequence_bilateral call has completed on this context");
     MID_REQUIRE(cap >= L.n_up && cap >= L.nb, "pipe_last_timeline: cap=%d, need %d uploads and %d outputs", cap, L.n_up, L.nb);
     MID_REQUIRE(ctx->pipe.ev.size() >= 2 * (size_t)L.n_up + 4 * (size_t)L.nb, "pipe_last_timeline: the event cache was released");
     hipEvent_t *up0 = ctx->pipe.ev.data(), *up1 = up0 + L.n_up, *c0 = up1 + L.n_up, *c1 = c0 + L.nb, *d0 = c1 + L.nb, *d1 = d0 + L.nb;
@@ -358,7 +447,7 @@ extern "C" int mid_pipe_last_timeline(mid_ctx *ctx, int cap, float *upload_ms, i
     for (int i = 0; i < L.nb; ++i) {
         MID_HIP(hipEventElapsedTime(&output_ms[4 * i], up0[0], c0[i]));
         MID_HIP(hipEventElapsedTime(&output_ms[4 * i + 1], up0[0], c1[i]));
-        // direct RGBA8 outputs have no download stage: reported as an empty interval at the end of the launch
+        // direct (kernel-stored) outputs have no download stage: reported as an empty interval at the end of the launch
         MID_HIP(hipEventElapsedTime(&output_ms[4 * i + 2], up0[0], L.direct ? c1[i] : d0[i]));
         MID_HIP(hipEventElapsedTime(&output_ms[4 * i + 3], up0[0], L.direct ? c1[i] : d1[i]));
     }

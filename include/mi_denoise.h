@@ -109,7 +109,7 @@ typedef struct mid_ctx mid_ctx;   /* opaque; bound to one HIP device */
  * (src/main.cpp:247-401): a context is one device + one compute stream. */
 int         mid_ctx_create(int device, mid_ctx **out);
 void        mid_ctx_destroy(mid_ctx *ctx);
-/* Frees the device buffers and events the frame pipeline (mid_sequence_nlm*, mid_nlm_multiframe) keeps in the context
+/* Frees the device buffers and events the frame pipeline (mid_sequence_nlm*, mid_sequence_bilateral, mid_nlm_multiframe) keeps in the context
  * between calls -- at 1080p RGBA32F and k = 2 about 400 MB -- and the 32 MiB of page-locked bounce buffers; the next call
  * allocates again.  Without it the cache follows the calls: it grows to the largest frame size seen, and a call whose frames
  * are more than four times smaller than the cached buffers gives those back and keeps buffers of its own size. */
@@ -264,7 +264,9 @@ int mid_pack_f16(mid_ctx *ctx, const float *in, size_t n_values, uint16_t *out, 
  * The device ring, the output slots and the events are kept in the context between calls (grown when a call needs more
  * or larger ones; mid_ctx_release_cached / mid_ctx_destroy free them), so only a context's first call -- or the first
  * at a larger frame size -- allocates.  Calls on one context are serialised (they share its four streams).
- * timings_ms (optional, 3 floats): wall time of the WHOLE call, set-up included; sum of kernel time; sum of copy time. */
+ * timings_ms (optional, 3 floats): wall time of the WHOLE call, set-up included; sum of kernel time; sum of copy time.
+ * The same machinery runs the bilateral over a whole animation: mid_sequence_bilateral below (window k = 0, each frame's guide
+ * layers uploaded with it, RGBA32F / RGBA8 / RGBA16F outputs chosen by an argument). */
 int mid_sequence_nlm(mid_ctx *ctx, const mid_nlm_params *p, const void *const *host_frames,
                      int n_frames, int k, mid_pixel *const *host_out, int overlap, float *timings_ms);
 /* Same, for the output frames [first, first+count) only (host_out has `count` entries): the unit of
@@ -287,11 +289,28 @@ int mid_sequence_nlm_range_f16(mid_ctx *ctx, const mid_nlm_params *p, const void
                                int n_frames, int k, int first, int count, uint16_t *const *host_out,
                                int overlap, float *timings_ms);
 
-/* Debug export: the DEVICE timeline of this context's last mid_sequence_nlm* call, from the events the call recorded on
+/* The same pipeline with the bilateral as its compute stage (window k = 0: output i reads frame i only), for a whole animation.
+ * Output i has the bits of mid_bilateral(p, frame i) -- host_layers == NULL, either layout -- or of mid_bilateral_layers(p, frame
+ * i, its n_layers layers) -- host_layers != NULL, texture layout -- followed by mid_pack_u8 / mid_pack_f16 when out_format is
+ * MID_FMT_RGBA8 / MID_FMT_RGBA16F (the kernel's epilogue packs).  With host_layers set and n_layers == 0 every output pixel is the
+ * magenta sentinel, as in mid_bilateral_layers.  host_frames: n_frames HOST pointers in p->format; host_layers: n_frames *
+ * n_layers RGBA8 HOST pointers, frame-major (frame i's layers are uploaded with frame i); host_out: n_frames HOST pointers.
+ * A packed output (RGBA8 or RGBA16F) is stored by the kernel itself when every output lies inside ONE page-locked allocation or
+ * registration of this device; otherwise the outputs are downloaded from device slots (through the bounce buffers where an
+ * output is not inside one mapping).  Frames are independent: a frame block is a sub-array, so there is no _range variant.
+ * overlap and timings_ms as for mid_sequence_nlm.  MID_ERR_INVALID, before anything is queued, for: a NULL frame, layer or output;
+ * n_layers outside 0..16; layers with MID_LAYOUT_LINEAR; an unknown out_format; an output that is also an input frame or layer
+ * (or appears twice); the parameter checks of mid_bilateral; a call while the context's stream records. */
+int mid_sequence_bilateral(mid_ctx *ctx, const mid_bilateral_params *p, const void *const *host_frames, int n_frames,
+                           const void *const *host_layers, int n_layers, void *const *host_out, int out_format,
+                           int overlap, float *timings_ms);
+
+/* Debug export: the DEVICE timeline of this context's last mid_sequence_nlm* or mid_sequence_bilateral call, from the events the call recorded on
  * its streams (no profiler: the call ran at its own pace).  All times in ms from the start of the call's first upload.
  * upload_ms[2*i], [2*i+1]: start / end of the upload of frame first_upload_frame + i; output_ms[4*j .. 4*j+3]: kernel
  * start, kernel end, download start, download end of output frame first_output_frame + j (output j runs on kernel stream
- * j & 1).  cap = rows either array can hold.  Valid until the next pipeline call or mid_ctx_release_cached on the context.
+ * j & 1; an output stored by the kernel reports an empty download interval at its kernel's end; the upload interval of a
+ * layer-guided mid_sequence_bilateral frame spans the frame and its layers).  cap = rows either array can hold.  Valid until the next pipeline call or mid_ctx_release_cached on the context.
  * Stands where the reference prints its per-submit timestamps (src/main.cpp:1095-1101). */
 int mid_pipe_last_timeline(mid_ctx *ctx, int cap, float *upload_ms /* cap x 2 */, int *n_uploads, int *first_upload_frame,
                            float *output_ms /* cap x 4 */, int *n_outputs, int *first_output_frame);
