@@ -1,6 +1,6 @@
 """image_denoising_filter_amd -- MI355X (gfx950) drop-in for the denoise hot path of
 Reefufui/image_denoising_filter: bilateral (texture / linear / layer-guided), non-local means
-(single frame and temporal), normalize and the u8 pack/unpack, as hand-written HIP behind the
+(single frame, temporal and layer-guided), normalize and the u8 pack/unpack, as hand-written HIP behind the
 C-ABI of include/mi_denoise.h.  Importing this package loads libmi_denoise.so; there is no
 fallback path."""
 from ._lib import EXPORTED, LIB_PATH, BilateralParams, NlmParams, NormalizeParams, lib  # noqa: F401

@@ -284,6 +284,34 @@ class Context:
                               k, first, count, _fmt_of(frames[0]))
         return [self.download(d, (h, w, 4), np.float32) for d in d_out]
 
+    def nlm_layers_accum(self, img, layer, W, hparam=0.5, search=(-7, 7), patch=(-3, 3)):
+        """One dispatch of nonlocal.comp with the patch distance on the uint8 guide `layer` and the colour from `img`:
+        returns W + this layer's sums (mid_nlm_layers_accum)."""
+        img, layer = _img(img), _img(layer)
+        if layer.dtype != np.uint8:
+            raise TypeError("layers are always RGBA8 (src/main.cpp:1396)")
+        h, w = img.shape[:2]
+        W = np.ascontiguousarray(W, dtype=np.float32)
+        d_in, d_l, d_w = self.upload(img), self.upload(layer), self.upload(W)
+        p = NlmParams(w, h, hparam, search[0], search[1], patch[0], patch[1], _fmt_of(img))
+        _check(lib.mid_nlm_layers_accum(self.handle, ctypes.byref(p), d_in.ptr, d_l.ptr, d_w.ptr, None), "mid_nlm_layers_accum")
+        return self.download(d_w, (h, w, 8), np.float32)
+
+    def nlm_layers(self, img, layers, hparam=0.5, search=(-7, 7), patch=(-3, 3)):
+        """Layer-guided NLM: one accumulate dispatch per uint8 guide layer + normalize, fused (mid_nlm_layers)."""
+        img = _img(img)
+        h, w = img.shape[:2]
+        layers = [_img(l) for l in layers]
+        for l in layers:
+            if l.dtype != np.uint8:
+                raise TypeError("layers are always RGBA8 (src/main.cpp:1396)")
+        d_in, d_out = self.upload(img), self.alloc(w * h * 16)
+        d_layers = [self.upload(l) for l in layers]
+        tbl = (ctypes.c_void_p * max(len(d_layers), 1))(*[d.ptr for d in d_layers])
+        p = NlmParams(w, h, hparam, search[0], search[1], patch[0], patch[1], _fmt_of(img))
+        _check(lib.mid_nlm_layers(self.handle, ctypes.byref(p), d_in.ptr, tbl, len(d_layers), d_out.ptr, None), "mid_nlm_layers")
+        return self.download(d_out, (h, w, 4), np.float32)
+
     def normalize(self, W):
         """normalize.comp."""
         W = np.ascontiguousarray(W, dtype=np.float32)
@@ -456,6 +484,66 @@ class Context:
                                                hout.ptrs if pinned_out else [o.ctypes.data for o in outs], w, h,
                                                _fmt_of(frames[0]), radius, sigma_s, sigma_c, layout, lptr, n_layers,
                                                overlap, out_dtype)
+            return (outs if outs is not None else [hout.array(i, out_shape, out_dtype) for i in range(n)]), t
+        finally:
+            for b in (hin, hlay, hout):
+                if b is not None:
+                    b.free()
+
+    def sequence_nlm_layers_pinned(self, hin, hout, w, h, fmt, hlayers, n_layers, overlap=True, hparam=0.5, search=(-7, 7),
+                                   patch=(-3, 3), out_dtype=None):
+        """mid_sequence_nlm_layers on host pointers the caller already holds: nothing but the C call, so a clock around it
+        measures what a C caller sees.  hlayers: len(hin) * n_layers RGBA8 host pointers, frame-major.
+        Returns (wall_ms of the whole call, kernel_ms, copy_ms)."""
+        n = len(hin)
+        if len(hout) < n:
+            raise ValueError(f"{n} frames, {len(hout)} output buffers given")
+        if len(hlayers) != n * n_layers:
+            raise ValueError(f"{n} frames x {n_layers} layers, {len(hlayers)} layer pointers given")
+        prm = NlmParams(w, h, hparam, search[0], search[1], patch[0], patch[1], fmt)
+        out_fmt = {np.dtype(np.uint8): FMT_RGBA8, np.dtype(np.float16): FMT_RGBA16F,
+                   np.dtype(np.float32): FMT_RGBA32F}[_out_dtype(False, out_dtype)]
+        tl = (ctypes.c_void_p * max(len(hlayers), 1))(*hlayers)
+        t = (ctypes.c_float * 3)()
+        _check(lib.mid_sequence_nlm_layers(self.handle, ctypes.byref(prm), (ctypes.c_void_p * n)(*hin), n, tl, n_layers,
+                                           (ctypes.c_void_p * n)(*hout[:n]), out_fmt, 1 if overlap else 0, t),
+               "mid_sequence_nlm_layers")
+        return tuple(t)
+
+    def sequence_nlm_layers(self, frames, layers, overlap=True, hparam=0.5, search=(-7, 7), patch=(-3, 3), pinned=True,
+                            pinned_out=True, out_dtype=None):
+        """A whole animation through the overlapped pipeline with layer-guided NLM as its compute stage (mid_sequence_nlm_layers):
+        output i is ctx.nlm_layers(frames[i], layers[i]) packed to out_dtype (None = float32; uint8 = the reference's read-back
+        conversion, float16 = round to nearest even) by the kernel.
+        layers: one list per frame of equally many uint8 (h, w, 4) guide layers.
+        pinned / pinned_out = False: the NumPy arrays themselves (pageable memory) are the sources / destinations.
+        Returns (outputs, (wall_ms, kernel_ms, copy_ms))."""
+        frames = _same_frames(frames, "sequence_nlm_layers")
+        n = len(frames)
+        h, w = frames[0].shape[:2]
+        if len(layers) != n:
+            raise ValueError(f"sequence_nlm_layers: {len(layers)} layer lists for {n} frames")
+        n_layers = len(layers[0])
+        flat = []
+        for i, ls in enumerate(layers):
+            if len(ls) != n_layers:
+                raise ValueError(f"sequence_nlm_layers: frame {i} has {len(ls)} layers, frame 0 has {n_layers}")
+            for lyr in ls:
+                lyr = _img(lyr)
+                if lyr.dtype != np.uint8 or lyr.shape != (h, w, 4):
+                    raise ValueError(f"sequence_nlm_layers: the layers of frame {i} must be uint8 {(h, w, 4)}, got {lyr.dtype} {lyr.shape}")
+                flat.append(lyr)
+        out_shape, out_dtype = (h, w, 4), _out_dtype(False, out_dtype)
+        hin = hlay = hout = None
+        try:
+            hin = PinnedFrames(self, frames) if pinned else None
+            hlay = PinnedFrames(self, flat) if pinned and flat else None
+            hout = PinnedFrames(self, n, w * h * 4 * out_dtype.itemsize) if pinned_out else None
+            outs = None if pinned_out else [np.empty(out_shape, out_dtype) for _ in range(n)]
+            lptr = hlay.ptrs if hlay is not None else [lyr.ctypes.data for lyr in flat]
+            t = self.sequence_nlm_layers_pinned(hin.ptrs if pinned else [f.ctypes.data for f in frames],
+                                                hout.ptrs if pinned_out else [o.ctypes.data for o in outs], w, h,
+                                                _fmt_of(frames[0]), lptr, n_layers, overlap, hparam, search, patch, out_dtype)
             return (outs if outs is not None else [hout.array(i, out_shape, out_dtype) for i in range(n)]), t
         finally:
             for b in (hin, hlay, hout):

@@ -58,9 +58,9 @@ struct Options {
     bool cpu_blue_bug = true;       // pow(texColor.b - texColor.b, 2), src/main.cpp:1850
     std::vector<int> cpu_threads = {1, 8};     // src/main.cpp:1979,1984
     bool run_gpu = true, run_cpu = true;
-    std::string modes = "all";      // comma list of: bilateral,layers,linear,nlm,multiframe,overlap
+    std::string modes = "all";      // comma list of: bilateral,layers,linear,nlm,multiframe,overlap (all of them: "all"), nlm-layers
     bool animation = false;         // new capability: temporal NLM of EVERY frame of the sequence
-    std::string animation_filter = "nlm";   // animation mode: nlm | bilateral | linear | layers (the bilateral of every frame)
+    std::string animation_filter = "nlm";   // animation mode: nlm | bilateral | linear | layers (the bilateral of every frame) | nlm-layers
     int gpus = 1;                   // animation mode: frame blocks over this many devices
     bool share_device = false;      // animation mode: every block on --device (rehearsal of --gpus N on fewer devices)
     bool halo_rccl = false;         // animation mode: blocks resident in HBM, halo frames GPU to GPU over RCCL (mid_nlm_temporal_sharded)
@@ -323,7 +323,7 @@ public:
             MID_CHECK(mid_alloc(ctx, out_bytes, &dOut));
             { TraceRange r("upload target"); timed(m_transferMs, [&] { MID_CHECK(mid_memcpy_h2d(ctx, dIn, target.data(), target.size(), nullptr)); }); }
             TraceRange dispatch_range("dispatch");
-            if (nlmFilter) {                                                                    // single-frame NLM, :1577-1606 with one frame
+            if (nlmFilter && !useLayers) {                                                      // single-frame NLM, :1577-1606 with one frame
                 mid_nlm_params p{w, h, opt.nlm_h, opt.search_lo, opt.search_hi, opt.patch_lo, opt.patch_hi, fmt};
                 const void *fr[1] = {dIn};
                 mid_pixel *ou[1] = {(mid_pixel *)dOut};
@@ -345,10 +345,17 @@ public:
                     timed(m_transferMs, [&] { MID_CHECK(mid_memcpy_h2d(ctx, d, l.data(), l.size(), nullptr)); });
                     MID_CHECK(mid_stream_sync(ctx, nullptr));             // (the decoded layers are released with `layerImgs`)
                 }
-                mid_bilateral_params p{w, h, opt.sigma_s, opt.sigma_c, opt.radius, MID_LAYOUT_TEXTURE, fmt};
-                timed(m_execMs, [&] {
-                    MID_CHECK(mid_bilateral_layers(ctx, &p, dIn, (const uint32_t *const *)dLayers.data(), (int)dLayers.size(), (mid_pixel *)dOut, nullptr));
-                });
+                if (nlmFilter) {                                                                // the same loop with nonlocal.comp
+                    mid_nlm_params p{w, h, opt.nlm_h, opt.search_lo, opt.search_hi, opt.patch_lo, opt.patch_hi, fmt};
+                    timed(m_execMs, [&] {
+                        MID_CHECK(mid_nlm_layers(ctx, &p, dIn, (const uint32_t *const *)dLayers.data(), (int)dLayers.size(), (mid_pixel *)dOut, nullptr));
+                    });
+                } else {
+                    mid_bilateral_params p{w, h, opt.sigma_s, opt.sigma_c, opt.radius, MID_LAYOUT_TEXTURE, fmt};
+                    timed(m_execMs, [&] {
+                        MID_CHECK(mid_bilateral_layers(ctx, &p, dIn, (const uint32_t *const *)dLayers.data(), (int)dLayers.size(), (mid_pixel *)dOut, nullptr));
+                    });
+                }
                 for (void *d : dLayers) mid_free(ctx, d);
             } else {                                                                            // plain bialteral, :1654-1659
                 mid_bilateral_params p{w, h, opt.sigma_s, opt.sigma_c, opt.radius, linear ? MID_LAYOUT_LINEAR : MID_LAYOUT_TEXTURE, fmt};
@@ -401,11 +408,12 @@ public:
         discover(frameNames, layerNames, true, false);
         if (frameNames.empty()) throw std::runtime_error("no frames next to " + opt.image);
         const int n = (int)frameNames.size(), k = opt.temporal_k < 0 ? 2 : opt.temporal_k;
-        const bool bil = opt.animation_filter != "nlm", use_layers = opt.animation_filter == "layers";
+        const bool nlm_layers = opt.animation_filter == "nlm-layers";                   // layer-guided NLM of every frame
+        const bool bil = opt.animation_filter != "nlm" && !nlm_layers, use_layers = opt.animation_filter == "layers" || nlm_layers;
         const bool linear = opt.animation_filter == "linear";
-        if (bil && opt.halo_rccl)
+        if ((bil || nlm_layers) && opt.halo_rccl)
             throw std::runtime_error("--halo rccl is not available with --animation-filter " + opt.animation_filter +
-                                     ": a bilateral frame reads no other frame, there is no halo to exchange");
+                                     ": its frames read no other frame, there is no halo to exchange");
         // every frame's own layers, all of them checked before anything is decoded: 1..16 per frame, the same count for all
         std::vector<std::vector<std::string>> frameLayers(use_layers ? n : 0);
         int L = 0;
@@ -414,7 +422,7 @@ public:
             discover_for(frameNames[i], none, frameLayers[i], false, true);
             const int li = (int)frameLayers[i].size();
             if (li < 1 || li > 16)
-                throw std::runtime_error(frameNames[i] + ": " + std::to_string(li) + " layer file(s) found, --animation-filter layers needs 1..16 per frame");
+                throw std::runtime_error(frameNames[i] + ": " + std::to_string(li) + " layer file(s) found, --animation-filter " + opt.animation_filter + " needs 1..16 per frame");
             if (i > 0 && li != L)
                 throw std::runtime_error(frameNames[i] + ": " + std::to_string(li) + " layer file(s), but " + frameNames[0] + " has " +
                                          std::to_string(L) + ": every frame needs the same layers");
@@ -489,7 +497,7 @@ public:
             if (a.width != b.width || a.height != b.height || a.format != b.format)
                 throw std::runtime_error(frameNames[i] + ": size/format differs from the first frame");
         });
-        // --animation-filter layers: PNG layers decoded as RGBA8 like the single-frame mode, page-locked with their frame
+        // --animation-filter layers / nlm-layers: PNG layers decoded as RGBA8 like the single-frame mode, page-locked with their frame
         std::vector<HostImage> layerImgs((size_t)n * L);             // (released before `pin` and its context)
         for_each_file(0, (int)layerImgs.size(), [&](int j) {
             const int i = j / L;
@@ -550,6 +558,12 @@ public:
                 for (int l = 0; l < L; ++l) wl[l] = lz.data();
                 void *wo[1] = {o.data()};
                 MID_CHECK(mid_sequence_bilateral(ctxs[g], &wbp, wi, 1, use_layers ? wl : nullptr, L, wo, out_fmt, 1, nullptr));
+            } else if (nlm_layers) {
+                std::vector<unsigned char> lz((size_t)ww * wh * 4, 0);
+                const void *wl[16];
+                for (int l = 0; l < L; ++l) wl[l] = lz.data();
+                void *wo[1] = {o.data()};
+                MID_CHECK(mid_sequence_nlm_layers(ctxs[g], &wp, wi, 1, wl, L, wo, out_fmt, 1, nullptr));
             } else if (hdr) { mid_pixel *wo[2] = {(mid_pixel *)o.data(), (mid_pixel *)o.data()}; MID_CHECK(mid_sequence_nlm_range(ctxs[g], &wp, wi, 2, k > 0 ? 1 : 0, 0, 1, wo, 1, nullptr)); }
             else if (half) { uint16_t *wo[2] = {(uint16_t *)o.data(), (uint16_t *)o.data()}; MID_CHECK(mid_sequence_nlm_range_f16(ctxs[g], &wp, wi, 2, k > 0 ? 1 : 0, 0, 1, wo, 1, nullptr)); }
             else { uint8_t *wo[2] = {o.data(), o.data()}; MID_CHECK(mid_sequence_nlm_range_u8(ctxs[g], &wp, wi, 2, k > 0 ? 1 : 0, 0, 1, wo, 1, nullptr)); }
@@ -648,6 +662,9 @@ public:
                     if (bil) {            // frames are independent: this device's block is a sub-array of frames, layers and outputs
                         const void *const *lp = use_layers ? layer_ptrs.data() + (size_t)start * L : nullptr;
                         MID_CHECK(mid_sequence_bilateral(ctx, &bp, in.data() + start, count, lp, L, pin.outs.data() + start, out_fmt, 1, t));
+                    } else if (nlm_layers) {   // likewise
+                        MID_CHECK(mid_sequence_nlm_layers(ctx, &p, in.data() + start, count, layer_ptrs.data() + (size_t)start * L, L,
+                                                          pin.outs.data() + start, out_fmt, 1, t));
                     } else if (hdr) {
                         std::vector<mid_pixel *> o(count);
                         for (int i = 0; i < count; ++i) o[i] = (mid_pixel *)pin.outs[start + i];
@@ -670,11 +687,11 @@ public:
         m_execMs = *std::max_element(kern.begin(), kern.end());
         m_transferMs = *std::max_element(copy.begin(), copy.end());
         std::cout << "\tdecoded " << n << " frames into pinned memory in " << load_sec << " sec (" << io_threads << " file(s) at a time); device set-up + warm-up " << warm_sec << " sec\n";
-        std::cout << "\t" << n << " frames, " << (bil ? opt.animation_filter + " bilateral r=" + std::to_string(opt.radius) : "k=" + std::to_string(k))
+        std::cout << "\t" << n << " frames, " << (bil ? opt.animation_filter + " bilateral r=" + std::to_string(opt.radius) : nlm_layers ? "nonlocal + " + std::to_string(L) + " layers" : "k=" + std::to_string(k))
                   << ", " << G << " device(s): " << sec << " sec, "
                   << (double)n * w * h / 1e6 / sec << " Mpixel/s end to end (host frames in -> host frames out)\n";
         // SaveEXR :1699 / lodepng::encode :1717, straight from the pinned results -- one file per worker thread, like the decode
-        const std::string mode_name = !bil ? "" : linear ? "linear-bialteral-" : use_layers ? "nonlinear-bialteral-layers-" : "nonlinear-bialteral-";
+        const std::string mode_name = nlm_layers ? "nonlinear-nlm-layers-" : !bil ? "" : linear ? "linear-bialteral-" : use_layers ? "nonlinear-bialteral-layers-" : "nonlinear-bialteral-";
         const auto te0 = std::chrono::steady_clock::now();
         for_each_file(0, n, [&](int i) {
             const std::string name = "output-animation-" + mode_name + fs::path(frameNames[i]).stem().string() + (hdr || half ? ".exr" : ".png");
@@ -738,7 +755,9 @@ static void usage()
         "  image                     target .png or .exr (default Animations/CornellBox/Animation01_LDR_0000.png)\n"
         "  --outdir DIR              where output-*.{png,exr} go (default .)\n"
         "  --device N                HIP device (default 0)\n"
-        "  --modes LIST              comma list of bilateral,layers,linear,nlm,multiframe,overlap (default all, reference order)\n"
+        "  --modes LIST              comma list of bilateral,layers,linear,nlm,multiframe,overlap (default all, reference order),\n"
+        "                            and nlm-layers (not part of all): NLM with its weights taken from the image's RenderElements\n"
+        "                            layers (--nlm-h / --search / --patch apply), output output-nonlinear-nlm-layers.{png,exr}\n"
         "  --gpu-only | --cpu-only   run only the GPU modes / only the CPU runs\n"
         "  --radius R                bilateral window radius (default 20 = TEXEL_WINDOW)\n"
         "  --sigma-s S --sigma-c C   bilateral sigmas (default 2.0 0.2)\n"
@@ -749,7 +768,9 @@ static void usage()
         "  --animation-filter F      animation mode: nlm (default: temporal NLM), or the bilateral of every frame -- bilateral\n"
         "                            (texture addressing), linear (linear addressing) or layers (guided by each frame's own\n"
         "                            RenderElements layers, 1..16 per frame, the same count for all); --radius / --sigma-s / --sigma-c\n"
-        "                            apply; outputs output-animation-{nonlinear-bialteral,linear-bialteral,nonlinear-bialteral-layers}-*\n"
+        "                            apply; outputs output-animation-{nonlinear-bialteral,linear-bialteral,nonlinear-bialteral-layers}-*;\n"
+        "                            or nlm-layers: NLM of every frame guided by its own layers (the same layer rules as layers;\n"
+        "                            --nlm-h / --search / --patch apply), outputs output-animation-nonlinear-nlm-layers-*\n"
         "  --gpus N                  animation mode: split the sequence into N frame blocks, one per device\n"
         "  --halo host|rccl          animation mode with --gpus N: 'host' (default) streams every block plus its K halo frames from host\n"
         "                            memory through the overlapped pipeline; 'rccl' keeps each block resident in its GPU's HBM and\n"
@@ -796,7 +817,7 @@ int main(int argc, char **argv)
         else if (a == "--animation-filter") {
             opt.animation_filter = next();
             const std::string &f = opt.animation_filter;
-            if (f != "nlm" && f != "bilateral" && f != "linear" && f != "layers") { std::cerr << "unknown --animation-filter " << f << "\n"; usage(); return EXIT_FAILURE; }
+            if (f != "nlm" && f != "bilateral" && f != "linear" && f != "layers" && f != "nlm-layers") { std::cerr << "unknown --animation-filter " << f << "\n"; usage(); return EXIT_FAILURE; }
         }
         else if (a == "--half") opt.half = true;
         else if (a == "--gpus") opt.gpus = atoi(next());
@@ -818,7 +839,8 @@ int main(int argc, char **argv)
         else if (!have_image) { opt.image = a; have_image = true; }
         else { usage(); return EXIT_FAILURE; }
     }
-    auto want = [&](const char *m) { return opt.modes == "all" || ("," + opt.modes + ",").find(std::string(",") + m + ",") != std::string::npos; };
+    auto listed = [&](const char *m) { return ("," + opt.modes + ",").find(std::string(",") + m + ",") != std::string::npos; };
+    auto want = [&](const char *m) { return opt.modes == "all" || listed(m); };
 
     try {
         DenoiseApplication app{opt};
@@ -830,7 +852,7 @@ int main(int argc, char **argv)
         if (opt.animation) {
             const std::string &f = opt.animation_filter;
             std::cout << "######\nRunning on GPU (animation, " << (f == "nlm" ? "temporal nonlocal" : f == "linear" ? "linear bialteral" :
-                                                                 f == "layers" ? "nonlinear bialteral + layers" : "nonlinear bialteral") << ")\n######\n";
+                                                                 f == "layers" ? "nonlinear bialteral + layers" : f == "nlm-layers" ? "nonlocal + layers" : "nonlinear bialteral") << ")\n######\n";
             app.RunAnimation();
             print_time();
             return EXIT_SUCCESS;
@@ -842,6 +864,8 @@ int main(int argc, char **argv)
             if (want("nlm")) { std::cout << "######\nRunning on GPU (nonlocal)\n######\n"; app.RunOnGPU(true, true, false, false, false); print_time(); }
             if (want("multiframe")) { std::cout << "######\nRunning on GPU (multiframe nonlocal)\n######\n"; app.RunOnGPU(true, true, true, false, false); print_time(); }
             if (want("overlap")) { std::cout << "######\nRunning on GPU (multiframe nonlocal + overlapping)\n######\n"; app.RunOnGPU(true, true, true, true, false); print_time(); }
+            // (not part of `all`: the reference has no NLM with layers, and the default run writes exactly the reference's files)
+            if (listed("nlm-layers")) { std::cout << "######\nRunning on GPU (nonlocal + layers)\n######\n"; app.RunOnGPU(true, true, false, false, true); print_time(); }
         }
         if (opt.run_cpu) {
             for (int threads : opt.cpu_threads) {

@@ -142,6 +142,15 @@ int nlm_temporal_out(mid_ctx *ctx, const mid_nlm_params *p, const void *const *f
 int bilateral_out(mid_ctx *ctx, const mid_bilateral_params *p, const void *in, const uint32_t *const *layers, int n_layers,
                   void *out, int out_fmt, hipStream_t s);
 
+// The parameter checks of mid_nlm_accum (size, filteringParameter, window limits, format): nlm.hip, shared with nlm_layers.hip.
+int nlm_check_params(const mid_nlm_params *p);
+
+// mid_nlm_layers with the output format as an argument (MID_FMT_RGBA8 / MID_FMT_RGBA16F: pack_rgba8 / pack_rgba16f of the float4
+// result), as bilateral_out.  No checks: the caller has made those of the public entry points.  nlm_layers.hip; used by the frame
+// pipeline (mid_sequence_nlm_layers), not exported.
+int nlm_layers_out(mid_ctx *ctx, const mid_nlm_params *p, const void *in, const uint32_t *const *layers, int n_layers, void *out,
+                   int out_fmt, hipStream_t s);
+
 // ROCTx ranges (csrc/markers.cpp): no-ops unless the process already holds a ROCTx (rocprofv3 --marker-trace preloads one).
 bool markers_active();
 void range_push(const char *name);

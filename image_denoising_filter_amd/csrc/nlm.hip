@@ -127,7 +127,7 @@ static int dispatch_ranges(mid_ctx *ctx, const mid_nlm_params *p, NlmArgs &a, hi
     return MID_OK;
 }
 
-static int check_params(const mid_nlm_params *p)
+int nlm_check_params(const mid_nlm_params *p)
 {
     MID_REQUIRE(p != nullptr, "nlm: params is NULL");
     MID_REQUIRE(p->width > 0 && p->height > 0, "nlm: bad size %dx%d", p->width, p->height);
@@ -161,7 +161,7 @@ extern "C" int mid_nlm_accum(mid_ctx *ctx, const mid_nlm_params *p, const void *
 {
     Bind b(ctx, stream);
     if (b.rc) return b.rc;
-    if (int rc = check_params(p)) return rc;
+    if (int rc = nlm_check_params(p)) return rc;
     MID_REQUIRE(target && neighbour && W, "nlm_accum: NULL image pointer");
     MID_REQUIRE(fmt_aligned(p->format, target) && fmt_aligned(p->format, neighbour), "nlm_accum: RGBA16F images must be 8-byte aligned");
     NlmArgs a{};
@@ -190,7 +190,7 @@ int mid::nlm_temporal_out(mid_ctx *ctx, const mid_nlm_params *p, const void *con
 {
     Bind b(ctx, stream);
     if (b.rc) return b.rc;
-    if (int rc = check_params(p)) return rc;
+    if (int rc = nlm_check_params(p)) return rc;
     MID_REQUIRE(frames && out, "nlm_temporal: NULL table");
     MID_REQUIRE(fmt_known(out_fmt), "nlm_temporal: unknown output format %d", out_fmt);
     MID_REQUIRE(n_frames >= 1 && k >= 0 && count >= 1 && first >= 0 && first + count <= n_frames,

@@ -5,10 +5,11 @@
 // followed, without a barrier, by "copy staging -> texture B", descriptor sets swapped by
 // parity, and a fence wait after every submit).  Here the stages run concurrently on their own HIP streams:
 //
-//   upload   : hipMemcpyAsync host frame f -> device ring slot f % RING (mid_sequence_bilateral with guide layers: and frame f's
-//              layers -> the layer ring's slot f % RING, in the same upload interval)
+//   upload   : hipMemcpyAsync host frame f -> device ring slot f % RING (mid_sequence_bilateral with guide layers and
+//              mid_sequence_nlm_layers: and frame f's layers -> the layer ring's slot f % RING, in the same upload interval)
 //   compute  : temporal NLM of output frame t over ring slots t-k..t+k (two kernel streams, frames alternate), or -- for
-//              mid_sequence_bilateral, window k = 0 -- the bilateral (plain, or guided by the layers) of ring slot t alone
+//              mid_sequence_bilateral, window k = 0 -- the bilateral (plain, or guided by the layers) of ring slot t alone, or --
+//              for mid_sequence_nlm_layers, k = 0 -- NLM of ring slot t guided by its layers
 //   download : hipMemcpyAsync device out slot t % 4 -> host   (RGBA32F and RGBA16F outputs, and RGBA8 outputs in pageable memory)
 //              RGBA8 outputs in page-locked memory have NO download stage: the kernel's epilogue stores the packed pixels
 //              straight into the caller's buffer (4 B per pixel = 17-19 GB/s at the kernel's frame rate, a third of the link);
@@ -96,13 +97,15 @@ void mid::pipe_cache_release(mid_ctx *ctx)
 }
 
 // What the compute stage of one pipeline call runs: temporal NLM of output t over ring slots t-k..t+k, or the bilateral of
-// ring slot t alone (k = 0) with, if it has any, the guide layers uploaded beside frame t into the layer ring.
+// ring slot t alone (k = 0) with, if it has any, the guide layers uploaded beside frame t into the layer ring, or layer-guided NLM
+// of ring slot t alone (k = 0) with those layers.
 struct Stage {
     const char *who;                          // the entry point, for ranges and messages
     int width, height, format;                // the input frames
     const mid_nlm_params *nlm;                // temporal NLM, or
-    const mid_bilateral_params *bil;          // bilateral (plain, or layer-guided when host_layers is set)
-    const void *const *host_layers;           // n_layers RGBA8 host layers per frame, frame-major; NULL: plain bilateral
+    const mid_bilateral_params *bil;          // bilateral (plain, or layer-guided when host_layers is set), or
+    const mid_nlm_params *nlm_layers;         // layer-guided NLM
+    const void *const *host_layers;           // n_layers RGBA8 host layers per frame, frame-major; NULL: plain bilateral / no layers
     int n_layers;
 };
 
@@ -148,18 +151,19 @@ static int run_pipeline(mid_ctx *ctx, const Stage &st, const void *const *host_f
     // when every output is PROVEN to lie inside one page-locked allocation or registration mapped for this device
     // (host_range_in_one_mapping): a range whose two ends are pinned but which spans two registrations would fault the GPU.
     // Measured on 64 x 1080p (profiles/r07_half_rates.txt): the staged download ran at a fraction of the link part way into the call.
-    // The bilateral takes the proven rule for BOTH packed formats: its outputs are stored by the kernel only when every one lies
-    // inside one page-locked allocation or registration; otherwise they are downloaded, and an output that is not inside one
-    // mapping goes through the bounce buffers (`bounced`) even where both of its ends are page-locked.
+    // The bilateral and layer-guided NLM take the proven rule for BOTH packed formats: their outputs are stored by the kernel only
+    // when every one lies inside one page-locked allocation or registration; otherwise they are downloaded, and an output that is
+    // not inside one mapping goes through the bounce buffers (`bounced`) even where both of its ends are page-locked.
+    const bool proven = st.bil || st.nlm_layers;
     bool out_pinned = true;
     std::vector<char> bounced(count, 0);
-    if (st.bil) {
+    if (proven) {
         for (int i = 0; i < count; ++i) { bounced[i] = !host_range_in_one_mapping(host_out[i], dl_bytes); out_pinned = out_pinned && !bounced[i]; }
     } else {
         for (int i = 0; i < count; ++i) out_pinned = out_pinned && host_is_pinned(host_out[i], dl_bytes);
     }
     bool direct = out_fmt == MID_FMT_RGBA8 && out_pinned;
-    if (st.bil) {                                 // (and aligned for the kernel's 4 B / 8 B stores)
+    if (proven) {                                 // (and aligned for the kernel's 4 B / 8 B stores)
         direct = out_fmt != MID_FMT_RGBA32F && out_pinned;
         for (int i = 0; direct && i < count; ++i) direct = ((uintptr_t)host_out[i] & (fmt_bytes(out_fmt) - 1)) == 0;
     }
@@ -308,6 +312,15 @@ static int run_pipeline(mid_ctx *ctx, const Stage &st, const void *const *host_f
             // bytes to write and to download; RGBA16F outputs: round to nearest even there -- half of them
             if (int rc = nlm_temporal_out(ctx, st.nlm, tbl, need - lo + 1, k, b0 - lo, bn, (void *const *)o, out_fmt, cs, 1)) return rc;
             MID_HIP(hipEventRecord(c1.ev[bi], cs));
+        } else if (st.nlm_layers) {
+            Range nlm_range("nlm_layers %d", b0);
+            MID_HIP(hipEventRecord(c0.ev[bi], cs));
+            for (int i = 0; i < bn; ++i) {        // (k = 0: output b0 + i reads ring slot b0 + i and its layers only)
+                const uint32_t *lt[16];
+                for (int l = 0; l < n_layers; ++l) lt[l] = (const uint32_t *)layer_slot(b0 + i, l);
+                if (int rc = nlm_layers_out(ctx, st.nlm_layers, slot(b0 + i), lt, n_layers, o[i], out_fmt, cs)) return rc;
+            }
+            MID_HIP(hipEventRecord(c1.ev[bi], cs));
         } else {
             Range bil_range("bilateral %d", b0);
             MID_HIP(hipEventRecord(c0.ev[bi], cs));
@@ -382,7 +395,7 @@ static int sequence_impl(mid_ctx *ctx, const mid_nlm_params *p, const void *cons
     const int f_hi = first + count - 1 + k > n - 1 ? n - 1 : first + count - 1 + k;
     for (int i = f_lo; i <= f_hi; ++i) MID_REQUIRE(host_frames[i], "sequence_nlm: frame %d is NULL", i);
     for (int i = 0; i < count; ++i) MID_REQUIRE(host_out[i], "sequence_nlm: output %d is NULL", i);
-    const Stage st{"sequence_nlm", p->width, p->height, p->format, p, nullptr, nullptr, 0};
+    const Stage st{"sequence_nlm", p->width, p->height, p->format, p, nullptr, nullptr, nullptr, 0};
     return run_pipeline(ctx, st, host_frames, n, k, first, count, host_out, out_fmt, overlap, timings_ms);
 }
 
@@ -421,11 +434,43 @@ extern "C" int mid_sequence_bilateral(mid_ctx *ctx, const mid_bilateral_params *
     }
     if (int rc = check_no_alias("sequence_bilateral", "an input frame or layer of this call", inputs.data(), (int)inputs.size(),
                                 (const void *const *)host_out, n_frames)) return rc;
-    const Stage st{"sequence_bilateral", p->width, p->height, p->format, nullptr, p, host_layers, n_layers};
+    const Stage st{"sequence_bilateral", p->width, p->height, p->format, nullptr, p, nullptr, host_layers, n_layers};
     return run_pipeline(ctx, st, host_frames, n_frames, 0, 0, n_frames, host_out, out_format, overlap, timings_ms);
 }
 
-// Device timeline of the context's last mid_sequence_nlm* or mid_sequence_bilateral call, read back from the events the call left in the context's
+// Layer-guided NLM of every frame: mid_sequence_bilateral's schedule and checks with nlm_layers_out as the compute stage.
+extern "C" int mid_sequence_nlm_layers(mid_ctx *ctx, const mid_nlm_params *p, const void *const *host_frames, int n_frames,
+                                       const void *const *host_layers, int n_layers, void *const *host_out, int out_format,
+                                       int overlap, float *timings_ms)
+{
+    Bind b(ctx, nullptr);
+    if (b.rc) return b.rc;
+    if (int rc = refuse_if_recording(ctx->compute, "mid_sequence_nlm_layers (four streams, host-side waits)")) return rc;
+    MID_REQUIRE(p && host_frames && host_out, "sequence_nlm_layers: NULL argument");
+    MID_REQUIRE(n_frames >= 1, "sequence_nlm_layers: n_frames %d < 1", n_frames);
+    if (int rc = nlm_check_params(p)) return rc;
+    MID_REQUIRE(fmt_known(out_format), "sequence_nlm_layers: unknown output format %d", out_format);
+    MID_REQUIRE(n_layers >= 0 && n_layers <= 16, "sequence_nlm_layers: n_layers %d outside 0..16", n_layers);
+    MID_REQUIRE(host_layers || n_layers == 0, "sequence_nlm_layers: host_layers is NULL");
+    for (int i = 0; i < n_frames; ++i) MID_REQUIRE(host_frames[i], "sequence_nlm_layers: frame %d is NULL", i);
+    const int n_in = host_layers ? n_frames * n_layers : 0;
+    for (int i = 0; i < n_in; ++i)
+        MID_REQUIRE(host_layers[i], "sequence_nlm_layers: layer %d of frame %d is NULL", i % n_layers, i / n_layers);
+    for (int i = 0; i < n_frames; ++i) MID_REQUIRE(host_out[i], "sequence_nlm_layers: output %d is NULL", i);
+    std::vector<const void *> inputs;
+    try {
+        inputs.assign(host_frames, host_frames + n_frames);
+        if (n_in) inputs.insert(inputs.end(), host_layers, host_layers + n_in);
+    } catch (...) {
+        return set_error(MID_ERR_INVALID, "sequence_nlm_layers: no host memory for the alias check");
+    }
+    if (int rc = check_no_alias("sequence_nlm_layers", "an input frame or layer of this call", inputs.data(), (int)inputs.size(),
+                                (const void *const *)host_out, n_frames)) return rc;
+    const Stage st{"sequence_nlm_layers", p->width, p->height, p->format, nullptr, nullptr, p, n_layers ? host_layers : nullptr, n_layers};
+    return run_pipeline(ctx, st, host_frames, n_frames, 0, 0, n_frames, host_out, out_format, overlap, timings_ms);
+}
+
+// Device timeline of the context's last mid_sequence_nlm*, mid_sequence_bilateral or mid_sequence_nlm_layers call, read back from the events the call left in the context's
 // cache (valid until the next pipeline call on this context; no profiler involved, so the call ran at its own pace).
 extern "C" int mid_pipe_last_timeline(mid_ctx *ctx, int cap, float *upload_ms, int *n_uploads, int *first_upload_frame,
                                       float *output_ms, int *n_outputs, int *first_output_frame)

@@ -232,6 +232,26 @@ int mid_nlm_temporal(mid_ctx *ctx, const mid_nlm_params *p,
                      int n_frames, int k, int first, int count,
                      mid_pixel *const *out /* host array of `count` device ptrs */, void *stream);
 
+/* ---- a4b: layer-guided non-local means ---------------------------------------------------
+ * The layer-guided loop of src/main.cpp:1610-1623 with nonlocal.comp as its kernel instead of bialteral_layers.comp: the patch
+ * distance is taken on an RGBA8 guide layer (albedo, normal, depth ...; texels c/255, out-of-image texels 0) and the colour from
+ * the input image (RGBA32F, RGBA8 or RGBA16F per p->format; out-of-image texels 0).
+ * mid_nlm_layers_accum = one dispatch for guide layer `layer_rgba8`: for each pixel p and search offset s,
+ *   d = sum over the patch of |G(p+q) - G(p+s+q)|^2_rgb,  w = exp(-d/h^2),  W[p].weightColor += w * in(p+s),
+ *   W[p].normWeight += w, plus 0.001 once per dispatch (nonlocal.comp:32-33, :55-62).
+ * mid_nlm_layers = n_layers such dispatches into a zeroed W (layers in the given order) followed by mid_normalize, fused in one
+ * kernel: no WeightInfo traffic, and the bits of that chain of calls.  With n_layers == 0 every pixel is the magenta sentinel,
+ * as in mid_bilateral_layers.  With one layer equal to an RGBA8 input the result is mid_nlm_temporal(k = 0) of that input to
+ * rounding (the guide's distances are summed as exact integers here).
+ * The windows and their limits are mid_nlm_accum's: the two tuned windows run on an LDS-tiled kernel, every other one on a
+ * per-pixel kernel.  MID_ERR_INVALID for: the parameter checks of mid_nlm_accum; a NULL pointer; n_layers outside 0..16; an
+ * RGBA16F input that is not 8-byte aligned; `out` equal to `in` or to a layer (mid_nlm_layers). */
+int mid_nlm_layers_accum(mid_ctx *ctx, const mid_nlm_params *p, const void *in,
+                         const uint32_t *layer_rgba8, mid_weightinfo *W, void *stream);
+int mid_nlm_layers(mid_ctx *ctx, const mid_nlm_params *p, const void *in,
+                   const uint32_t *const *layers_rgba8 /* host array of device ptrs */,
+                   int n_layers, mid_pixel *out, void *stream);
+
 /* ---- a5: normalize ----------------------------------------------------------------------
  * One dispatch of shaders/normalize.comp (RecordCommandsOfExecuteAndTransfer(normKernel=true)):
  * out = weightColor / normWeight, or (1,0,1,1) where normWeight == 0; bindings {0: out; 1: W}. */
@@ -305,7 +325,20 @@ int mid_sequence_bilateral(mid_ctx *ctx, const mid_bilateral_params *p, const vo
                            const void *const *host_layers, int n_layers, void *const *host_out, int out_format,
                            int overlap, float *timings_ms);
 
-/* Debug export: the DEVICE timeline of this context's last mid_sequence_nlm* or mid_sequence_bilateral call, from the events the call recorded on
+/* The same pipeline with layer-guided NLM as its compute stage (window k = 0), for a whole animation: output i has the bits of
+ * mid_nlm_layers(p, frame i, its n_layers layers) followed by mid_pack_u8 / mid_pack_f16 when out_format is MID_FMT_RGBA8 /
+ * MID_FMT_RGBA16F (the kernel's epilogue packs).  host_frames: n_frames HOST pointers in p->format; host_layers: n_frames *
+ * n_layers RGBA8 HOST pointers, frame-major (frame i's layers are uploaded with frame i; NULL only with n_layers == 0, which gives
+ * magenta outputs); host_out: n_frames HOST pointers.  Outputs are stored by the kernel or downloaded by the rule of
+ * mid_sequence_bilateral; frames are independent, so a frame block is a sub-array.  overlap and timings_ms as for
+ * mid_sequence_nlm.  MID_ERR_INVALID, before anything is queued, for: a NULL frame, layer or output; n_layers outside 0..16; an
+ * unknown out_format; an output that is also an input frame or layer (or appears twice); the parameter checks of mid_nlm_accum;
+ * a call while the context's stream records. */
+int mid_sequence_nlm_layers(mid_ctx *ctx, const mid_nlm_params *p, const void *const *host_frames, int n_frames,
+                            const void *const *host_layers, int n_layers, void *const *host_out, int out_format,
+                            int overlap, float *timings_ms);
+
+/* Debug export: the DEVICE timeline of this context's last mid_sequence_nlm*, mid_sequence_bilateral or mid_sequence_nlm_layers call, from the events the call recorded on
  * its streams (no profiler: the call ran at its own pace).  All times in ms from the start of the call's first upload.
  * upload_ms[2*i], [2*i+1]: start / end of the upload of frame first_upload_frame + i; output_ms[4*j .. 4*j+3]: kernel
  * start, kernel end, download start, download end of output frame first_output_frame + j (output j runs on kernel stream

@@ -15,6 +15,8 @@ extern "C" int mid_normalize(mid_ctx *, const mid_normalize_params *, const mid_
 int mid::nlm_temporal_out(mid_ctx *, const mid_nlm_params *, const void *const *, int, int, int, int, void *const *, int, void *, int) { return MID_ERR_UNSUPPORTED; }
 int mid::fill_bytes(mid_ctx *, void *, int, size_t, hipStream_t) { return MID_ERR_UNSUPPORTED; }      // (pointwise.hip: kernels are not part of this CPU build)
 int mid::bilateral_out(mid_ctx *, const mid_bilateral_params *, const void *, const uint32_t *const *, int, void *, int, hipStream_t) { return MID_ERR_UNSUPPORTED; }   // (bilateral.hip)
+int mid::nlm_layers_out(mid_ctx *, const mid_nlm_params *, const void *, const uint32_t *const *, int, void *, int, hipStream_t) { return MID_ERR_UNSUPPORTED; }   // (nlm_layers.hip)
+int mid::nlm_check_params(const mid_nlm_params *) { return MID_ERR_UNSUPPORTED; }   // (nlm.hip)
 
 int main()
 {
