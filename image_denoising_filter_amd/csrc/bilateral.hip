@@ -494,7 +494,7 @@ static int dispatch_radius(mid_ctx *ctx, int radius, BilArgs &a, hipStream_t s, 
         }
     }
     // (unreachable for the plain bilateral: its single tile fits LDS for every legal radius; only the two-tile
-    // layer modes at r > 16 get here, and those are never batched)
+    // layer modes at r > 17 get here, and those are never batched)
     if (n_frames != 1) return set_error(MID_ERR_UNSUPPORTED, "bilateral: no batched kernel for radius %d", radius);
     dim3 grid(cdiv(a.w, 16), cdiv(a.h, 16));
     hipLaunchKernelGGL((bilateral_generic_kernel<FMT, LINEAR, MODE>), grid, dim3(256), 0, s, a, radius);

@@ -87,9 +87,10 @@ typedef struct mid_bilateral_params {
  * HALF-OPEN [lo,hi) like the shader's loops (:36-44): the reference is search [-7,7) patch
  * [-3,3); the 21x21 / 7x7 benchmark configuration is search [-10,11) patch [-3,4).
  * Limits: both ranges contain 0, search width <= 64, patch width <= 16.  Every search range and every patch of the forms
- * [-P,P) and [-P,P] up to 16 wide runs on the LDS-tiled kernel (as long as the tile fits 160 KB: search width <= 51 at a
- * 7x7 patch); anything else (lopsided patches, wider windows) is computed by a per-pixel kernel -- same results, the
- * reference's S^2 * P^2 work. */
+ * [-P,P) and [-P,P] up to 16 wide runs on the LDS-tiled kernel as long as its tile of (64 + S - 1) x (T + P - 1 + S - 1)
+ * RGBA32F texels fits 160 KB (search width S, patch width P, T = 32 rows, 16 for patches 10 wide and up): search width
+ * <= 52 at a 7x7 patch, <= 50 at 9x9, <= 55 at 1x1, <= 56 at 16x16; anything else (lopsided patches, wider windows) is
+ * computed by a per-pixel kernel -- same results, the reference's S^2 * P^2 work. */
 typedef struct mid_nlm_params {
     int32_t width;
     int32_t height;

@@ -61,7 +61,8 @@ def test_bilateral_sigma_sweep(ctx):
 
 
 # ---- a3 -------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("R", [4, 8, 6, 16, 22])               # 22: two tiles exceed LDS -> per-pixel fallback
+# 17: the last radius whose two tiles fit the LDS (156,800 B); 18, 19, 22, 24: two tiles exceed it -> per-pixel fallback
+@pytest.mark.parametrize("R", [4, 8, 6, 16, 17, 18, 19, 22, 24])
 def test_layers_accumulate_and_fused(ctx, R):
     rng = np.random.default_rng(20 + R)
     h, w = 50, 90

@@ -116,7 +116,7 @@ def test_layers_match_per_frame_calls(ctx, L):
     rng = np.random.default_rng(50 + L)
     h, w, n = 45, 77, 5
     outs = list(DT.values())
-    for j, r in enumerate((8, 20, 13, 22)):                          # tuned, tuned, run-time radius, generic kernel
+    for j, r in enumerate((8, 20, 13, 22, 24)):                      # tuned, tuned, run-time radius, generic kernel (22 and the largest, 24)
         in_dt = list(DT.values())[j % 3]
         out_dt = outs[(j + L) % 3]
         frames = frames_of(rng, n, h, w, in_dt)
