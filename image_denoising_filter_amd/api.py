@@ -312,6 +312,41 @@ class Context:
         _check(lib.mid_nlm_layers(self.handle, ctypes.byref(p), d_in.ptr, tbl, len(d_layers), d_out.ptr, None), "mid_nlm_layers")
         return self.download(d_out, (h, w, 4), np.float32)
 
+    def nlm_layers_pair_accum(self, target_layer, neighbour_layer, neighbour, W, hparam=0.5, search=(-7, 7), patch=(-3, 3)):
+        """One dispatch with the patch distance between two uint8 guides -- the target frame's layer and the neighbour frame's
+        layer -- and the colour from the `neighbour` frame: returns W + its sums (mid_nlm_layers_pair_accum)."""
+        neighbour, target_layer, neighbour_layer = _img(neighbour), _img(target_layer), _img(neighbour_layer)
+        if target_layer.dtype != np.uint8 or neighbour_layer.dtype != np.uint8:
+            raise TypeError("layers are always RGBA8 (src/main.cpp:1396)")
+        h, w = neighbour.shape[:2]
+        W = np.ascontiguousarray(W, dtype=np.float32)
+        d_in, d_n, d_w = self.upload(neighbour), self.upload(neighbour_layer), self.upload(W)
+        d_t = d_n if target_layer is neighbour_layer else self.upload(target_layer)
+        p = NlmParams(w, h, hparam, search[0], search[1], patch[0], patch[1], _fmt_of(neighbour))
+        _check(lib.mid_nlm_layers_pair_accum(self.handle, ctypes.byref(p), d_t.ptr, d_n.ptr, d_in.ptr, d_w.ptr, None),
+               "mid_nlm_layers_pair_accum")
+        return self.download(d_w, (h, w, 8), np.float32)
+
+    def nlm_layers_temporal(self, frames, layers, k=0, first=0, count=None, hparam=0.5, search=(-7, 7), patch=(-3, 3), out_dtype=None):
+        """Layer-guided NLM over the frames t-k..t+k for `count` output frames, fused (mid_nlm_layers_temporal).
+        layers: one list per frame of equally many uint8 (h, w, 4) guide layers; out_dtype: None = float32, uint8 or float16."""
+        frames = _same_frames(frames, "nlm_layers_temporal")
+        n = len(frames)
+        count = n - first if count is None else count
+        h, w = frames[0].shape[:2]
+        n_layers, flat = _flat_layers(layers, n, h, w, "nlm_layers_temporal")
+        out_dtype = _out_dtype(False, out_dtype)
+        out_fmt = {np.dtype(np.uint8): FMT_RGBA8, np.dtype(np.float16): FMT_RGBA16F, np.dtype(np.float32): FMT_RGBA32F}[out_dtype]
+        d_fr = [self.upload(f) for f in frames]
+        d_l = [self.upload(l) for l in flat]
+        d_out = [self.alloc(w * h * 4 * out_dtype.itemsize) for _ in range(max(count, 0))]
+        p = NlmParams(w, h, hparam, search[0], search[1], patch[0], patch[1], _fmt_of(frames[0]))
+        _check(lib.mid_nlm_layers_temporal(self.handle, ctypes.byref(p), (ctypes.c_void_p * n)(*[d.ptr for d in d_fr]),
+                                           (ctypes.c_void_p * max(len(d_l), 1))(*[d.ptr for d in d_l]), n_layers, n, k, first, count,
+                                           (ctypes.c_void_p * max(len(d_out), 1))(*[d.ptr for d in d_out]), out_fmt, None),
+               "mid_nlm_layers_temporal")
+        return [self.download(d, (h, w, 4), out_dtype) for d in d_out]
+
     def normalize(self, W):
         """normalize.comp."""
         W = np.ascontiguousarray(W, dtype=np.float32)
@@ -521,18 +556,7 @@ class Context:
         frames = _same_frames(frames, "sequence_nlm_layers")
         n = len(frames)
         h, w = frames[0].shape[:2]
-        if len(layers) != n:
-            raise ValueError(f"sequence_nlm_layers: {len(layers)} layer lists for {n} frames")
-        n_layers = len(layers[0])
-        flat = []
-        for i, ls in enumerate(layers):
-            if len(ls) != n_layers:
-                raise ValueError(f"sequence_nlm_layers: frame {i} has {len(ls)} layers, frame 0 has {n_layers}")
-            for lyr in ls:
-                lyr = _img(lyr)
-                if lyr.dtype != np.uint8 or lyr.shape != (h, w, 4):
-                    raise ValueError(f"sequence_nlm_layers: the layers of frame {i} must be uint8 {(h, w, 4)}, got {lyr.dtype} {lyr.shape}")
-                flat.append(lyr)
+        n_layers, flat = _flat_layers(layers, n, h, w, "sequence_nlm_layers")
         out_shape, out_dtype = (h, w, 4), _out_dtype(False, out_dtype)
         hin = hlay = hout = None
         try:
@@ -549,6 +573,75 @@ class Context:
             for b in (hin, hlay, hout):
                 if b is not None:
                     b.free()
+
+    def sequence_nlm_layers_temporal_pinned(self, hin, hout, w, h, fmt, hlayers, n_layers, k, first=0, count=None, overlap=True,
+                                            hparam=0.5, search=(-7, 7), patch=(-3, 3), out_dtype=None):
+        """mid_sequence_nlm_layers_temporal on host pointers the caller already holds: nothing but the C call.  hin: all n frames of
+        the sequence (only those of [first-k, first+count+k) are read); hlayers: n * n_layers RGBA8 host pointers, frame-major;
+        hout: `count` output buffers.  Returns (wall_ms of the whole call, kernel_ms, copy_ms)."""
+        n = len(hin)
+        count = n - first if count is None else count
+        if len(hout) < count:
+            raise ValueError(f"{count} outputs, {len(hout)} output buffers given")
+        if len(hlayers) != n * n_layers:
+            raise ValueError(f"{n} frames x {n_layers} layers, {len(hlayers)} layer pointers given")
+        prm = NlmParams(w, h, hparam, search[0], search[1], patch[0], patch[1], fmt)
+        out_fmt = {np.dtype(np.uint8): FMT_RGBA8, np.dtype(np.float16): FMT_RGBA16F,
+                   np.dtype(np.float32): FMT_RGBA32F}[_out_dtype(False, out_dtype)]
+        tl = (ctypes.c_void_p * max(len(hlayers), 1))(*hlayers)
+        t = (ctypes.c_float * 3)()
+        _check(lib.mid_sequence_nlm_layers_temporal(self.handle, ctypes.byref(prm), (ctypes.c_void_p * n)(*hin), n, tl, n_layers, k,
+                                                    first, count, (ctypes.c_void_p * max(count, 1))(*hout[:max(count, 0)]), out_fmt,
+                                                    1 if overlap else 0, t),
+               "mid_sequence_nlm_layers_temporal")
+        return tuple(t)
+
+    def sequence_nlm_layers_temporal(self, frames, layers, k=2, first=0, count=None, overlap=True, hparam=0.5, search=(-7, 7),
+                                     patch=(-3, 3), pinned=True, pinned_out=True, out_dtype=None):
+        """Outputs [first, first+count) of an animation through the overlapped pipeline with layer-guided NLM over the frames
+        t-k..t+k as its compute stage (mid_sequence_nlm_layers_temporal): output t is ctx.nlm_layers_temporal(frames, layers, k)
+        of frame t in out_dtype.  layers, pinned, pinned_out, out_dtype as for sequence_nlm_layers.
+        Returns (outputs, (wall_ms, kernel_ms, copy_ms))."""
+        frames = _same_frames(frames, "sequence_nlm_layers_temporal")
+        n = len(frames)
+        count = n - first if count is None else count
+        h, w = frames[0].shape[:2]
+        n_layers, flat = _flat_layers(layers, n, h, w, "sequence_nlm_layers_temporal")
+        out_shape, out_dtype = (h, w, 4), _out_dtype(False, out_dtype)
+        hin = hlay = hout = None
+        try:
+            hin = PinnedFrames(self, frames) if pinned else None
+            hlay = PinnedFrames(self, flat) if pinned and flat else None
+            hout = PinnedFrames(self, max(count, 1), w * h * 4 * out_dtype.itemsize) if pinned_out else None
+            outs = None if pinned_out else [np.empty(out_shape, out_dtype) for _ in range(max(count, 0))]
+            lptr = hlay.ptrs if hlay is not None else [lyr.ctypes.data for lyr in flat]
+            t = self.sequence_nlm_layers_temporal_pinned(hin.ptrs if pinned else [f.ctypes.data for f in frames],
+                                                         hout.ptrs if pinned_out else [o.ctypes.data for o in outs], w, h,
+                                                         _fmt_of(frames[0]), lptr, n_layers, k, first, count, overlap, hparam,
+                                                         search, patch, out_dtype)
+            return (outs if outs is not None else [hout.array(i, out_shape, out_dtype) for i in range(count)]), t
+        finally:
+            for b in (hin, hlay, hout):
+                if b is not None:
+                    b.free()
+
+
+
+def _flat_layers(layers, n, h, w, who):
+    """(layers per frame, the frames' uint8 (h, w, 4) guide layers as one frame-major list) of one list of layers per frame."""
+    if len(layers) != n:
+        raise ValueError(f"{who}: {len(layers)} layer lists for {n} frames")
+    n_layers = len(layers[0])
+    flat = []
+    for i, ls in enumerate(layers):
+        if len(ls) != n_layers:
+            raise ValueError(f"{who}: frame {i} has {len(ls)} layers, frame 0 has {n_layers}")
+        for lyr in ls:
+            lyr = _img(lyr)
+            if lyr.dtype != np.uint8 or lyr.shape != (h, w, 4):
+                raise ValueError(f"{who}: the layers of frame {i} must be uint8 {(h, w, 4)}, got {lyr.dtype} {lyr.shape}")
+            flat.append(lyr)
+    return n_layers, flat
 
 
 def _out_dtype(out_u8, out_dtype):

@@ -151,6 +151,13 @@ int nlm_check_params(const mid_nlm_params *p);
 int nlm_layers_out(mid_ctx *ctx, const mid_nlm_params *p, const void *in, const uint32_t *const *layers, int n_layers, void *out,
                    int out_fmt, hipStream_t s);
 
+// mid_nlm_layers_temporal without its checks (the caller has made them), one launch per output frame on `s`:
+// nlm_layers_temporal.hip; used by the frame pipeline (mid_sequence_nlm_layers_temporal), not exported.
+// nlm_layers_temporal_fits: the pointer limit of one launch (MID_NLM_LAYERS_TEMPORAL_MAX_POINTERS), MID_ERR_INVALID beyond it.
+int nlm_layers_temporal_out(mid_ctx *ctx, const mid_nlm_params *p, const void *const *frames, const uint32_t *const *layers,
+                            int n_layers, int n_frames, int k, int first, int count, void *const *out, int out_fmt, hipStream_t s);
+int nlm_layers_temporal_fits(const char *who, int n_layers, int n_frames, int k);
+
 // ROCTx ranges (csrc/markers.cpp): no-ops unless the process already holds a ROCTx (rocprofv3 --marker-trace preloads one).
 bool markers_active();
 void range_push(const char *name);

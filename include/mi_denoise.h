@@ -177,7 +177,8 @@ int mid_stream_sync(mid_ctx *ctx, void *stream);                     /* vkWaitFo
  * A matter of program shape; for speed use the fused entry points (mid_nlm_temporal, mid_bilateral_batch, mid_bilateral_layers).
  * mid_record_begin and mid_record_end of one recording are called on the same thread.
  * Refused while a stream records (MID_ERR_INVALID, the recording stays valid): calls that wait on the host, drive several streams or
- * bounce pageable memory -- mid_stream_sync, mid_timer_tick/tock, mid_sequence_nlm*, mid_nlm_multiframe, mid_nlm_temporal_sharded,
+ * bounce pageable memory -- mid_stream_sync, mid_timer_tick/tock, mid_sequence_nlm* (mid_sequence_nlm_layers_temporal among them),
+ * mid_sequence_bilateral, mid_nlm_multiframe, mid_nlm_temporal_sharded,
  * mid_comm_loopback, copies from / to pageable host memory.  Do not allocate or free (mid_alloc*, mid_free*, mid_host_register) on the
  * recording thread between begin and end: the runtime fails such calls and invalidates the recording (mid_record_end then reports
  * it).  The capture is thread-local: other threads keep using their own streams meanwhile.  A kernel's first ever launch may be
@@ -253,6 +254,37 @@ int mid_nlm_layers(mid_ctx *ctx, const mid_nlm_params *p, const void *in,
                    const uint32_t *const *layers_rgba8 /* host array of device ptrs */,
                    int n_layers, mid_pixel *out, void *stream);
 
+/* ---- a4c: layer-guided non-local means over neighbouring frames --------------------------
+ * mid_nlm_layers with the neighbouring frames of an animation as further sources of samples: the guide layers, which are free
+ * of noise, say which pixels belong together; the frames t-k..t+k supply more samples of them.
+ * mid_nlm_layers_pair_accum = one dispatch with a target guide Gt, a neighbour guide Gn and a neighbour colour image In (guides
+ * RGBA8, texels c/255; In in p->format; out-of-image texels 0 everywhere): for each pixel p and search offset s,
+ *   d = sum over the patch of |Gt(p+q) - Gn(p+s+q)|^2_rgb,  w = exp(-d/h^2),  W[p].weightColor += w * In(p+s),
+ *   W[p].normWeight += w, plus 0.001 once per dispatch.
+ * With target_layer_rgba8 == neighbour_layer_rgba8 it gives the bits of mid_nlm_layers_accum(p, neighbour_in, that layer, W).
+ * mid_nlm_layers_temporal = outputs [first, first+count) of a sequence of n_frames frames with n_layers layers each.  Output t:
+ * into a zeroed W, for each neighbour f = max(0,t-k) .. min(n_frames-1,t+k), ascending, and inside it each layer l = 0 ..
+ * n_layers-1, ascending, one such dispatch with Gt = layer[t][l], Gn = layer[f][l], In = frame[f]; then mid_normalize and, for
+ * out_format MID_FMT_RGBA8 / MID_FMT_RGBA16F, mid_pack_u8 / mid_pack_f16.  Fused in one kernel per output frame (no WeightInfo
+ * traffic), with the bits of that chain of calls; with k == 0 the bits of mid_nlm_layers; with n_layers == 0 every pixel is the
+ * magenta sentinel.  frames: host array of n_frames device pointers in p->format; layers_rgba8: host array of n_frames * n_layers
+ * device pointers, frame-major (NULL only with n_layers == 0); out: host array of `count` device pointers in out_format.  Only
+ * the frames and layers of [first-k, first+count+k) are read.
+ * Windows as for mid_nlm_layers: the two tuned ones run on an LDS-tiled kernel, every other one on a per-pixel kernel.
+ * A launch carries the pointers of one output's window by value, so MID_ERR_INVALID for
+ *   min(2k+1, n_frames) * (n_layers + 1) > MID_NLM_LAYERS_TEMPORAL_MAX_POINTERS
+ * (k = 2 with 16 layers needs 85, k = 4 with 16 layers 153), and for: the parameter checks of mid_nlm_accum; a NULL pointer;
+ * n_layers outside 0..16; k < 0, first < 0, count < 1, first + count > n_frames; an unknown out_format; an RGBA16F frame or output
+ * that is not 8-byte aligned; an output that is also a frame or layer of the window, or appears twice. */
+#define MID_NLM_LAYERS_TEMPORAL_MAX_POINTERS 176
+int mid_nlm_layers_pair_accum(mid_ctx *ctx, const mid_nlm_params *p, const uint32_t *target_layer_rgba8,
+                              const uint32_t *neighbour_layer_rgba8, const void *neighbour_in, mid_weightinfo *W, void *stream);
+int mid_nlm_layers_temporal(mid_ctx *ctx, const mid_nlm_params *p,
+                            const void *const *frames /* host array of n_frames device ptrs */,
+                            const uint32_t *const *layers_rgba8 /* host array of n_frames * n_layers device ptrs */,
+                            int n_layers, int n_frames, int k, int first, int count,
+                            void *const *out /* host array of `count` device ptrs */, int out_format, void *stream);
+
 /* ---- a5: normalize ----------------------------------------------------------------------
  * One dispatch of shaders/normalize.comp (RecordCommandsOfExecuteAndTransfer(normKernel=true)):
  * out = weightColor / normWeight, or (1,0,1,1) where normWeight == 0; bindings {0: out; 1: W}. */
@@ -326,7 +358,8 @@ int mid_sequence_bilateral(mid_ctx *ctx, const mid_bilateral_params *p, const vo
                            const void *const *host_layers, int n_layers, void *const *host_out, int out_format,
                            int overlap, float *timings_ms);
 
-/* The same pipeline with layer-guided NLM as its compute stage (window k = 0), for a whole animation: output i has the bits of
+/* The same pipeline with layer-guided NLM as its compute stage (one frame's window; mid_sequence_nlm_layers_temporal adds the
+ * neighbouring frames), for a whole animation: output i has the bits of
  * mid_nlm_layers(p, frame i, its n_layers layers) followed by mid_pack_u8 / mid_pack_f16 when out_format is MID_FMT_RGBA8 /
  * MID_FMT_RGBA16F (the kernel's epilogue packs).  host_frames: n_frames HOST pointers in p->format; host_layers: n_frames *
  * n_layers RGBA8 HOST pointers, frame-major (frame i's layers are uploaded with frame i; NULL only with n_layers == 0, which gives
@@ -339,7 +372,24 @@ int mid_sequence_nlm_layers(mid_ctx *ctx, const mid_nlm_params *p, const void *c
                             const void *const *host_layers, int n_layers, void *const *host_out, int out_format,
                             int overlap, float *timings_ms);
 
-/* Debug export: the DEVICE timeline of this context's last mid_sequence_nlm*, mid_sequence_bilateral or mid_sequence_nlm_layers call, from the events the call recorded on
+/* The same pipeline with layer-guided NLM over neighbouring frames as its compute stage: outputs [first, first+count) of the
+ * sequence, output t with the bits of mid_nlm_layers_temporal(p, frames, layers, k) for frame t in out_format.  The temporal
+ * window is mid_sequence_nlm_range's (ring of 2k+4 frames; only the frames of [first-k, first+count+k) are read and uploaded,
+ * so a frame block plus k halo frames on either side is the unit of sharding) and the layer ring is mid_sequence_nlm_layers':
+ * frame f's layers are uploaded with frame f and live as long as its ring slot, across the 2k+1 outputs that read them.
+ * host_frames: n_frames HOST pointers in p->format; host_layers: n_frames * n_layers RGBA8 HOST pointers, frame-major (NULL only
+ * with n_layers == 0, which gives magenta outputs); host_out: `count` HOST pointers.  Outputs are stored by the kernel or
+ * downloaded by the rule of mid_sequence_bilateral.  overlap and timings_ms as for mid_sequence_nlm.  MID_ERR_INVALID, before
+ * anything is queued, for: a NULL frame, layer or output of the range; n_layers outside 0..16; bad k, first or count (k >= 0,
+ * 2k+2 <= 96, first >= 0, count >= 1, first + count <= n_frames); the pointer limit of mid_nlm_layers_temporal; an unknown
+ * out_format; an output that is also an input frame or layer of the range (or appears twice); the parameter checks of
+ * mid_nlm_accum; a call while the context's stream records. */
+int mid_sequence_nlm_layers_temporal(mid_ctx *ctx, const mid_nlm_params *p, const void *const *host_frames, int n_frames,
+                                     const void *const *host_layers, int n_layers, int k, int first, int count,
+                                     void *const *host_out, int out_format, int overlap, float *timings_ms);
+
+/* Debug export: the DEVICE timeline of this context's last mid_sequence_nlm*, mid_sequence_bilateral, mid_sequence_nlm_layers or
+ * mid_sequence_nlm_layers_temporal call, from the events the call recorded on
  * its streams (no profiler: the call ran at its own pace).  All times in ms from the start of the call's first upload.
  * upload_ms[2*i], [2*i+1]: start / end of the upload of frame first_upload_frame + i; output_ms[4*j .. 4*j+3]: kernel
  * start, kernel end, download start, download end of output frame first_output_frame + j (output j runs on kernel stream

@@ -16,6 +16,8 @@ int mid::nlm_temporal_out(mid_ctx *, const mid_nlm_params *, const void *const *
 int mid::fill_bytes(mid_ctx *, void *, int, size_t, hipStream_t) { return MID_ERR_UNSUPPORTED; }      // (pointwise.hip: kernels are not part of this CPU build)
 int mid::bilateral_out(mid_ctx *, const mid_bilateral_params *, const void *, const uint32_t *const *, int, void *, int, hipStream_t) { return MID_ERR_UNSUPPORTED; }   // (bilateral.hip)
 int mid::nlm_layers_out(mid_ctx *, const mid_nlm_params *, const void *, const uint32_t *const *, int, void *, int, hipStream_t) { return MID_ERR_UNSUPPORTED; }   // (nlm_layers.hip)
+int mid::nlm_layers_temporal_out(mid_ctx *, const mid_nlm_params *, const void *const *, const uint32_t *const *, int, int, int, int, int, void *const *, int, hipStream_t) { return MID_ERR_UNSUPPORTED; }   // (nlm_layers_temporal.hip)
+int mid::nlm_layers_temporal_fits(const char *, int, int, int) { return MID_ERR_UNSUPPORTED; }   // (nlm_layers_temporal.hip)
 int mid::nlm_check_params(const mid_nlm_params *) { return MID_ERR_UNSUPPORTED; }   // (nlm.hip)
 
 int main()
