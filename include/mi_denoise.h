@@ -244,7 +244,8 @@ int mid_nlm_temporal(mid_ctx *ctx, const mid_nlm_params *p,
  * mid_nlm_layers = n_layers such dispatches into a zeroed W (layers in the given order) followed by mid_normalize, fused in one
  * kernel: no WeightInfo traffic, and the bits of that chain of calls.  With n_layers == 0 every pixel is the magenta sentinel,
  * as in mid_bilateral_layers.  With one layer equal to an RGBA8 input the result is mid_nlm_temporal(k = 0) of that input to
- * rounding (the guide's distances are summed as exact integers here).
+ * rounding (the guide's distances are summed as exact integers here).  A non-finite input texel (NaN, +-Inf) makes every output
+ * whose search window contains it non-finite in the channels where the texel is, Inf * 0 being NaN as in IEEE arithmetic.
  * The windows and their limits are mid_nlm_accum's: the two tuned windows run on an LDS-tiled kernel, every other one on a
  * per-pixel kernel.  MID_ERR_INVALID for: the parameter checks of mid_nlm_accum; a NULL pointer; n_layers outside 0..16; an
  * RGBA16F input that is not 8-byte aligned; `out` equal to `in` or to a layer (mid_nlm_layers). */
@@ -267,7 +268,8 @@ int mid_nlm_layers(mid_ctx *ctx, const mid_nlm_params *p, const void *in,
  * n_layers-1, ascending, one such dispatch with Gt = layer[t][l], Gn = layer[f][l], In = frame[f]; then mid_normalize and, for
  * out_format MID_FMT_RGBA8 / MID_FMT_RGBA16F, mid_pack_u8 / mid_pack_f16.  Fused in one kernel per output frame (no WeightInfo
  * traffic), with the bits of that chain of calls; with k == 0 the bits of mid_nlm_layers; with n_layers == 0 every pixel is the
- * magenta sentinel.  frames: host array of n_frames device pointers in p->format; layers_rgba8: host array of n_frames * n_layers
+ * magenta sentinel.  A non-finite texel of a frame makes every output of the frames t-k..t+k whose search window contains it
+ * non-finite, as in mid_nlm_layers.  frames: host array of n_frames device pointers in p->format; layers_rgba8: host array of n_frames * n_layers
  * device pointers, frame-major (NULL only with n_layers == 0); out: host array of `count` device pointers in out_format.  Only
  * the frames and layers of [first-k, first+count+k) are read.
  * Windows as for mid_nlm_layers: the two tuned ones run on an LDS-tiled kernel, every other one on a per-pixel kernel.
