@@ -347,6 +347,57 @@ class Context:
                "mid_nlm_layers_temporal")
         return [self.download(d, (h, w, 4), out_dtype) for d in d_out]
 
+    def bilateral_pair_accum(self, target, neighbour, W, radius, sigma_s=2.0, sigma_c=0.2):
+        """One plain pair dispatch: the range weight between the `target` frame's centre and the `neighbour` frame's taps, the
+        colour from `neighbour`: returns W + its sums (mid_bilateral_pair_accum)."""
+        target, neighbour = _img(target), _img(neighbour)
+        if target.shape != neighbour.shape or target.dtype != neighbour.dtype:
+            raise ValueError(f"bilateral_pair_accum: target is {target.shape} {target.dtype}, neighbour {neighbour.shape} {neighbour.dtype}")
+        h, w = neighbour.shape[:2]
+        W = np.ascontiguousarray(W, dtype=np.float32)
+        d_n, d_w = self.upload(neighbour), self.upload(W)
+        d_t = d_n if target is neighbour else self.upload(target)
+        p = BilateralParams(w, h, sigma_s, sigma_c, radius, LAYOUT_TEXTURE, _fmt_of(neighbour))
+        _check(lib.mid_bilateral_pair_accum(self.handle, ctypes.byref(p), d_t.ptr, d_n.ptr, d_w.ptr, None), "mid_bilateral_pair_accum")
+        return self.download(d_w, (h, w, 8), np.float32)
+
+    def bilateral_layers_pair_accum(self, target_layer, neighbour_layer, neighbour, W, radius, sigma_s=2.0, sigma_c=0.2):
+        """One layered pair dispatch: the range weight between two uint8 guides -- the target frame's layer at the centre, the
+        neighbour frame's layer under the taps -- and the colour from the `neighbour` frame: returns W + its sums
+        (mid_bilateral_layers_pair_accum)."""
+        neighbour, target_layer, neighbour_layer = _img(neighbour), _img(target_layer), _img(neighbour_layer)
+        if target_layer.dtype != np.uint8 or neighbour_layer.dtype != np.uint8:
+            raise TypeError("layers are always RGBA8 (src/main.cpp:1396)")
+        h, w = neighbour.shape[:2]
+        W = np.ascontiguousarray(W, dtype=np.float32)
+        d_in, d_n, d_w = self.upload(neighbour), self.upload(neighbour_layer), self.upload(W)
+        d_t = d_n if target_layer is neighbour_layer else self.upload(target_layer)
+        p = BilateralParams(w, h, sigma_s, sigma_c, radius, LAYOUT_TEXTURE, _fmt_of(neighbour))
+        _check(lib.mid_bilateral_layers_pair_accum(self.handle, ctypes.byref(p), d_t.ptr, d_n.ptr, d_in.ptr, d_w.ptr, None),
+               "mid_bilateral_layers_pair_accum")
+        return self.download(d_w, (h, w, 8), np.float32)
+
+    def bilateral_temporal(self, frames, k=0, first=0, count=None, radius=8, sigma_s=2.0, sigma_c=0.2, layers=None, out_dtype=None):
+        """The bilateral over the frames t-k..t+k for `count` output frames, fused (mid_bilateral_temporal).
+        layers: None (plain form: the frames guide themselves), or one list per frame of equally many uint8 (h, w, 4) guide
+        layers; out_dtype: None = float32, uint8 or float16."""
+        frames = _same_frames(frames, "bilateral_temporal")
+        n = len(frames)
+        count = n - first if count is None else count
+        h, w = frames[0].shape[:2]
+        n_layers, flat = (0, None) if layers is None else _flat_layers(layers, n, h, w, "bilateral_temporal")
+        out_dtype = _out_dtype(False, out_dtype)
+        out_fmt = {np.dtype(np.uint8): FMT_RGBA8, np.dtype(np.float16): FMT_RGBA16F, np.dtype(np.float32): FMT_RGBA32F}[out_dtype]
+        d_fr = [self.upload(f) for f in frames]
+        d_l = None if flat is None else [self.upload(l) for l in flat]
+        d_out = [self.alloc(w * h * 4 * out_dtype.itemsize) for _ in range(max(count, 0))]
+        tl = None if d_l is None else (ctypes.c_void_p * max(len(d_l), 1))(*[d.ptr for d in d_l])
+        p = BilateralParams(w, h, sigma_s, sigma_c, radius, LAYOUT_TEXTURE, _fmt_of(frames[0]))
+        _check(lib.mid_bilateral_temporal(self.handle, ctypes.byref(p), (ctypes.c_void_p * n)(*[d.ptr for d in d_fr]), tl, n_layers, n,
+                                          k, first, count, (ctypes.c_void_p * max(len(d_out), 1))(*[d.ptr for d in d_out]), out_fmt, None),
+               "mid_bilateral_temporal")
+        return [self.download(d, (h, w, 4), out_dtype) for d in d_out]
+
     def normalize(self, W):
         """normalize.comp."""
         W = np.ascontiguousarray(W, dtype=np.float32)
@@ -619,6 +670,59 @@ class Context:
                                                          hout.ptrs if pinned_out else [o.ctypes.data for o in outs], w, h,
                                                          _fmt_of(frames[0]), lptr, n_layers, k, first, count, overlap, hparam,
                                                          search, patch, out_dtype)
+            return (outs if outs is not None else [hout.array(i, out_shape, out_dtype) for i in range(count)]), t
+        finally:
+            for b in (hin, hlay, hout):
+                if b is not None:
+                    b.free()
+
+    def sequence_bilateral_temporal_pinned(self, hin, hout, w, h, fmt, k, first=0, count=None, radius=8, sigma_s=2.0, sigma_c=0.2,
+                                           hlayers=None, n_layers=0, overlap=True, out_dtype=None):
+        """mid_sequence_bilateral_temporal on host pointers the caller already holds: nothing but the C call.  hin: all n frames
+        of the sequence (only those of [first-k, first+count+k) are read); hlayers: None (plain form) or n * n_layers RGBA8 host
+        pointers, frame-major; hout: `count` output buffers.  Returns (wall_ms of the whole call, kernel_ms, copy_ms)."""
+        n = len(hin)
+        count = n - first if count is None else count
+        if len(hout) < count:
+            raise ValueError(f"{count} outputs, {len(hout)} output buffers given")
+        tl = None
+        if hlayers is not None:
+            if len(hlayers) != n * n_layers:
+                raise ValueError(f"{n} frames x {n_layers} layers, {len(hlayers)} layer pointers given")
+            tl = (ctypes.c_void_p * max(len(hlayers), 1))(*hlayers)
+        prm = BilateralParams(w, h, sigma_s, sigma_c, radius, LAYOUT_TEXTURE, fmt)
+        out_fmt = {np.dtype(np.uint8): FMT_RGBA8, np.dtype(np.float16): FMT_RGBA16F,
+                   np.dtype(np.float32): FMT_RGBA32F}[_out_dtype(False, out_dtype)]
+        t = (ctypes.c_float * 3)()
+        _check(lib.mid_sequence_bilateral_temporal(self.handle, ctypes.byref(prm), (ctypes.c_void_p * n)(*hin), n, tl, n_layers, k,
+                                                   first, count, (ctypes.c_void_p * max(count, 1))(*hout[:max(count, 0)]), out_fmt,
+                                                   1 if overlap else 0, t),
+               "mid_sequence_bilateral_temporal")
+        return tuple(t)
+
+    def sequence_bilateral_temporal(self, frames, k=2, first=0, count=None, overlap=True, radius=8, sigma_s=2.0, sigma_c=0.2,
+                                    layers=None, pinned=True, pinned_out=True, out_dtype=None):
+        """Outputs [first, first+count) of an animation through the overlapped pipeline with the bilateral over the frames
+        t-k..t+k as its compute stage (mid_sequence_bilateral_temporal): output t is ctx.bilateral_temporal(frames, k,
+        layers=layers) of frame t in out_dtype.  layers, pinned, pinned_out, out_dtype as for sequence_bilateral.
+        Returns (outputs, (wall_ms, kernel_ms, copy_ms))."""
+        frames = _same_frames(frames, "sequence_bilateral_temporal")
+        n = len(frames)
+        count = n - first if count is None else count
+        h, w = frames[0].shape[:2]
+        n_layers, flat = (0, None) if layers is None else _flat_layers(layers, n, h, w, "sequence_bilateral_temporal")
+        out_shape, out_dtype = (h, w, 4), _out_dtype(False, out_dtype)
+        hin = hlay = hout = None
+        try:
+            hin = PinnedFrames(self, frames) if pinned else None
+            hlay = PinnedFrames(self, flat) if pinned and flat else None
+            hout = PinnedFrames(self, max(count, 1), w * h * 4 * out_dtype.itemsize) if pinned_out else None
+            outs = None if pinned_out else [np.empty(out_shape, out_dtype) for _ in range(max(count, 0))]
+            lptr = None if flat is None else (hlay.ptrs if hlay is not None else [lyr.ctypes.data for lyr in flat])
+            t = self.sequence_bilateral_temporal_pinned(hin.ptrs if pinned else [f.ctypes.data for f in frames],
+                                                        hout.ptrs if pinned_out else [o.ctypes.data for o in outs], w, h,
+                                                        _fmt_of(frames[0]), k, first, count, radius, sigma_s, sigma_c, lptr, n_layers,
+                                                        overlap, out_dtype)
             return (outs if outs is not None else [hout.array(i, out_shape, out_dtype) for i in range(count)]), t
         finally:
             for b in (hin, hlay, hout):

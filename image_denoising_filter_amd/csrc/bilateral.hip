@@ -514,6 +514,8 @@ static int check_params(const mid_bilateral_params *p, const char *who)
     return MID_OK;
 }
 
+int bilateral_check_params(const mid_bilateral_params *p, const char *who) { return check_params(p, who); }
+
 // The input's texel format as a template argument: one switch for every entry point (the guide layers are always RGBA8).
 template <bool LINEAR, int MODE, typename BT = BilOne>
 static int dispatch_format(mid_ctx *ctx, int format, int radius, BilArgs &a, hipStream_t s, const BT &bt = BT{}, int n_frames = 1)

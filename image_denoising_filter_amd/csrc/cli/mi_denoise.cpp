@@ -60,7 +60,7 @@ struct Options {
     bool run_gpu = true, run_cpu = true;
     std::string modes = "all";      // comma list of: bilateral,layers,linear,nlm,multiframe,overlap (all of them: "all"), nlm-layers
     bool animation = false;         // new capability: temporal NLM of EVERY frame of the sequence
-    std::string animation_filter = "nlm";   // animation mode: nlm | bilateral | linear | layers (the bilateral of every frame) | nlm-layers | nlm-layers-temporal
+    std::string animation_filter = "nlm";   // animation mode: nlm | bilateral | linear | layers (the bilateral of every frame) | nlm-layers | nlm-layers-temporal | bilateral-temporal | layers-temporal
     int gpus = 1;                   // animation mode: frame blocks over this many devices
     bool share_device = false;      // animation mode: every block on --device (rehearsal of --gpus N on fewer devices)
     bool halo_rccl = false;         // animation mode: blocks resident in HBM, halo frames GPU to GPU over RCCL (mid_nlm_temporal_sharded)
@@ -404,6 +404,8 @@ public:
     // the single-frame modes' names (nonlinear-bialteral, linear-bialteral, nonlinear-bialteral-layers).
     // --animation-filter nlm-layers is layer-guided NLM of every frame on its own (mid_sequence_nlm_layers); nlm-layers-temporal adds
     // the frames t-k..t+k and their layers (mid_sequence_nlm_layers_temporal: blocks with k halo frames, like nlm, from the host only).
+    // --animation-filter bilateral-temporal | layers-temporal is the bilateral over the frames t-k..t+k, plain or guided by each
+    // frame's layers (mid_sequence_bilateral_temporal: blocks with k halo frames and their layers, from the host only).
     void RunAnimation()
     {
         std::vector<std::string> frameNames, layerNames;
@@ -412,14 +414,15 @@ public:
         const int n = (int)frameNames.size(), k = opt.temporal_k < 0 ? 2 : opt.temporal_k;
         const bool nlm_layers = opt.animation_filter == "nlm-layers";                   // layer-guided NLM of every frame
         const bool nlm_layers_t = opt.animation_filter == "nlm-layers-temporal";        // ... over the frames t-k..t+k and their layers
-        const bool bil = opt.animation_filter != "nlm" && !nlm_layers && !nlm_layers_t;
-        const bool use_layers = opt.animation_filter == "layers" || nlm_layers || nlm_layers_t;
+        const bool bil_t = opt.animation_filter == "bilateral-temporal" || opt.animation_filter == "layers-temporal";   // the bilateral over the frames t-k..t+k
+        const bool bil = opt.animation_filter != "nlm" && !nlm_layers && !nlm_layers_t && !bil_t;
+        const bool use_layers = opt.animation_filter == "layers" || nlm_layers || nlm_layers_t || opt.animation_filter == "layers-temporal";
         const bool linear = opt.animation_filter == "linear";
         if ((bil || nlm_layers) && opt.halo_rccl)
             throw std::runtime_error("--halo rccl is not available with --animation-filter " + opt.animation_filter +
                                      ": its frames read no other frame, there is no halo to exchange");
-        if (nlm_layers_t && opt.halo_rccl)
-            throw std::runtime_error("--halo rccl is not available with --animation-filter nlm-layers-temporal: the halo would have to "
+        if ((nlm_layers_t || bil_t) && opt.halo_rccl)
+            throw std::runtime_error("--halo rccl is not available with --animation-filter " + opt.animation_filter + ": the halo would have to "
                                      "carry every halo frame's layers as well, and that exchange is not built (use --halo host)");
         // every frame's own layers, all of them checked before anything is decoded: 1..16 per frame, the same count for all
         std::vector<std::vector<std::string>> frameLayers(use_layers ? n : 0);
@@ -571,6 +574,14 @@ public:
                 for (int l = 0; l < L; ++l) wl[l] = lz.data();
                 void *wo[1] = {o.data()};
                 MID_CHECK(mid_sequence_nlm_layers(ctxs[g], &wp, wi, 1, wl, L, wo, out_fmt, 1, nullptr));
+            } else if (bil_t) {
+                mid_bilateral_params wbp = bp;
+                wbp.width = ww; wbp.height = wh;
+                std::vector<unsigned char> lz((size_t)ww * wh * 4, 0);
+                const void *wl[32];
+                for (int l = 0; l < 2 * L; ++l) wl[l] = lz.data();
+                void *wo[1] = {o.data()};
+                MID_CHECK(mid_sequence_bilateral_temporal(ctxs[g], &wbp, wi, 2, use_layers ? wl : nullptr, L, k > 0 ? 1 : 0, 0, 1, wo, out_fmt, 1, nullptr));
             } else if (nlm_layers_t) {
                 std::vector<unsigned char> lz((size_t)ww * wh * 4, 0);
                 const void *wl[32];
@@ -681,6 +692,9 @@ public:
                     } else if (nlm_layers_t) { // this device's block plus k halo frames on either side, and their layers, from the host
                         MID_CHECK(mid_sequence_nlm_layers_temporal(ctx, &p, in.data(), n, layer_ptrs.data(), L, k, start, count,
                                                                    pin.outs.data() + start, out_fmt, 1, t));
+                    } else if (bil_t) {        // likewise, plain or with the layers
+                        MID_CHECK(mid_sequence_bilateral_temporal(ctx, &bp, in.data(), n, use_layers ? layer_ptrs.data() : nullptr, L, k, start, count,
+                                                                  pin.outs.data() + start, out_fmt, 1, t));
                     } else if (hdr) {
                         std::vector<mid_pixel *> o(count);
                         for (int i = 0; i < count; ++i) o[i] = (mid_pixel *)pin.outs[start + i];
@@ -703,11 +717,11 @@ public:
         m_execMs = *std::max_element(kern.begin(), kern.end());
         m_transferMs = *std::max_element(copy.begin(), copy.end());
         std::cout << "\tdecoded " << n << " frames into pinned memory in " << load_sec << " sec (" << io_threads << " file(s) at a time); device set-up + warm-up " << warm_sec << " sec\n";
-        std::cout << "\t" << n << " frames, " << (bil ? opt.animation_filter + " bilateral r=" + std::to_string(opt.radius) : nlm_layers ? "nonlocal + " + std::to_string(L) + " layers" : nlm_layers_t ? "nonlocal + " + std::to_string(L) + " layers, k=" + std::to_string(k) : "k=" + std::to_string(k))
+        std::cout << "\t" << n << " frames, " << (bil ? opt.animation_filter + " bilateral r=" + std::to_string(opt.radius) : nlm_layers ? "nonlocal + " + std::to_string(L) + " layers" : nlm_layers_t ? "nonlocal + " + std::to_string(L) + " layers, k=" + std::to_string(k) : bil_t ? "bilateral r=" + std::to_string(opt.radius) + (use_layers ? " + " + std::to_string(L) + " layers" : "") + ", k=" + std::to_string(k) : "k=" + std::to_string(k))
                   << ", " << G << " device(s): " << sec << " sec, "
                   << (double)n * w * h / 1e6 / sec << " Mpixel/s end to end (host frames in -> host frames out)\n";
         // SaveEXR :1699 / lodepng::encode :1717, straight from the pinned results -- one file per worker thread, like the decode
-        const std::string mode_name = nlm_layers ? "nonlinear-nlm-layers-" : nlm_layers_t ? "nonlinear-nlm-layers-multiframe-" : !bil ? "" : linear ? "linear-bialteral-" : use_layers ? "nonlinear-bialteral-layers-" : "nonlinear-bialteral-";
+        const std::string mode_name = nlm_layers ? "nonlinear-nlm-layers-" : nlm_layers_t ? "nonlinear-nlm-layers-multiframe-" : bil_t ? (use_layers ? "nonlinear-bialteral-layers-multiframe-" : "nonlinear-bialteral-multiframe-") : !bil ? "" : linear ? "linear-bialteral-" : use_layers ? "nonlinear-bialteral-layers-" : "nonlinear-bialteral-";
         const auto te0 = std::chrono::steady_clock::now();
         for_each_file(0, n, [&](int i) {
             const std::string name = "output-animation-" + mode_name + fs::path(frameNames[i]).stem().string() + (hdr || half ? ".exr" : ".png");
@@ -791,7 +805,12 @@ static void usage()
         "                            patch distance between frame t's layer and the neighbour frame's layer, the colour from the\n"
         "                            neighbour frame (--temporal-k, default 2; frame blocks take their K halo frames and layers\n"
         "                            from the host, not with --halo rccl), outputs\n"
-        "                            output-animation-nonlinear-nlm-layers-multiframe-*\n"
+        "                            output-animation-nonlinear-nlm-layers-multiframe-*;\n"
+        "                            or bilateral-temporal / layers-temporal: the bilateral over the frames t-K..t+K, plain or\n"
+        "                            guided by each frame's layers (K = --temporal-k, default 2; --radius / --sigma-s / --sigma-c\n"
+        "                            apply; halo frames and their layers from the host, not with --halo rccl), outputs\n"
+        "                            output-animation-nonlinear-bialteral-multiframe-* and\n"
+        "                            output-animation-nonlinear-bialteral-layers-multiframe-*\n"
         "  --gpus N                  animation mode: split the sequence into N frame blocks, one per device\n"
         "  --halo host|rccl          animation mode with --gpus N: 'host' (default) streams every block plus its K halo frames from host\n"
         "                            memory through the overlapped pipeline; 'rccl' keeps each block resident in its GPU's HBM and\n"
@@ -838,7 +857,8 @@ int main(int argc, char **argv)
         else if (a == "--animation-filter") {
             opt.animation_filter = next();
             const std::string &f = opt.animation_filter;
-            if (f != "nlm" && f != "bilateral" && f != "linear" && f != "layers" && f != "nlm-layers" && f != "nlm-layers-temporal") { std::cerr << "unknown --animation-filter " << f << "\n"; usage(); return EXIT_FAILURE; }
+            if (f != "nlm" && f != "bilateral" && f != "linear" && f != "layers" && f != "nlm-layers" && f != "nlm-layers-temporal" && f != "bilateral-temporal" && f != "layers-temporal") {
+                std::cerr << "unknown --animation-filter " << f << " (nlm, bilateral, linear, layers, nlm-layers, nlm-layers-temporal, bilateral-temporal, layers-temporal)\n"; usage(); return EXIT_FAILURE; }
         }
         else if (a == "--half") opt.half = true;
         else if (a == "--gpus") opt.gpus = atoi(next());
@@ -873,7 +893,7 @@ int main(int argc, char **argv)
         if (opt.animation) {
             const std::string &f = opt.animation_filter;
             std::cout << "######\nRunning on GPU (animation, " << (f == "nlm" ? "temporal nonlocal" : f == "linear" ? "linear bialteral" :
-                                                                 f == "layers" ? "nonlinear bialteral + layers" : f == "nlm-layers" ? "nonlocal + layers" : f == "nlm-layers-temporal" ? "nonlocal + layers, multiframe" : "nonlinear bialteral") << ")\n######\n";
+                                                                 f == "layers" ? "nonlinear bialteral + layers" : f == "nlm-layers" ? "nonlocal + layers" : f == "nlm-layers-temporal" ? "nonlocal + layers, multiframe" : f == "bilateral-temporal" ? "nonlinear bialteral, multiframe" : f == "layers-temporal" ? "nonlinear bialteral + layers, multiframe" : "nonlinear bialteral") << ")\n######\n";
             app.RunAnimation();
             print_time();
             return EXIT_SUCCESS;

@@ -158,6 +158,17 @@ int nlm_layers_temporal_out(mid_ctx *ctx, const mid_nlm_params *p, const void *c
                             int n_layers, int n_frames, int k, int first, int count, void *const *out, int out_fmt, hipStream_t s);
 int nlm_layers_temporal_fits(const char *who, int n_layers, int n_frames, int k);
 
+// The parameter checks of mid_bilateral (size, sigmas, radius, format, layout): bilateral.hip, shared with bilateral_temporal.hip.
+int bilateral_check_params(const mid_bilateral_params *p, const char *who);
+
+// mid_bilateral_temporal without its checks (the caller has made them), one launch per output frame on `s`; layers == nullptr is
+// the plain form: bilateral_temporal.hip; used by the frame pipeline (mid_sequence_bilateral_temporal), not exported.
+// bilateral_temporal_check: the checks both entry points share -- bilateral_check_params, the texture layout, n_layers in 0..16
+// (0 in the plain form), n_frames >= 1, k >= 0 and the pointer limit of one launch (nlm_layers_temporal_fits).
+int bilateral_temporal_out(mid_ctx *ctx, const mid_bilateral_params *p, const void *const *frames, const uint32_t *const *layers,
+                           int n_layers, int n_frames, int k, int first, int count, void *const *out, int out_fmt, hipStream_t s);
+int bilateral_temporal_check(const mid_bilateral_params *p, const char *who, bool layered, int n_layers, int n_frames, int k);
+
 // ROCTx ranges (csrc/markers.cpp): no-ops unless the process already holds a ROCTx (rocprofv3 --marker-trace preloads one).
 bool markers_active();
 void range_push(const char *name);

@@ -11,7 +11,8 @@
 //              mid_sequence_bilateral, window k = 0 -- the bilateral (plain, or guided by the layers) of ring slot t alone, or --
 //              for mid_sequence_nlm_layers, k = 0 -- NLM of ring slot t guided by its layers, or -- for
 //              mid_sequence_nlm_layers_temporal -- layer-guided NLM of output t over ring slots t-k..t+k and the layers uploaded
-//              with them
+//              with them, or -- for mid_sequence_bilateral_temporal -- the bilateral (plain or layer-guided) of output t over the
+//              same ring slots and layers
 //   download : hipMemcpyAsync device out slot t % 4 -> host   (RGBA32F and RGBA16F outputs, and RGBA8 outputs in pageable memory)
 //              RGBA8 outputs in page-locked memory have NO download stage: the kernel's epilogue stores the packed pixels
 //              straight into the caller's buffer (4 B per pixel = 17-19 GB/s at the kernel's frame rate, a third of the link);
@@ -109,7 +110,7 @@ struct Stage {
     const mid_nlm_params *nlm_layers;         // layer-guided NLM
     const void *const *host_layers;           // n_layers RGBA8 host layers per frame, frame-major; NULL: plain bilateral / no layers
     int n_layers;
-    bool temporal = false;                    // nlm_layers over the frames t-k..t+k (mid_sequence_nlm_layers_temporal), any k
+    bool temporal = false;                    // nlm_layers / bil over the frames t-k..t+k (mid_sequence_nlm_layers_temporal, mid_sequence_bilateral_temporal), any k
 };
 
 // Outputs [first, first+count) of an n-frame host sequence; frames outside that range are only
@@ -334,7 +335,14 @@ static int run_pipeline(mid_ctx *ctx, const Stage &st, const void *const *host_f
         } else {
             Range bil_range("bilateral %d", b0);
             MID_HIP(hipEventRecord(c0.ev[bi], cs));
-            for (int i = 0; i < bn; ++i) {        // (k = 0: output b0 + i reads ring slot b0 + i and its layers only)
+            if (st.temporal) {                    // output b0 + i reads ring slots b0+i-k .. b0+i+k and the layers uploaded with them
+                static_assert(B == 1, "one output per launch: its window is what bilateral_temporal_check admitted");
+                const uint32_t *lt[MID_NLM_LAYERS_TEMPORAL_MAX_POINTERS];      // the window's layers, frame-major like tbl
+                for (int f = lo; f <= need; ++f)
+                    for (int l = 0; l < n_layers; ++l) lt[(f - lo) * n_layers + l] = (const uint32_t *)layer_slot(f, l);
+                if (int rc = bilateral_temporal_out(ctx, st.bil, tbl, st.host_layers ? lt : nullptr, n_layers, need - lo + 1, k, b0 - lo, bn,
+                                                    (void *const *)o, out_fmt, cs)) return rc;
+            } else for (int i = 0; i < bn; ++i) { // (k = 0: output b0 + i reads ring slot b0 + i and its layers only)
                 const uint32_t *lt[16];
                 for (int l = 0; l < n_layers; ++l) lt[l] = (const uint32_t *)layer_slot(b0 + i, l);
                 if (int rc = bilateral_out(ctx, st.bil, slot(b0 + i), st.host_layers ? lt : nullptr, n_layers, o[i], out_fmt, cs)) return rc;
@@ -519,6 +527,44 @@ extern "C" int mid_sequence_nlm_layers_temporal(mid_ctx *ctx, const mid_nlm_para
                                 (const void *const *)host_out, count)) return rc;
     const Stage st{"sequence_nlm_layers_temporal", p->width, p->height, p->format, nullptr, nullptr, p, n_layers ? host_layers : nullptr,
                    n_layers, true};
+    return run_pipeline(ctx, st, host_frames, n_frames, k, first, count, host_out, out_format, overlap, timings_ms);
+}
+
+// The bilateral over neighbouring frames: mid_sequence_nlm_layers_temporal's schedule, layer ring and refusals with
+// bilateral_temporal_out as the compute stage; host_layers == NULL is the plain form.
+extern "C" int mid_sequence_bilateral_temporal(mid_ctx *ctx, const mid_bilateral_params *p, const void *const *host_frames, int n_frames,
+                                               const void *const *host_layers, int n_layers, int k, int first, int count,
+                                               void *const *host_out, int out_format, int overlap, float *timings_ms)
+{
+    Bind b(ctx, nullptr);
+    if (b.rc) return b.rc;
+    if (int rc = refuse_if_recording(ctx->compute, "mid_sequence_bilateral_temporal (four streams, host-side waits)")) return rc;
+    MID_REQUIRE(p && host_frames && host_out, "sequence_bilateral_temporal: NULL argument");
+    MID_REQUIRE(n_frames >= 1 && k >= 0 && 2 * (long)k + 2 <= kMaxFrames, "sequence_bilateral_temporal: bad n_frames=%d k=%d", n_frames, k);
+    MID_REQUIRE(first >= 0 && count >= 1 && (long)first + count <= n_frames,
+                "sequence_bilateral_temporal: bad range first=%d count=%d n_frames=%d", first, count, n_frames);
+    if (int rc = bilateral_temporal_check(p, "sequence_bilateral_temporal", host_layers != nullptr, n_layers, n_frames, k)) return rc;
+    MID_REQUIRE(fmt_known(out_format), "sequence_bilateral_temporal: unknown output format %d", out_format);
+    const int f_lo = first - k < 0 ? 0 : first - k;
+    const int f_hi = first + count - 1 + k > n_frames - 1 ? n_frames - 1 : first + count - 1 + k;
+    std::vector<const void *> inputs;
+    try {
+        inputs.reserve((size_t)(f_hi - f_lo + 1) * (n_layers + 1));
+    } catch (...) {
+        return set_error(MID_ERR_INVALID, "sequence_bilateral_temporal: no host memory for the alias check");
+    }
+    for (int f = f_lo; f <= f_hi; ++f) {
+        MID_REQUIRE(host_frames[f], "sequence_bilateral_temporal: frame %d is NULL", f);
+        inputs.push_back(host_frames[f]);
+        for (int l = 0; l < n_layers; ++l) {
+            MID_REQUIRE(host_layers[(size_t)f * n_layers + l], "sequence_bilateral_temporal: layer %d of frame %d is NULL", l, f);
+            inputs.push_back(host_layers[(size_t)f * n_layers + l]);
+        }
+    }
+    for (int i = 0; i < count; ++i) MID_REQUIRE(host_out[i], "sequence_bilateral_temporal: output %d is NULL", i);
+    if (int rc = check_no_alias("sequence_bilateral_temporal", "an input frame or layer of this call", inputs.data(), (int)inputs.size(),
+                                (const void *const *)host_out, count)) return rc;
+    const Stage st{"sequence_bilateral_temporal", p->width, p->height, p->format, nullptr, p, nullptr, host_layers, n_layers, true};
     return run_pipeline(ctx, st, host_frames, n_frames, k, first, count, host_out, out_format, overlap, timings_ms);
 }
 

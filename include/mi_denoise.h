@@ -287,6 +287,48 @@ int mid_nlm_layers_temporal(mid_ctx *ctx, const mid_nlm_params *p,
                             int n_layers, int n_frames, int k, int first, int count,
                             void *const *out /* host array of `count` device ptrs */, int out_format, void *stream);
 
+/* ---- a4d: the bilateral filter over neighbouring frames -----------------------------------
+ * mid_bilateral / mid_bilateral_layers with the neighbouring frames of an animation as further sources of samples.  Texture
+ * addressing only (out-of-image texel = vec4(0)); guides RGBA8, texels c/255; frames in p->format; radius, spatialSigma and
+ * colorSigma as in mid_bilateral.
+ * One pair dispatch has a target guide Gt, a neighbour guide Gn and a neighbour colour image In: for each pixel p and tap
+ * o = (i, j), |i|, |j| <= radius,
+ *   w = exp(-0.5 |o|^2 / spatialSigma^2) * exp(-0.5 |Gt(p) - Gn(p+o)|^2_rgb / colorSigma^2)
+ *   W[p].weightColor += w * In(p+o),   W[p].normWeight += w.
+ * Only the centre comes from the target; everything under the taps comes from the neighbour (bialteral_layers.comp with
+ * layerColor fetched from a second image).
+ * mid_bilateral_pair_accum = the plain form: Gt = target, Gn = In = neighbour, both frames in p->format.
+ * mid_bilateral_layers_pair_accum = the layered form: Gt = target_layer_rgba8, Gn = neighbour_layer_rgba8, In = neighbour_in.
+ * With target guide == neighbour guide (the same buffer, or equal texels) a pair dispatch gives the bits of
+ * mid_bilateral_layers_accum(p, neighbour_in, that layer, W).
+ * mid_bilateral_temporal = outputs [first, first+count) of a sequence of n_frames frames.  Output t: into a zeroed W, for each
+ * neighbour f = max(0,t-k) .. min(n_frames-1,t+k), ascending -- plain form (layers_rgba8 == NULL, n_layers must be 0): one
+ * mid_bilateral_pair_accum(frame[t], frame[f]); layered form: for each layer l = 0 .. n_layers-1, ascending, one
+ * mid_bilateral_layers_pair_accum(layer[t][l], layer[f][l], frame[f]) -- then mid_normalize and, for out_format MID_FMT_RGBA8 /
+ * MID_FMT_RGBA16F, mid_pack_u8 / mid_pack_f16.  Fused in one kernel per output frame (accumulators in registers, no WeightInfo
+ * traffic), with the bits of that chain of calls; with k == 0 the bits of mid_bilateral (plain) / mid_bilateral_layers
+ * (layered); layered with n_layers == 0 (a non-NULL table) every pixel is the magenta sentinel, as in mid_bilateral_layers.
+ * There is no temporal falloff weight: a neighbour frame weighs by range and space only, as in the temporal NLM modes.
+ * frames: host array of n_frames device pointers in p->format; layers_rgba8: host array of n_frames * n_layers device pointers,
+ * frame-major; out: host array of `count` device pointers in out_format.  Only the frames and layers of
+ * [first-k, first+count+k) are read.  Radii 4, 8, 10 and 20 run on tuned LDS-tiled kernels, every other radius on a
+ * run-time-radius tiled kernel, the layered form at radius > 17 (two tiles exceed LDS) on a per-pixel kernel.
+ * A launch carries the pointers of one output's window by value, so MID_ERR_INVALID, before anything is queued, for
+ *   min(2k+1, n_frames) * (n_layers + 1) > MID_NLM_LAYERS_TEMPORAL_MAX_POINTERS
+ * (the limit and the rule of mid_nlm_layers_temporal), and for: the parameter checks of mid_bilateral; MID_LAYOUT_LINEAR (the
+ * linear variant exists to time a buffer against a texture and has no temporal form); a NULL pointer; n_layers outside 0..16,
+ * or not 0 in the plain form; k < 0, first < 0, count < 1, first + count > n_frames; an unknown out_format; an RGBA16F frame or
+ * output that is not 8-byte aligned; an output that is also a frame or layer of the window, or appears twice. */
+int mid_bilateral_pair_accum(mid_ctx *ctx, const mid_bilateral_params *p, const void *target, const void *neighbour,
+                             mid_weightinfo *W, void *stream);
+int mid_bilateral_layers_pair_accum(mid_ctx *ctx, const mid_bilateral_params *p, const uint32_t *target_layer_rgba8,
+                                    const uint32_t *neighbour_layer_rgba8, const void *neighbour_in, mid_weightinfo *W, void *stream);
+int mid_bilateral_temporal(mid_ctx *ctx, const mid_bilateral_params *p,
+                           const void *const *frames /* host array of n_frames device ptrs */,
+                           const uint32_t *const *layers_rgba8 /* host array of n_frames * n_layers device ptrs, or NULL */,
+                           int n_layers, int n_frames, int k, int first, int count,
+                           void *const *out /* host array of `count` device ptrs */, int out_format, void *stream);
+
 /* ---- a5: normalize ----------------------------------------------------------------------
  * One dispatch of shaders/normalize.comp (RecordCommandsOfExecuteAndTransfer(normKernel=true)):
  * out = weightColor / normWeight, or (1,0,1,1) where normWeight == 0; bindings {0: out; 1: W}. */
@@ -390,7 +432,21 @@ int mid_sequence_nlm_layers_temporal(mid_ctx *ctx, const mid_nlm_params *p, cons
                                      const void *const *host_layers, int n_layers, int k, int first, int count,
                                      void *const *host_out, int out_format, int overlap, float *timings_ms);
 
-/* Debug export: the DEVICE timeline of this context's last mid_sequence_nlm*, mid_sequence_bilateral, mid_sequence_nlm_layers or
+/* The same pipeline with the bilateral over neighbouring frames as its compute stage: outputs [first, first+count) of the
+ * sequence, output t with the bits of mid_bilateral_temporal(p, frames, layers, k) for frame t in out_format.  host_layers ==
+ * NULL selects the plain form (n_layers must be 0).  Schedule, layer ring and output rule are mid_sequence_nlm_layers_temporal's:
+ * ring of 2k+4 frames, frame f's layers uploaded with frame f and alive as long as its slot, only the frames of
+ * [first-k, first+count+k) read, packed outputs stored by the kernel only when every one lies inside ONE page-locked allocation
+ * or registration.  MID_ERR_INVALID, before anything is queued, for: a NULL frame, layer or output of the range; n_layers
+ * outside 0..16 (not 0 in the plain form); bad k, first or count (k >= 0, 2k+2 <= 96, first >= 0, count >= 1, first + count <=
+ * n_frames); the pointer limit and the parameter checks of mid_bilateral_temporal (MID_LAYOUT_LINEAR among them); an unknown
+ * out_format; an output that is also an input frame or layer of the range (or appears twice); a call while the context's
+ * stream records. */
+int mid_sequence_bilateral_temporal(mid_ctx *ctx, const mid_bilateral_params *p, const void *const *host_frames, int n_frames,
+                                    const void *const *host_layers, int n_layers, int k, int first, int count,
+                                    void *const *host_out, int out_format, int overlap, float *timings_ms);
+
+/* Debug export: the DEVICE timeline of this context's last mid_sequence_nlm*, mid_sequence_bilateral[_temporal], mid_sequence_nlm_layers or
  * mid_sequence_nlm_layers_temporal call, from the events the call recorded on
  * its streams (no profiler: the call ran at its own pace).  All times in ms from the start of the call's first upload.
  * upload_ms[2*i], [2*i+1]: start / end of the upload of frame first_upload_frame + i; output_ms[4*j .. 4*j+3]: kernel

@@ -18,6 +18,8 @@ int mid::bilateral_out(mid_ctx *, const mid_bilateral_params *, const void *, co
 int mid::nlm_layers_out(mid_ctx *, const mid_nlm_params *, const void *, const uint32_t *const *, int, void *, int, hipStream_t) { return MID_ERR_UNSUPPORTED; }   // (nlm_layers.hip)
 int mid::nlm_layers_temporal_out(mid_ctx *, const mid_nlm_params *, const void *const *, const uint32_t *const *, int, int, int, int, int, void *const *, int, hipStream_t) { return MID_ERR_UNSUPPORTED; }   // (nlm_layers_temporal.hip)
 int mid::nlm_layers_temporal_fits(const char *, int, int, int) { return MID_ERR_UNSUPPORTED; }   // (nlm_layers_temporal.hip)
+int mid::bilateral_temporal_out(mid_ctx *, const mid_bilateral_params *, const void *const *, const uint32_t *const *, int, int, int, int, int, void *const *, int, hipStream_t) { return MID_ERR_UNSUPPORTED; }   // (bilateral_temporal.hip)
+int mid::bilateral_temporal_check(const mid_bilateral_params *, const char *, bool, int, int, int) { return MID_ERR_UNSUPPORTED; }   // (bilateral_temporal.hip)
 int mid::nlm_check_params(const mid_nlm_params *) { return MID_ERR_UNSUPPORTED; }   // (nlm.hip)
 
 int main()
