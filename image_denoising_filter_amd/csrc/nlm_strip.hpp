@@ -5,6 +5,7 @@
 // fp32, other priorities ...) is indexed in tools/experiments/README.md; none of it is in this file.
 #pragma once
 #include "common.hpp"
+#include "nlm_vbox_plan.hpp"
 #include <cmath>
 #include <cstdlib>
 #include <type_traits>
@@ -40,7 +41,8 @@ struct NlmArgs {
 // (Pf); a window that starts inside block b is S[k] (rest of block b) + Pf[k+PW-1] (head of block b+1), a
 // window that starts on a block boundary is that block's total.  PW=7, R=8: 18 additions for 8 outputs
 // instead of 36 with shared pair/quad sums (48 direct).  Every partial sum only ever adds non-negative
-// terms, so there is no cancellation; unused S/Pf entries are dead code after unrolling.
+// terms, so there is no cancellation; unused S/Pf entries are dead code after unrolling.  (The layer-guided kernels' form; the strip
+// kernel below evaluates the same decomposition fused with its distances, by the plan of nlm_vbox_plan.hpp.)
 template <int PW, int R>
 __device__ __forceinline__ void vertical_box(const float (&D)[R + PW - 1], float (&V)[R])
 {
@@ -63,29 +65,11 @@ __device__ __forceinline__ void vertical_box(const float (&D)[R + PW - 1], float
     }
 }
 
-// The vertical sums of HALF an 8-row strip -- output rows 0..3 (lower == false) or 4..7 (lower == true) from the 4 + PW - 1 rows they
-// need -- with the additions of vertical_box<PW, 8> for those rows, in its order: the block decomposition is evaluated in the 8-row
-// strip's frame with the rows outside this half left out (none of them feeds the half's outputs; they fold away).  Two waves that take
-// one half each therefore produce the bits one wave produces for the whole strip.
-template <int PW, bool LOWER>
-__device__ __forceinline__ void vertical_box_half(const float (&D)[4 + PW - 1], float (&V)[4])
-{
-    constexpr int N8 = 8 + PW - 1;
-    float D8[N8], V8[8];
-    if constexpr (LOWER) {
-#pragma unroll
-        for (int m = 0; m < N8; ++m) D8[m] = (m >= 4) ? D[m - 4] : 0.f;
-        vertical_box<PW, 8>(D8, V8);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) V[k] = V8[k + 4];
-    } else {
-#pragma unroll
-        for (int m = 0; m < N8; ++m) D8[m] = (m < 4 + PW - 1) ? D[m] : 0.f;
-        vertical_box<PW, 8>(D8, V8);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) V[k] = V8[k];
-    }
-}
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): a loop whose index is a constant expression in its body
+template <class F, int... I>
+__device__ __forceinline__ void static_for_impl(F &&f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
+template <int N, class F>
+__device__ __forceinline__ void static_for(F &&f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
 
 // H[l] = sum_{i=PLO}^{PHI-1} V[l+i] across lanes; valid for lanes -PLO .. 63-(PHI-1).
 template <int PLO, int PHI>
@@ -121,7 +105,7 @@ constexpr int nlm_min_waves(bool rts, bool multi, int pw)
 // from the arguments instead of being folded constants.
 // HALF: the launch shape for the last, partly filled round of a small launch.  Eight waves per workgroup on the SAME 32-row tile,
 // each taking half of an 8-row strip (R = 4; even waves the upper, odd waves the lower four rows) with the strip's own vertical sums
-// (vertical_box_half): identical output bits, 0.6 of a strip's instructions per wave, and two waves per SIMD on a CU that holds this
+// (the plan of nlm_vbox_plan.hpp for its four output rows): identical output bits, 0.6 of a strip's instructions per wave, and two waves per SIMD on a CU that holds this
 // workgroup alone -- where a 4-wave workgroup alone leaves every wave a SIMD to itself at half issue rate.
 // TAG: no effect on the code -- it only names a second copy of an instantiation, so that the copies in nlm_small.hip (compiled with another
 // scheduling strategy, see there) and in nlm.hip are different symbols.
@@ -269,13 +253,41 @@ void nlm_strip_kernel(const NlmArgs a)
         // (LT: std::bool_constant -- the lower half of a strip in the HALF shape; the two halves are two copies of the loop, chosen
         // per wave by a scalar branch around a whole run, so that each copy is straight-line code)
         auto step = [&](auto LT, auto A1, int j, float4 (&n)[DR], const float4 *nextp, bool more) {
-            float D[DR];
-#pragma unroll
-            for (int m = 0; m < DR; ++m) {
-                const float4 &t = n[(j + m) % DR];
-                const float dx = Tr[m] - t.x, dy = Tg[m] - t.y, dz = Tb[m] - t.z;
-                D[m] = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
-            }
+            // Distances and vertical patch sums in one piece, by the plan of nlm_vbox_plan.hpp for this wave's output rows (HALF: its
+            // half of the 8-row strip, in the strip's frame -- the same operations on the same operands as the whole strip's, so
+            // the same bits).  A single-use row's squared differences are accumulated onto the running sum it continues (three
+            // FMAs, no separate add); the first row of a running sum and rows that two sums share are formed on their own and
+            // added.  The two kinds of running sums are issued alternately, row by row.
+            constexpr int OFF = (HALF && decltype(LT)::value) ? 4 : 0;      // this wave's first output row in the strip's frame
+            using Plan = VboxPlanOf<PW, HALF ? 8 : R, OFF, OFF + R>;
+            constexpr int N = Plan::plan.n;
+            constexpr bool FOLD = Plan::plan.folded > 0;    // (nothing to fold: the additions stay behind the priority change, as before)
+            float S[N], Pf[N], D[N];
+            auto add_row = [&](auto I) {
+                constexpr int i = decltype(I)::value, m = Plan::order.row[i];
+                constexpr VboxRow row = Plan::plan.row[m];
+                if constexpr (Plan::order.is_s[i]) {
+                    if constexpr (row.s_from < 0) S[m] = D[m]; else S[m] = D[m] + S[row.s_from];
+                } else {
+                    if constexpr (row.p_from < 0) Pf[m] = D[m]; else Pf[m] = Pf[row.p_from] + D[m];
+                }
+            };
+            static_for<Plan::order.count>([&](auto I) {
+                constexpr int i = decltype(I)::value, m = Plan::order.row[i];
+                constexpr VboxRow row = Plan::plan.row[m];
+                const float4 &t = n[(j + m - OFF) % DR];
+                if constexpr (row.single) {
+                    const float dx = Tr[m - OFF] - t.x, dy = Tg[m - OFF] - t.y, dz = Tb[m - OFF] - t.z;
+                    if constexpr (Plan::order.is_s[i]) S[m] = fmaf(dz, dz, fmaf(dy, dy, fmaf(dx, dx, S[row.s_from])));
+                    else Pf[m] = fmaf(dz, dz, fmaf(dy, dy, fmaf(dx, dx, Pf[row.p_from])));
+                } else {
+                    if constexpr (Plan::order.first[i]) {
+                        const float dx = Tr[m - OFF] - t.x, dy = Tg[m - OFF] - t.y, dz = Tb[m - OFF] - t.z;
+                        D[m] = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
+                    }
+                    if constexpr (FOLD) add_row(I);
+                }
+            });
             // the row that leaves the window: its alpha was never used unless it has been a centre row; keep it formally
             // live up to here so that every tile read stays a ds_read_b128 (4 LDS cycles; a ds_read_b96 takes 8), then reuse
             // its slot for the row that enters
@@ -283,10 +295,18 @@ void nlm_strip_kernel(const NlmArgs a)
                 asm volatile("" ::"v"(n[j % DR].w));
                 if (more) n[j % DR] = nextp[0];
             }
-            raise_priority();
+            if constexpr (!FOLD) raise_priority();
+            if constexpr (!FOLD) static_for<Plan::order.count>(add_row);
+            // (with folded rows the few additions that are left -- six for the 7x7 patch -- belong to the distance phase: measured 0.6 %
+            // faster than behind the priority change, profiles/r07_ab_nlm_folded_distance.txt)
             float V[R];
-            if constexpr (HALF) vertical_box_half<PW, decltype(LT)::value>(D, V);
-            else vertical_box<PW, R>(D, V);
+            static_for<R>([&](auto K) {
+                constexpr int k = decltype(K)::value + OFF;
+                if constexpr (Plan::plan.v_uses_s(k) && Plan::plan.v_uses_p(k)) V[k - OFF] = S[k] + Pf[k + PW - 1];
+                else if constexpr (Plan::plan.v_uses_s(k)) V[k - OFF] = S[k];
+                else V[k - OFF] = Pf[k + PW - 1];
+            });
+            if constexpr (FOLD) raise_priority();
             float dd[R], ww[R];
 #pragma unroll
             for (int k = 0; k < R; ++k) dd[k] = horizontal_box<PLO, PHI>(V[k]);

@@ -225,7 +225,9 @@ int mid_bilateral_layers(mid_ctx *ctx, const mid_bilateral_params *p, const void
  * mid_nlm_temporal = the multi-frame mode (src/main.cpp:1539-1606) for an animation: for each
  * output frame t in [first, first+count) it accumulates over neighbour frames
  * max(0,t-k)..min(n_frames-1,t+k) in ascending order (target = frame t) and normalizes, all in
- * one launch (grid.z = output frame); k = 0 is independent single-frame NLM over a batch. */
+ * one launch (grid.z = output frame); k = 0 is independent single-frame NLM over a batch.
+ * (Version note: the strip kernels now add most rows' squared differences straight onto the vertical running sums, one rounding fewer
+ * per row -- the last bits of NLM outputs differ from earlier builds; they still do not depend on the launch shape.) */
 int mid_nlm_accum(mid_ctx *ctx, const mid_nlm_params *p, const void *target,
                   const void *neighbour, mid_weightinfo *W, void *stream);
 /* (mid_nlm_temporal: no aliasing -- an `out` buffer must not be a frame of the sequence nor appear twice: MID_ERR_INVALID, as for mid_bilateral_batch.) */

@@ -151,7 +151,8 @@ if bil:
 N_SIMD, N_CU, N_XCD = 1024, 256, 8
 # instruction classes of the inner loops, from the ISA (llvm -S census): share of the VALU
 # wave-instructions that are DPP adds and transcendentals (v_exp_f32); the rest are plain full-rate fp32/int VALU
-CLASSES = {"nlm": {"dpp": 48 / 198, "trans": 8 / 198}, "bilateral": {"dpp": 0.0, "trans": 34 / 420}}
+CLASSES = {"nlm": {"dpp": 48 / 186, "trans": 8 / 186},    # (round 7: 186 per offset, 198 before the vertical sums moved into the distance FMAs)
+           "bilateral": {"dpp": 0.0, "trans": 34 / 420}}
 # Issue cost per wave-instruction on one SIMD, cycles.
 # "floor": what the hardware can do at best, from tools/microbench17.hip (two DIFFERENT streams on the two waves of a SIMD,
 # profiles/r04_microbench17_two_streams.txt): a wave64 VALU instruction occupies the SIMD-32 for 2 cycles; a DPP add costs 4 beside
@@ -241,7 +242,7 @@ def utilisation(key, cls, offsets=None):
     if offsets and "SQ_WAVES" in d:
         per = simd_cyc / (d["SQ_WAVES"] * offsets)              # SIMD cycles per (wave, search offset): both waves of a SIMD counted
         sh_ = CLASSES[cls]
-        n_inst = d["SQ_INSTS_VALU"] / (d["SQ_WAVES"] * offsets)  # VALU wave-instructions per wave-offset (198-199 in the hot loop + prologue share)
+        n_inst = d["SQ_INSTS_VALU"] / (d["SQ_WAVES"] * offsets)  # VALU wave-instructions per wave-offset (186-187 in the hot loop, 179 in its opaque form, + prologue share)
         floor = n_inst * ((1 - sh_["dpp"] - sh_["trans"]) * 2.0 + sh_["dpp"] * 2.0 + sh_["trans"] * 8.0)
         occ = n_inst * ((1 - sh_["dpp"] - sh_["trans"]) * COST["nlm_occupancy"]["plain"] + sh_["dpp"] * 2.39 + sh_["trans"] * 8.09)
         u["cycles_per_wave_offset"] = {"measured": round(per, 1), "floor": round(floor, 1), "at_occupancy_prices": round(occ, 1),
