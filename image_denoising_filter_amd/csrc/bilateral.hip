@@ -13,10 +13,18 @@
 // The texture and linear variants differ only in how the tile is addressed when it is filled
 // (2-D zero border vs flat index with row wrap-around), exactly the difference between
 // bialteral.comp:58-59 and bialteral_linear.comp:58.
-#include "common.hpp"
-#include <cmath>
+//
+// The tap loops, the guide prefetch, the opaque vote and the epilogue below are restated in bilateral_temporal.hip, whose kernels
+// put a loop over neighbouring frames around them.  The copies are deliberate.  With both files calling one set of
+// __forceinline__ function templates the instruction mix, LDS and occupancy classes stayed the same but register allocation
+// did not, and on an MI355X (profiles/r10_ab_shared_filter_bodies.txt; medians in ms, parent -> shared, parent-against-parent
+// spread 0.0000-0.0012) r = 20 went 0.9281 -> 0.9390 (+1.2 %), r = 4 0.0495 -> 0.0497, layers fused r = 8 L = 1 0.1648 -> 0.1671
+// (+1.4 %), r = 10 L = 4 1.0021 -> 1.0096, run-time radius r = 3 / 12 / 16 +0.3-3 %; only r = 8 and r = 10 held.  These are the
+// bench paths.  A change to the tap arithmetic has to be made in both files; the k = 0 identities of
+// tests/test_gpu_bilateral_temporal.py fail when only one is changed, tests/test_gpu_kernel_bits.py when the bits move at all.
+// Shared with that file: the scales and the table of tuned radii and tile shapes (bilateral_shapes.hpp), store_out (common.hpp).
+#include "bilateral_shapes.hpp"
 #include <cstdlib>
-#include <type_traits>
 
 namespace mid {
 
@@ -30,17 +38,8 @@ struct BilArgs {
     mid_weightinfo *W;     // layers accumulate mode
     int n_layers;
     int out_fmt;           // MID_FMT_* of `out`: float4, RGBA8 (pack_rgba8) or RGBA16F (pack_rgba16f); a kernarg, so wave-uniform
-    const uint32_t *layers[16];
+    const uint32_t *layers[kMaxLayers];
 };
-
-// The plain / fused-layers epilogue: one pixel in the output format of the launch (the frame pipeline's packed outputs; every
-// single-frame entry point passes MID_FMT_RGBA32F).  The same rounding as mid_pack_u8 / mid_pack_f16 of the float4 result.
-__device__ __forceinline__ void store_out(void *out, size_t idx, int fmt, float4 o)
-{
-    if (fmt == MID_FMT_RGBA8) ((uint32_t *)out)[idx] = pack_rgba8(o);
-    else if (fmt == MID_FMT_RGBA16F) ((uint2 *)out)[idx] = pack_rgba16f(o);
-    else ((float4 *)out)[idx] = o;
-}
 
 // Frame tables of the batched plain bilateral (mid_bilateral_batch): passed by value in kernarg space like the NLM
 // kernels' tables.  Single-frame launches pass the empty BilOne instead, so their kernarg block stays small.
@@ -454,8 +453,7 @@ __global__ __launch_bounds__(256) void bilateral_generic_kernel(const BilArgs a,
 template <int R, int P, int NW, int FMT, bool LINEAR, int MODE, typename BT>
 static int launch_tiled(mid_ctx *ctx, BilArgs &a, const BT &bt, int n_frames, hipStream_t s)
 {
-    constexpr int LW = 64 + 2 * R, LH = NW * P + 2 * R;
-    constexpr size_t lds_bytes = (size_t)LW * LH * sizeof(float4) * (MODE == 0 ? 1 : 2);
+    constexpr size_t lds_bytes = bil_lds_bytes(R, NW * P, MODE != 0);
     auto kern = bilateral_kernel<R, P, NW, FMT, LINEAR, MODE, BT>;
     if ((int)lds_bytes > ctx->lds_max)
         return set_error(MID_ERR_UNSUPPORTED, "bilateral tile needs %zu B of LDS, device offers %d", lds_bytes, ctx->lds_max);
@@ -471,35 +469,27 @@ static int launch_tiled(mid_ctx *ctx, BilArgs &a, const BT &bt, int n_frames, hi
 template <int FMT, bool LINEAR, int MODE, typename BT = BilOne>
 static int dispatch_radius(mid_ctx *ctx, int radius, BilArgs &a, hipStream_t s, const BT &bt = BT{}, int n_frames = 1)
 {
-    // Tile shapes by A/B on MI355X (tools/ab_bil.py): the kernel is latency-sensitive, so many
-    // independent waves (P = 2 rows per lane, 8 waves per workgroup) beat deeper register blocking.
-    switch (radius) {
-    case 4:  return launch_tiled<4, 2, 8, FMT, LINEAR, MODE, BT>(ctx, a, bt, n_frames, s);    // BASELINE config 1 window
-    case 8:  return launch_tiled<8, 2, 8, FMT, LINEAR, MODE, BT>(ctx, a, bt, n_frames, s);    // BASELINE configs[1] and [3] (layer modes: also best of six shapes, profiles/r05_ab_layer_tile_shapes.txt)
-    case 10: return launch_tiled<10, 2, 16, FMT, LINEAR, MODE, BT>(ctx, a, bt, n_frames, s);  // CPU path window, src/main.cpp:1819
-    case 20:                                                                 // TEXEL_WINDOW as shipped
-        return launch_tiled<20, 1, 8, FMT, LINEAR, MODE, BT>(ctx, a, bt, n_frames, s);          // 80 KB tile: two workgroups per CU (or image + guide tile)
-    default: break;
-    }
-    {   // run-time radius, LDS tiled
-        const size_t lds_bytes = (size_t)(64 + 2 * radius) * (16 + 2 * radius) * sizeof(float4) * (MODE == 0 ? 1 : 2);
-        if ((int)lds_bytes <= ctx->lds_max) {
-            auto kern = bilateral_rt_kernel<FMT, LINEAR, MODE, BT>;
-            if (int rc = ensure_lds(ctx, (const void *)kern, (size_t)ctx->lds_max)) return rc;
-            a.tiles_x = (int)cdiv(a.w, 64);
-            a.tiles_y = (int)cdiv(a.h, 16);
-            hipLaunchKernelGGL(kern, dim3((unsigned)a.tiles_x * a.tiles_y * (unsigned)n_frames), dim3(512), lds_bytes, s, a, radius, bt);
+    return bil_for_radius(radius,
+        [&](auto sh) { return launch_tiled<decltype(sh)::R, decltype(sh)::P, decltype(sh)::NW, FMT, LINEAR, MODE, BT>(ctx, a, bt, n_frames, s); },
+        [&]() -> int {
+            const size_t lds_bytes = bil_lds_bytes(radius, kBilRtNW * kBilRtP, MODE != 0);
+            if ((int)lds_bytes <= ctx->lds_max) {    // run-time radius, LDS tiled
+                auto kern = bilateral_rt_kernel<FMT, LINEAR, MODE, BT>;
+                if (int rc = ensure_lds(ctx, (const void *)kern, (size_t)ctx->lds_max)) return rc;
+                a.tiles_x = (int)cdiv(a.w, 64);
+                a.tiles_y = (int)cdiv(a.h, kBilRtNW * kBilRtP);
+                hipLaunchKernelGGL(kern, dim3((unsigned)a.tiles_x * a.tiles_y * (unsigned)n_frames), dim3(kBilRtNW * 64), lds_bytes, s, a, radius, bt);
+                MID_HIP(hipGetLastError());
+                return MID_OK;
+            }
+            // (unreachable for the plain bilateral: its single tile fits LDS for every legal radius; only the two-tile
+            // layer modes at r > 17 get here, and those are never batched)
+            if (n_frames != 1) return set_error(MID_ERR_UNSUPPORTED, "bilateral: no batched kernel for radius %d", radius);
+            dim3 grid(cdiv(a.w, 16), cdiv(a.h, 16));
+            hipLaunchKernelGGL((bilateral_generic_kernel<FMT, LINEAR, MODE>), grid, dim3(256), 0, s, a, radius);
             MID_HIP(hipGetLastError());
             return MID_OK;
-        }
-    }
-    // (unreachable for the plain bilateral: its single tile fits LDS for every legal radius; only the two-tile
-    // layer modes at r > 17 get here, and those are never batched)
-    if (n_frames != 1) return set_error(MID_ERR_UNSUPPORTED, "bilateral: no batched kernel for radius %d", radius);
-    dim3 grid(cdiv(a.w, 16), cdiv(a.h, 16));
-    hipLaunchKernelGGL((bilateral_generic_kernel<FMT, LINEAR, MODE>), grid, dim3(256), 0, s, a, radius);
-    MID_HIP(hipGetLastError());
-    return MID_OK;
+        });
 }
 
 static int check_params(const mid_bilateral_params *p, const char *who)
@@ -525,20 +515,11 @@ static int dispatch_format(mid_ctx *ctx, int format, int radius, BilArgs &a, hip
     return dispatch_radius<MID_FMT_RGBA32F, LINEAR, MODE, BT>(ctx, radius, a, s, bt, n_frames);
 }
 
-static void fill_scales(const mid_bilateral_params *p, BilArgs &a)
-{
-    a.w = p->width; a.h = p->height;
-    a.ks = (float)(-0.5 * 1.4426950408889634 / ((double)p->spatialSigma * (double)p->spatialSigma));
-    a.kc = (float)(-0.5 * 1.4426950408889634 / ((double)p->colorSigma * (double)p->colorSigma));
-    a.sc = (float)(sqrt(0.5 * 1.4426950408889634) / (double)p->colorSigma);
-    a.inv_sc = (float)(1.0 / (double)a.sc);
-}
-
 int bilateral_out(mid_ctx *ctx, const mid_bilateral_params *p, const void *in, const uint32_t *const *layers, int n_layers,
                   void *out, int out_fmt, hipStream_t s)
 {
     BilArgs a{};
-    fill_scales(p, a);
+    bil_fill_scales(p, a);
     a.in = in; a.out = out; a.out_fmt = out_fmt;
     if (!layers) {
         if (p->layout == MID_LAYOUT_LINEAR) return dispatch_format<true, 0>(ctx, p->format, p->radius, a, s);
@@ -576,7 +557,7 @@ extern "C" int mid_bilateral_layers_accum(mid_ctx *ctx, const mid_bilateral_para
     // NLM/layers are only ever bound to textures in the reference (src/main.cpp:1406-1428).
     MID_REQUIRE(p->layout == MID_LAYOUT_TEXTURE, "bilateral_layers_accum: layers exist for the texture layout only");
     BilArgs a{};
-    fill_scales(p, a);
+    bil_fill_scales(p, a);
     a.in = in; a.W = W; a.n_layers = 1; a.layers[0] = layer;
     return dispatch_format<false, 1>(ctx, p->format, p->radius, a, b.s);
 }
@@ -591,7 +572,7 @@ extern "C" int mid_bilateral_layers(mid_ctx *ctx, const mid_bilateral_params *p,
     MID_REQUIRE(fmt_aligned(p->format, in), "bilateral_layers: RGBA16F input must be 8-byte aligned");
     MID_REQUIRE((const void *)out != in, "bilateral_layers: out is the input image (in-place filtering is not supported)");
     MID_REQUIRE(p->layout == MID_LAYOUT_TEXTURE, "bilateral_layers: layers exist for the texture layout only");
-    MID_REQUIRE(n_layers >= 0 && n_layers <= 16, "bilateral_layers: n_layers %d outside 0..16", n_layers);
+    MID_REQUIRE(n_layers >= 0 && n_layers <= kMaxLayers, "bilateral_layers: n_layers %d outside 0..16", n_layers);
     for (int i = 0; i < n_layers; ++i) MID_REQUIRE(layers[i] != nullptr, "bilateral_layers: layer %d is NULL", i);
     return bilateral_out(ctx, p, in, layers, n_layers, out, MID_FMT_RGBA32F, b.s);
 }
@@ -613,7 +594,7 @@ extern "C" int mid_bilateral_batch(mid_ctx *ctx, const mid_bilateral_params *p, 
     for (int c0 = 0; c0 < n_frames; c0 += kMaxFrames) {          // one launch per kMaxFrames frames
         const int cn = n_frames - c0 < kMaxFrames ? n_frames - c0 : kMaxFrames;
         BilArgs a{};
-        fill_scales(p, a);
+        bil_fill_scales(p, a);
         BilBatch bt{};
         for (int i = 0; i < cn; ++i) { bt.in.p[i] = in[c0 + i]; bt.out.p[i] = out[c0 + i]; }
         int rc;

@@ -25,10 +25,7 @@
 //
 // Kernel arguments: as nlm_layers_temporal.hip, one launch per output frame carries that output's window by value -- for each
 // neighbour its frame pointer and its L layer pointers -- at most MID_NLM_LAYERS_TEMPORAL_MAX_POINTERS of them.
-#include "common.hpp"
-#include <cmath>
-#include <type_traits>
-#include <vector>
+#include "bilateral_shapes.hpp"
 
 namespace mid {
 
@@ -52,19 +49,10 @@ struct BilPairArgs {
     const void *p[kMaxPtrs];            // slot j: p[j * (n_layers + 1)] = frame, then its n_layers guide layers
 };
 
-// (xcd_remap and store_out restate bilateral.hip's xcd_remap_b and store_out: that file is left as it is, so that its code
-// objects do not change)
 __device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nwg)
 {
     const unsigned q = nwg >> 3, r = nwg & 7u, x = bid & 7u, i = bid >> 3;
     return x * q + (x < r ? x : r) + i;
-}
-
-__device__ __forceinline__ void store_out(void *out, size_t idx, int fmt, float4 o)
-{
-    if (fmt == MID_FMT_RGBA8) ((uint32_t *)out)[idx] = pack_rgba8(o);
-    else if (fmt == MID_FMT_RGBA16F) ((uint2 *)out)[idx] = pack_rgba16f(o);
-    else ((float4 *)out)[idx] = o;
 }
 
 __device__ __forceinline__ const void *nb_frame(const BilPairArgs &a, int j) { return a.p[j * (a.n_layers + 1)]; }
@@ -441,8 +429,7 @@ __global__ __launch_bounds__(256) void bilateral_pair_generic_kernel(const BilPa
 template <int R, int P, int NW, bool LAYERED, bool FUSED>
 int launch_pair_tiled(mid_ctx *ctx, BilPairArgs &a, hipStream_t s)
 {
-    constexpr int LW = 64 + 2 * R, LH = NW * P + 2 * R;
-    constexpr size_t lds_bytes = (size_t)LW * LH * sizeof(float4) * (LAYERED ? 2 : 1);
+    constexpr size_t lds_bytes = bil_lds_bytes(R, NW * P, LAYERED);
     auto kern = bilateral_pair_kernel<R, P, NW, LAYERED, FUSED>;
     if ((int)lds_bytes > ctx->lds_max)
         return set_error(MID_ERR_UNSUPPORTED, "bilateral_temporal tile needs %zu B of LDS, device offers %d", lds_bytes, ctx->lds_max);
@@ -457,45 +444,35 @@ int launch_pair_tiled(mid_ctx *ctx, BilPairArgs &a, hipStream_t s)
 template <bool LAYERED, bool FUSED>
 int dispatch_pair(mid_ctx *ctx, int radius, BilPairArgs &a, hipStream_t s)
 {
-    // The radii and tile shapes of bilateral.hip's dispatch_radius, all four: a radius must run the arithmetic of its
-    // single-frame kernel (the tuned kernels add the spatial term as si + ks*j^2, the run-time one as fma(ks, j^2, si)), or
-    // k = 0 would not give the bits of mid_bilateral / mid_bilateral_layers.
-    switch (radius) {
-    case 4:  return launch_pair_tiled<4, 2, 8, LAYERED, FUSED>(ctx, a, s);
-    case 8:  return launch_pair_tiled<8, 2, 8, LAYERED, FUSED>(ctx, a, s);
-    case 10: return launch_pair_tiled<10, 2, 16, LAYERED, FUSED>(ctx, a, s);
-    case 20: return launch_pair_tiled<20, 1, 8, LAYERED, FUSED>(ctx, a, s);
-    default: break;
-    }
-    const size_t lds_bytes = (size_t)(64 + 2 * radius) * (16 + 2 * radius) * sizeof(float4) * (LAYERED ? 2 : 1);
-    if ((int)lds_bytes <= ctx->lds_max) {
-        auto kern = bilateral_pair_rt_kernel<LAYERED, FUSED>;
-        if (int rc = ensure_lds(ctx, (const void *)kern, (size_t)ctx->lds_max)) return rc;
-        a.tiles_x = (int)cdiv(a.w, 64);
-        a.tiles_y = (int)cdiv(a.h, 16);
-        hipLaunchKernelGGL(kern, dim3((unsigned)a.tiles_x * a.tiles_y), dim3(512), lds_bytes, s, a, radius);
-        MID_HIP(hipGetLastError());
-        return MID_OK;
-    }
-    // (only the two-tile layered form at r > 17 gets here: the plain form's single tile fits LDS for every legal radius)
-    if constexpr (LAYERED) {
-        const dim3 grid(cdiv(a.w, 16), cdiv(a.h, 16));
-        hipLaunchKernelGGL((bilateral_pair_generic_kernel<FUSED>), grid, dim3(256), 0, s, a, radius);
-        MID_HIP(hipGetLastError());
-        return MID_OK;
-    } else {
-        return set_error(MID_ERR_UNSUPPORTED, "bilateral_temporal: the tile of radius %d does not fit %d B of LDS", radius, ctx->lds_max);
-    }
+    return bil_for_radius(radius,
+        [&](auto sh) { return launch_pair_tiled<decltype(sh)::R, decltype(sh)::P, decltype(sh)::NW, LAYERED, FUSED>(ctx, a, s); },
+        [&]() -> int {
+            const size_t lds_bytes = bil_lds_bytes(radius, kBilRtNW * kBilRtP, LAYERED);
+            if ((int)lds_bytes <= ctx->lds_max) {
+                auto kern = bilateral_pair_rt_kernel<LAYERED, FUSED>;
+                if (int rc = ensure_lds(ctx, (const void *)kern, (size_t)ctx->lds_max)) return rc;
+                a.tiles_x = (int)cdiv(a.w, 64);
+                a.tiles_y = (int)cdiv(a.h, kBilRtNW * kBilRtP);
+                hipLaunchKernelGGL(kern, dim3((unsigned)a.tiles_x * a.tiles_y), dim3(kBilRtNW * 64), lds_bytes, s, a, radius);
+                MID_HIP(hipGetLastError());
+                return MID_OK;
+            }
+            // (only the two-tile layered form at r > 17 gets here: the plain form's single tile fits LDS for every legal radius)
+            if constexpr (LAYERED) {
+                const dim3 grid(cdiv(a.w, 16), cdiv(a.h, 16));
+                hipLaunchKernelGGL((bilateral_pair_generic_kernel<FUSED>), grid, dim3(256), 0, s, a, radius);
+                MID_HIP(hipGetLastError());
+                return MID_OK;
+            } else {
+                return set_error(MID_ERR_UNSUPPORTED, "bilateral_temporal: the tile of radius %d does not fit %d B of LDS", radius, ctx->lds_max);
+            }
+        });
 }
 
 void init_args(BilPairArgs &a, const mid_bilateral_params *p)
 {
-    a.w = p->width; a.h = p->height; a.fmt = p->format;
-    // (bilateral.hip's fill_scales)
-    a.ks = (float)(-0.5 * 1.4426950408889634 / ((double)p->spatialSigma * (double)p->spatialSigma));
-    a.kc = (float)(-0.5 * 1.4426950408889634 / ((double)p->colorSigma * (double)p->colorSigma));
-    a.sc = (float)(sqrt(0.5 * 1.4426950408889634) / (double)p->colorSigma);
-    a.inv_sc = (float)(1.0 / (double)a.sc);
+    bil_fill_scales(p, a);
+    a.fmt = p->format;
 }
 
 // mid_bilateral's parameter checks and "no temporal form for the linear layout".
@@ -511,7 +488,7 @@ int check_pair_params(const mid_bilateral_params *p, const char *who)
 int bilateral_temporal_check(const mid_bilateral_params *p, const char *who, bool layered, int n_layers, int n_frames, int k)
 {
     if (int rc = check_pair_params(p, who)) return rc;
-    MID_REQUIRE(n_layers >= 0 && n_layers <= 16, "%s: n_layers %d outside 0..16", who, n_layers);
+    MID_REQUIRE(n_layers >= 0 && n_layers <= kMaxLayers, "%s: n_layers %d outside 0..16", who, n_layers);
     MID_REQUIRE(layered || n_layers == 0, "%s: n_layers is %d without a layer table (the plain form takes 0)", who, n_layers);
     MID_REQUIRE(n_frames >= 1 && k >= 0, "%s: bad n_frames=%d k=%d", who, n_frames, k);
     return nlm_layers_temporal_fits(who, n_layers, n_frames, k);
@@ -521,15 +498,10 @@ int bilateral_temporal_out(mid_ctx *ctx, const mid_bilateral_params *p, const vo
                            int n_layers, int n_frames, int k, int first, int count, void *const *out, int out_fmt, hipStream_t s)
 {
     for (int t = first; t < first + count; ++t) {
-        const int lo = t - k < 0 ? 0 : t - k, hi = t + k > n_frames - 1 ? n_frames - 1 : t + k;
         BilPairArgs a{};
         init_args(a, p);
-        a.n_nb = hi - lo + 1; a.n_layers = layers ? n_layers : 0; a.t_slot = t - lo;
+        pack_temporal_window(a, frames, layers, layers ? n_layers : 0, n_frames, k, t);
         a.out = out[t - first]; a.out_fmt = out_fmt;
-        for (int f = lo; f <= hi; ++f) {
-            a.p[(f - lo) * (a.n_layers + 1)] = frames[f];
-            for (int l = 0; l < a.n_layers; ++l) a.p[(f - lo) * (a.n_layers + 1) + 1 + l] = layers[(size_t)f * n_layers + l];
-        }
         const int rc = layers ? dispatch_pair<true, true>(ctx, p->radius, a, s) : dispatch_pair<false, true>(ctx, p->radius, a, s);
         if (rc) return rc;
     }
@@ -585,31 +557,6 @@ extern "C" int mid_bilateral_temporal(mid_ctx *ctx, const mid_bilateral_params *
     MID_REQUIRE(frames && out, "bilateral_temporal: NULL table");
     MID_REQUIRE(fmt_known(out_format), "bilateral_temporal: unknown output format %d", out_format);
     if (int rc = bilateral_temporal_check(p, "bilateral_temporal", layers_rgba8 != nullptr, n_layers, n_frames, k)) return rc;
-    MID_REQUIRE(count >= 1 && first >= 0 && (long)first + count <= n_frames,
-                "bilateral_temporal: bad frame range (n=%d k=%d first=%d count=%d)", n_frames, k, first, count);
-    const int lo = first - k < 0 ? 0 : first - k;
-    const int hi = (long)first + count - 1 + k > n_frames - 1 ? n_frames - 1 : first + count - 1 + k;
-    std::vector<const void *> inputs;
-    try {
-        inputs.reserve((size_t)(hi - lo + 1) * (n_layers + 1));
-    } catch (...) {
-        return set_error(MID_ERR_INVALID, "bilateral_temporal: no host memory for the alias check");
-    }
-    for (int f = lo; f <= hi; ++f) {
-        MID_REQUIRE(frames[f] != nullptr, "bilateral_temporal: frame %d is NULL", f);
-        MID_REQUIRE(fmt_aligned(p->format, frames[f]), "bilateral_temporal: frame %d is not 8-byte aligned (RGBA16F)", f);
-        inputs.push_back(frames[f]);
-        for (int l = 0; l < n_layers; ++l) {
-            MID_REQUIRE(layers_rgba8[(size_t)f * n_layers + l] != nullptr, "bilateral_temporal: layer %d of frame %d is NULL", l, f);
-            inputs.push_back(layers_rgba8[(size_t)f * n_layers + l]);
-        }
-    }
-    for (int t = 0; t < count; ++t) {
-        MID_REQUIRE(out[t] != nullptr, "bilateral_temporal: out %d is NULL", t);
-        MID_REQUIRE(fmt_aligned(out_format, out[t]), "bilateral_temporal: out %d is not 8-byte aligned (RGBA16F)", t);
-    }
-    // every output of the call may be in flight beside launches that still read the window's frames and layers
-    if (int rc = check_no_alias("bilateral_temporal", "a frame or layer of the window", inputs.data(), (int)inputs.size(),
-                                (const void *const *)out, count)) return rc;
+    if (int rc = check_temporal_window("bilateral_temporal", p->format, frames, layers_rgba8, n_layers, n_frames, k, first, count, out, out_format)) return rc;
     return bilateral_temporal_out(ctx, p, frames, layers_rgba8, n_layers, n_frames, k, first, count, out, out_format, b.s);
 }

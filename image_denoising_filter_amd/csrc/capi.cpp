@@ -45,6 +45,35 @@ int check_no_alias(const char *who, const char *input_is, const void *const *in,
     return MID_OK;
 }
 
+int check_temporal_window(const char *who, int fmt, const void *const *frames, const uint32_t *const *layers, int n_layers,
+                          int n_frames, int k, int first, int count, void *const *out, int out_fmt)
+{
+    MID_REQUIRE(count >= 1 && first >= 0 && (long)first + count <= n_frames,
+                "%s: bad frame range (n=%d k=%d first=%d count=%d)", who, n_frames, k, first, count);
+    const int lo = first - k < 0 ? 0 : first - k;
+    const int hi = (long)first + count - 1 + k > n_frames - 1 ? n_frames - 1 : first + count - 1 + k;
+    std::vector<const void *> inputs;
+    try {
+        inputs.reserve((size_t)(hi - lo + 1) * (n_layers + 1));
+    } catch (...) {
+        return set_error(MID_ERR_INVALID, "%s: no host memory for the alias check", who);
+    }
+    for (int f = lo; f <= hi; ++f) {
+        MID_REQUIRE(frames[f] != nullptr, "%s: frame %d is NULL", who, f);
+        MID_REQUIRE(fmt_aligned(fmt, frames[f]), "%s: frame %d is not 8-byte aligned (RGBA16F)", who, f);
+        inputs.push_back(frames[f]);
+        for (int l = 0; l < n_layers; ++l) {
+            MID_REQUIRE(layers[(size_t)f * n_layers + l] != nullptr, "%s: layer %d of frame %d is NULL", who, l, f);
+            inputs.push_back(layers[(size_t)f * n_layers + l]);
+        }
+    }
+    for (int t = 0; t < count; ++t) {
+        MID_REQUIRE(out[t] != nullptr, "%s: out %d is NULL", who, t);
+        MID_REQUIRE(fmt_aligned(out_fmt, out[t]), "%s: out %d is not 8-byte aligned (RGBA16F)", who, t);
+    }
+    return check_no_alias(who, "a frame or layer of the window", inputs.data(), (int)inputs.size(), (const void *const *)out, count);
+}
+
 Bind::Bind(mid_ctx *ctx, void *stream) : rc(MID_OK), s(nullptr)
 {
     if (!ctx) { rc = set_error(MID_ERR_INVALID, "context is NULL"); return; }

@@ -79,6 +79,30 @@ int set_error(int code, const char *fmt, ...);
 // them).  Sorted copies, no hash sets; a failed allocation is an error code too, never an exception through the C-ABI.
 int check_no_alias(const char *who, const char *input_is, const void *const *in, int n_in, const void *const *out, int n_out);
 
+// Guide layers per frame that one call may pass: the "n_layers ... outside 0..16" limit of every layer-guided entry point.
+constexpr int kMaxLayers = 16;
+
+// What mid_nlm_layers_temporal and mid_bilateral_temporal check between their parameters and their launches, `who` being the
+// name in the messages: the output range [first, first + count) inside n_frames, every frame and layer of its window
+// [first - k, first + count - 1 + k] non-NULL (frames aligned for `fmt`), every output non-NULL and aligned for `out_fmt`, and
+// no output among the window's frames and layers (all outputs of the call may be in flight beside launches that still read
+// them).  layers[f * n_layers + l]; n_layers == 0 reads no layer table.  capi.cpp.
+int check_temporal_window(const char *who, int fmt, const void *const *frames, const uint32_t *const *layers, int n_layers,
+                          int n_frames, int k, int first, int count, void *const *out, int out_fmt);
+
+// The window of output frame t in the argument block of a kernel over neighbouring frames (NlmLayerPairArgs, BilPairArgs):
+// slot j holds frame max(0, t - k) + j followed by its n_layers guide layers, t_slot is the output frame's own slot.
+template <typename Args>
+inline void pack_temporal_window(Args &a, const void *const *frames, const uint32_t *const *layers, int n_layers, int n_frames, int k, int t)
+{
+    const int lo = t - k < 0 ? 0 : t - k, hi = t + k > n_frames - 1 ? n_frames - 1 : t + k;
+    a.n_nb = hi - lo + 1; a.n_layers = n_layers; a.t_slot = t - lo;
+    for (int f = lo; f <= hi; ++f) {
+        a.p[(f - lo) * (n_layers + 1)] = frames[f];
+        for (int l = 0; l < n_layers; ++l) a.p[(f - lo) * (n_layers + 1) + 1 + l] = layers[(size_t)f * n_layers + l];
+    }
+}
+
 // Binds the calling thread to the context's device and resolves the stream argument.
 struct Bind {
     int rc;
@@ -243,6 +267,15 @@ __device__ __forceinline__ uint32_t pack_half2(float lo, float hi)
     return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)lo) | ((uint32_t)__builtin_bit_cast(uint16_t, (_Float16)hi) << 16);
 }
 __device__ __forceinline__ uint2 pack_rgba16f(float4 p) { return make_uint2(pack_half2(p.x, p.y), pack_half2(p.z, p.w)); }
+
+// One pixel in the output format of the launch (a kernarg, so wave-uniform): float4, or the rounding of mid_pack_u8 /
+// mid_pack_f16 of the float4 result (the frame pipeline's packed outputs).
+__device__ __forceinline__ void store_out(void *out, size_t idx, int fmt, float4 o)
+{
+    if (fmt == MID_FMT_RGBA8) ((uint32_t *)out)[idx] = pack_rgba8(o);
+    else if (fmt == MID_FMT_RGBA16F) ((uint2 *)out)[idx] = pack_rgba16f(o);
+    else ((float4 *)out)[idx] = o;
+}
 
 // Bytes of one texel of a MID_FMT_* (host side: buffer sizes of the frame pipeline and the sharded exchange).
 inline size_t fmt_bytes(int fmt) { return fmt == MID_FMT_RGBA8 ? 4 : fmt == MID_FMT_RGBA16F ? 8 : 16; }

@@ -26,7 +26,6 @@ namespace mid {
 
 namespace {
 
-constexpr int kMaxLayers = 16;
 constexpr int kLR = 8, kLNW = 8;        // strip kernel: rows per wave, waves per workgroup
 
 struct NlmLayerArgs {

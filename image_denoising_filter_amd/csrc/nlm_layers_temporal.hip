@@ -30,7 +30,6 @@ namespace mid {
 
 namespace {
 
-constexpr int kMaxLayers = 16;
 constexpr int kLR = 8, kLNW = 8;        // strip kernel: rows per wave, waves per workgroup (as nlm_layers.hip)
 constexpr int kMaxPtrs = MID_NLM_LAYERS_TEMPORAL_MAX_POINTERS;
 
@@ -50,8 +49,6 @@ struct NlmLayerPairArgs {
 };
 static_assert(sizeof(NlmLayerPairArgs) <= sizeof(NlmArgs), "no larger than the temporal NLM kernels' argument block");
 
-// (bytes_rgb, guide_at and fill_guide restate nlm_layers.hip's helpers of the same names: that file keeps them in its own
-// unnamed namespace and is left as it is, so that its code objects do not change)
 __device__ __forceinline__ float3 bytes_rgb(uint32_t v)
 {
     return make_float3((float)(v & 0xffu), (float)((v >> 8) & 0xffu), (float)((v >> 16) & 0xffu));
@@ -340,15 +337,10 @@ int nlm_layers_temporal_out(mid_ctx *ctx, const mid_nlm_params *p, const void *c
                             int n_layers, int n_frames, int k, int first, int count, void *const *out, int out_fmt, hipStream_t s)
 {
     for (int t = first; t < first + count; ++t) {
-        const int lo = t - k < 0 ? 0 : t - k, hi = t + k > n_frames - 1 ? n_frames - 1 : t + k;
         NlmLayerPairArgs a{};
         init_args(a, p);
-        a.n_nb = hi - lo + 1; a.n_layers = n_layers; a.t_slot = t - lo;
+        pack_temporal_window(a, frames, layers, n_layers, n_frames, k, t);
         a.out = out[t - first]; a.out_fmt = out_fmt;
-        for (int f = lo; f <= hi; ++f) {
-            a.p[(f - lo) * (n_layers + 1)] = frames[f];
-            for (int l = 0; l < n_layers; ++l) a.p[(f - lo) * (n_layers + 1) + 1 + l] = layers[(size_t)f * n_layers + l];
-        }
         if (int rc = dispatch_pair<true>(ctx, p, a, s)) return rc;
     }
     return MID_OK;
@@ -387,32 +379,9 @@ extern "C" int mid_nlm_layers_temporal(mid_ctx *ctx, const mid_nlm_params *p, co
     MID_REQUIRE(fmt_known(out_format), "nlm_layers_temporal: unknown output format %d", out_format);
     MID_REQUIRE(n_layers >= 0 && n_layers <= kMaxLayers, "nlm_layers_temporal: n_layers %d outside 0..16", n_layers);
     MID_REQUIRE(layers_rgba8 || n_layers == 0, "nlm_layers_temporal: layers is NULL");
-    MID_REQUIRE(n_frames >= 1 && k >= 0 && count >= 1 && first >= 0 && first + count <= n_frames,
+    MID_REQUIRE(n_frames >= 1 && k >= 0,
                 "nlm_layers_temporal: bad frame range (n=%d k=%d first=%d count=%d)", n_frames, k, first, count);
     if (int rc = nlm_layers_temporal_fits("nlm_layers_temporal", n_layers, n_frames, k)) return rc;
-    const int lo = first - k < 0 ? 0 : first - k;
-    const int hi = (long)first + count - 1 + k > n_frames - 1 ? n_frames - 1 : first + count - 1 + k;
-    std::vector<const void *> inputs;
-    try {
-        inputs.reserve((size_t)(hi - lo + 1) * (n_layers + 1));
-    } catch (...) {
-        return set_error(MID_ERR_INVALID, "nlm_layers_temporal: no host memory for the alias check");
-    }
-    for (int f = lo; f <= hi; ++f) {
-        MID_REQUIRE(frames[f] != nullptr, "nlm_layers_temporal: frame %d is NULL", f);
-        MID_REQUIRE(fmt_aligned(p->format, frames[f]), "nlm_layers_temporal: frame %d is not 8-byte aligned (RGBA16F)", f);
-        inputs.push_back(frames[f]);
-        for (int l = 0; l < n_layers; ++l) {
-            MID_REQUIRE(layers_rgba8[(size_t)f * n_layers + l] != nullptr, "nlm_layers_temporal: layer %d of frame %d is NULL", l, f);
-            inputs.push_back(layers_rgba8[(size_t)f * n_layers + l]);
-        }
-    }
-    for (int t = 0; t < count; ++t) {
-        MID_REQUIRE(out[t] != nullptr, "nlm_layers_temporal: out %d is NULL", t);
-        MID_REQUIRE(fmt_aligned(out_format, out[t]), "nlm_layers_temporal: out %d is not 8-byte aligned (RGBA16F)", t);
-    }
-    // every output of the call may be in flight beside launches that still read the window's frames and layers
-    if (int rc = check_no_alias("nlm_layers_temporal", "a frame or layer of the window", inputs.data(), (int)inputs.size(),
-                                (const void *const *)out, count)) return rc;
+    if (int rc = check_temporal_window("nlm_layers_temporal", p->format, frames, layers_rgba8, n_layers, n_frames, k, first, count, out, out_format)) return rc;
     return nlm_layers_temporal_out(ctx, p, frames, layers_rgba8, n_layers, n_frames, k, first, count, out, out_format, b.s);
 }

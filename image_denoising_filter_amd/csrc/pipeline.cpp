@@ -327,7 +327,7 @@ static int run_pipeline(mid_ctx *ctx, const Stage &st, const void *const *host_f
                 if (int rc = nlm_layers_temporal_out(ctx, st.nlm_layers, tbl, lt, n_layers, need - lo + 1, k, b0 - lo, bn,
                                                      (void *const *)o, out_fmt, cs)) return rc;
             } else for (int i = 0; i < bn; ++i) { // (k = 0: output b0 + i reads ring slot b0 + i and its layers only)
-                const uint32_t *lt[16];
+                const uint32_t *lt[kMaxLayers];
                 for (int l = 0; l < n_layers; ++l) lt[l] = (const uint32_t *)layer_slot(b0 + i, l);
                 if (int rc = nlm_layers_out(ctx, st.nlm_layers, slot(b0 + i), lt, n_layers, o[i], out_fmt, cs)) return rc;
             }
@@ -343,7 +343,7 @@ static int run_pipeline(mid_ctx *ctx, const Stage &st, const void *const *host_f
                 if (int rc = bilateral_temporal_out(ctx, st.bil, tbl, st.host_layers ? lt : nullptr, n_layers, need - lo + 1, k, b0 - lo, bn,
                                                     (void *const *)o, out_fmt, cs)) return rc;
             } else for (int i = 0; i < bn; ++i) { // (k = 0: output b0 + i reads ring slot b0 + i and its layers only)
-                const uint32_t *lt[16];
+                const uint32_t *lt[kMaxLayers];
                 for (int l = 0; l < n_layers; ++l) lt[l] = (const uint32_t *)layer_slot(b0 + i, l);
                 if (int rc = bilateral_out(ctx, st.bil, slot(b0 + i), st.host_layers ? lt : nullptr, n_layers, o[i], out_fmt, cs)) return rc;
             }
@@ -436,7 +436,7 @@ extern "C" int mid_sequence_bilateral(mid_ctx *ctx, const mid_bilateral_params *
     MID_REQUIRE(fmt_known(p->format), "sequence_bilateral: unknown format %d", p->format);
     MID_REQUIRE(p->layout == MID_LAYOUT_TEXTURE || p->layout == MID_LAYOUT_LINEAR, "sequence_bilateral: unknown layout %d", p->layout);
     MID_REQUIRE(fmt_known(out_format), "sequence_bilateral: unknown output format %d", out_format);
-    MID_REQUIRE(n_layers >= 0 && n_layers <= 16, "sequence_bilateral: n_layers %d outside 0..16", n_layers);
+    MID_REQUIRE(n_layers >= 0 && n_layers <= kMaxLayers, "sequence_bilateral: n_layers %d outside 0..16", n_layers);
     MID_REQUIRE(!host_layers || p->layout == MID_LAYOUT_TEXTURE, "sequence_bilateral: layers exist for the texture layout only");
     for (int i = 0; i < n_frames; ++i) MID_REQUIRE(host_frames[i], "sequence_bilateral: frame %d is NULL", i);
     const int n_in = host_layers ? n_frames * n_layers : 0;
@@ -468,7 +468,7 @@ extern "C" int mid_sequence_nlm_layers(mid_ctx *ctx, const mid_nlm_params *p, co
     MID_REQUIRE(n_frames >= 1, "sequence_nlm_layers: n_frames %d < 1", n_frames);
     if (int rc = nlm_check_params(p)) return rc;
     MID_REQUIRE(fmt_known(out_format), "sequence_nlm_layers: unknown output format %d", out_format);
-    MID_REQUIRE(n_layers >= 0 && n_layers <= 16, "sequence_nlm_layers: n_layers %d outside 0..16", n_layers);
+    MID_REQUIRE(n_layers >= 0 && n_layers <= kMaxLayers, "sequence_nlm_layers: n_layers %d outside 0..16", n_layers);
     MID_REQUIRE(host_layers || n_layers == 0, "sequence_nlm_layers: host_layers is NULL");
     for (int i = 0; i < n_frames; ++i) MID_REQUIRE(host_frames[i], "sequence_nlm_layers: frame %d is NULL", i);
     const int n_in = host_layers ? n_frames * n_layers : 0;
@@ -503,7 +503,7 @@ extern "C" int mid_sequence_nlm_layers_temporal(mid_ctx *ctx, const mid_nlm_para
                 "sequence_nlm_layers_temporal: bad range first=%d count=%d n_frames=%d", first, count, n_frames);
     if (int rc = nlm_check_params(p)) return rc;
     MID_REQUIRE(fmt_known(out_format), "sequence_nlm_layers_temporal: unknown output format %d", out_format);
-    MID_REQUIRE(n_layers >= 0 && n_layers <= 16, "sequence_nlm_layers_temporal: n_layers %d outside 0..16", n_layers);
+    MID_REQUIRE(n_layers >= 0 && n_layers <= kMaxLayers, "sequence_nlm_layers_temporal: n_layers %d outside 0..16", n_layers);
     MID_REQUIRE(host_layers || n_layers == 0, "sequence_nlm_layers_temporal: host_layers is NULL");
     if (int rc = nlm_layers_temporal_fits("sequence_nlm_layers_temporal", n_layers, n_frames, k)) return rc;
     const int f_lo = first - k < 0 ? 0 : first - k;

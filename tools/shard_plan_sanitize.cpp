@@ -1,7 +1,8 @@
 // shard_plan_sanitize.cpp -- ASan/UBSan sweep of the pure-host sharding entry points of csrc/sharded.cpp (mid_shard_block /
 // mid_shard_halo_plan / mid_shard_launch_plan): every (n <= 70, world <= 9, k <= 6, rank), caller arrays of capacity 0, 1, 3 and
 // 64 (too-small capacities must come back as error codes, never as writes past the arrays), bad arguments; and the alias check
-// the launch entry points share (mid::check_no_alias).  CPU build only; the kernel entry points the host files reference are
+// the launch entry points share (mid::check_no_alias), and the window check of the entry points over neighbouring frames
+// (mid::check_temporal_window) on hostile tables: NULL entries, first + count past INT_MAX, misaligned RGBA16F.  CPU build only; the kernel entry points the host files reference are
 // stubbed (never reached).  Built and run by tests/test_shard_native_plan.py:
 //   hipcc -x hip --offload-arch=gfx950 -fno-gpu-sanitize -fsanitize=address,undefined -O1 -g -std=c++17 -Iinclude \
 //         csrc/sharded.cpp csrc/capi.cpp csrc/pipeline.cpp tools/shard_plan_sanitize.cpp -o shard_plan_sanitize -ldl
@@ -59,6 +60,48 @@ int main()
         bad += ac.want ? rc != MID_ERR_INVALID || strncmp(mid_last_error(), ac.want, strlen(ac.want)) != 0 : rc != MID_OK;
     }
     bad += mid::check_no_alias("t", "an input", nullptr, 0, nullptr, 0) != MID_OK;
+    // the window check of mid_nlm_layers_temporal / mid_bilateral_temporal (capi.cpp).  Tables of EXACTLY n frames, n * L layers
+    // and `count` outputs on the heap: a read outside the window's part of them is a heap overflow ASan reports.
+    {
+        alignas(8) static char mem[256];
+        const int n = 4, L = 2;
+        struct Case { int fmt, n_layers, k, first, count, out_fmt; int null_frame, null_layer, odd_frame, null_out, odd_out, alias_out; const char *want; };
+        const int I = 0x7fffffff, F32 = MID_FMT_RGBA32F, F16 = MID_FMT_RGBA16F;
+        const Case window_cases[] = {
+            {F32, L, 1, 1, 2, F32, -1, -1, -1, -1, -1, -1, nullptr},
+            {F32, 0, 1, 1, 2, F32, -1, -1, -1, -1, -1, -1, nullptr},                       // no layer table at all
+            {F32, L, I, 0, 4, F32, -1, -1, -1, -1, -1, -1, nullptr},                       // k far beyond the sequence: the window is clamped
+            {F32, L, 1, 2, 1, F32, 0, 1, -1, -1, -1, -1, nullptr},                         // NULL entries OUTSIDE the window [1, 3] are not its business
+            {F32, L, 1, I, 1, F32, -1, -1, -1, -1, -1, -1, "w: bad frame range (n=4 k=1 first=2147483647 count=1)"},
+            {F32, L, 1, 1, I, F32, -1, -1, -1, -1, -1, -1, "w: bad frame range (n=4 k=1 first=1 count=2147483647)"},
+            {F32, L, 1, 3, 2, F32, -1, -1, -1, -1, -1, -1, "w: bad frame range"},
+            {F32, L, 1, -1, 2, F32, -1, -1, -1, -1, -1, -1, "w: bad frame range"},
+            {F32, L, 1, 0, 0, F32, -1, -1, -1, -1, -1, -1, "w: bad frame range"},
+            {F32, L, 1, 1, 2, F32, 3, -1, -1, -1, -1, -1, "w: frame 3 is NULL"},
+            {F32, L, 1, 1, 2, F32, -1, 1, -1, -1, -1, -1, "w: layer 1 of frame 0 is NULL"},
+            {F16, L, 1, 1, 2, F32, -1, -1, 2, -1, -1, -1, "w: frame 2 is not 8-byte aligned (RGBA16F)"},
+            {F32, L, 1, 1, 2, F32, -1, -1, 2, -1, -1, -1, nullptr},                        // (alignment matters for RGBA16F only)
+            {F32, L, 1, 1, 2, F32, -1, -1, -1, 1, -1, -1, "w: out 1 is NULL"},
+            {F32, L, 1, 1, 2, F16, -1, -1, -1, -1, 0, -1, "w: out 0 is not 8-byte aligned (RGBA16F)"},
+            {F32, L, 1, 1, 2, F32, -1, -1, -1, -1, -1, 1, "w: out[1] is also a frame or layer of the window"},
+        };
+        for (const Case &c : window_cases) {
+            std::vector<const void *> frames(n);
+            std::vector<const uint32_t *> layers((size_t)n * c.n_layers);
+            std::vector<void *> out(c.count > 0 && c.count < 16 ? c.count : 1);
+            for (int f = 0; f < n; ++f) frames[f] = mem + 16 * f + (f == c.odd_frame ? 4 : 0);
+            for (size_t i = 0; i < layers.size(); ++i) layers[i] = (const uint32_t *)(mem + 64 + 8 * i);
+            for (size_t t = 0; t < out.size(); ++t) out[t] = mem + 160 + 16 * t + ((int)t == c.odd_out ? 4 : 0);
+            if (c.null_frame >= 0) frames[c.null_frame] = nullptr;
+            if (c.null_layer >= 0 && !layers.empty()) layers[c.null_layer] = nullptr;
+            if (c.null_out >= 0) out[c.null_out] = nullptr;
+            if (c.alias_out >= 0) out[c.alias_out] = (void *)layers[(size_t)2 * c.n_layers];
+            const int rc = mid::check_temporal_window("w", c.fmt, frames.data(), c.n_layers ? layers.data() : nullptr, c.n_layers, n, c.k,
+                                                      c.first, c.count, out.data(), c.out_fmt);
+            bad += c.want ? rc != MID_ERR_INVALID || strncmp(mid_last_error(), c.want, strlen(c.want)) != 0 : rc != MID_OK;
+            ++calls;
+        }
+    }
     printf("shard_plan_sanitize: %ld calls, %ld refused for capacity, %ld wrong\n", calls, refused, bad);
     return bad ? 1 : 0;
 }
