@@ -18,6 +18,11 @@ import numpy as np
 from ._lib import BilateralParams, Image, NlmParams, NormalizeParams, c_void_pp, lib
 
 FMT_RGBA32F, FMT_RGBA8, FMT_RGBA16F = 0, 1, 2
+
+
+def fmt_with_guide(fmt, guide_fmt):
+    """MID_FMT_WITH_GUIDE: the format word of a bilateral call whose guide layers are not RGBA8."""
+    return fmt | ((guide_fmt + 1) << 8)
 LAYOUT_TEXTURE, LAYOUT_LINEAR = 0, 1
 
 # nonlocal.comp:5-6 as shipped, and the 21x21 / 7x7 benchmark configuration (half-open ranges)
@@ -97,6 +102,23 @@ def _fmt_of(a):
     if a.dtype == np.float16:
         return FMT_RGBA16F
     raise TypeError(f"image dtype must be float32, uint8 or float16, got {a.dtype}")
+
+
+_GUIDE_DTYPES = (np.uint8, np.float16, np.float32)
+
+
+def _guide_fmt(fmt, layers, who):
+    """The format word of a bilateral call with guide layers: the frames' FMT_* with the guide field set from the layers' dtype
+    (uint8 leaves it 0: RGBA8, as always).  All layers of a call share one dtype."""
+    dts = {np.dtype(l.dtype) for l in layers}
+    if len(dts) > 1:
+        raise ValueError(f"{who}: all guide layers of a call share one dtype, got {sorted(str(d) for d in dts)}")
+    if not dts or dts == {np.dtype(np.uint8)}:
+        return fmt
+    (dt,) = dts
+    if dt not in (np.dtype(np.float16), np.dtype(np.float32)):
+        raise TypeError(f"{who}: guide layers must be uint8, float16 or float32, got {dt}")
+    return fmt_with_guide(fmt, _fmt_of(layers[0]))
 
 
 def _img(a):
@@ -239,26 +261,28 @@ class Context:
         return [self.download(d, (h, w, 4), np.float32) for d in d_out]
 
     def bilateral_layers_accum(self, img, layer, W, radius, sigma_s=2.0, sigma_c=0.2):
-        """One dispatch of bialteral_layers.comp: returns W + this layer's sums."""
+        """One dispatch of bialteral_layers.comp: returns W + this layer's sums.  layer: uint8, float16 or float32 (h, w, 4)."""
         img, layer = _img(img), _img(layer)
-        if layer.dtype != np.uint8:
-            raise TypeError("layers are always RGBA8 (src/main.cpp:1396)")
+        fmt = _guide_fmt(_fmt_of(img), [layer], "bilateral_layers_accum")
         h, w = img.shape[:2]
         W = np.ascontiguousarray(W, dtype=np.float32)
         d_in, d_l, d_w = self.upload(img), self.upload(layer), self.upload(W)
-        p = BilateralParams(w, h, sigma_s, sigma_c, radius, LAYOUT_TEXTURE, _fmt_of(img))
+        p = BilateralParams(w, h, sigma_s, sigma_c, radius, LAYOUT_TEXTURE, fmt)
         _check(lib.mid_bilateral_layers_accum(self.handle, ctypes.byref(p), d_in.ptr, d_l.ptr, d_w.ptr, None),
                "mid_bilateral_layers_accum")
         return self.download(d_w, (h, w, 8), np.float32)
 
     def bilateral_layers(self, img, layers, radius, sigma_s=2.0, sigma_c=0.2):
-        """The per-layer loop + normalize, fused (src/main.cpp:1610-1623,1649-1652)."""
+        """The per-layer loop + normalize, fused (src/main.cpp:1610-1623,1649-1652).  layers: uint8, float16 or float32
+        (h, w, 4) guides, all of one dtype."""
         img = _img(img)
         h, w = img.shape[:2]
+        layers = [_img(l) for l in layers]
+        fmt = _guide_fmt(_fmt_of(img), layers, "bilateral_layers")
         d_in, d_out = self.upload(img), self.alloc(w * h * 16)
-        d_layers = [self.upload(_img(l)) for l in layers]
+        d_layers = [self.upload(l) for l in layers]
         tbl = (ctypes.c_void_p * max(len(d_layers), 1))(*[d.ptr for d in d_layers])
-        p = BilateralParams(w, h, sigma_s, sigma_c, radius, LAYOUT_TEXTURE, _fmt_of(img))
+        p = BilateralParams(w, h, sigma_s, sigma_c, radius, LAYOUT_TEXTURE, fmt)
         _check(lib.mid_bilateral_layers(self.handle, ctypes.byref(p), d_in.ptr, tbl, len(d_layers), d_out.ptr, None),
                "mid_bilateral_layers")
         return self.download(d_out, (h, w, 4), np.float32)
@@ -362,37 +386,36 @@ class Context:
         return self.download(d_w, (h, w, 8), np.float32)
 
     def bilateral_layers_pair_accum(self, target_layer, neighbour_layer, neighbour, W, radius, sigma_s=2.0, sigma_c=0.2):
-        """One layered pair dispatch: the range weight between two uint8 guides -- the target frame's layer at the centre, the
+        """One layered pair dispatch: the range weight between two guides of one dtype (uint8, float16 or float32) -- the target frame's layer at the centre, the
         neighbour frame's layer under the taps -- and the colour from the `neighbour` frame: returns W + its sums
         (mid_bilateral_layers_pair_accum)."""
         neighbour, target_layer, neighbour_layer = _img(neighbour), _img(target_layer), _img(neighbour_layer)
-        if target_layer.dtype != np.uint8 or neighbour_layer.dtype != np.uint8:
-            raise TypeError("layers are always RGBA8 (src/main.cpp:1396)")
+        fmt = _guide_fmt(_fmt_of(neighbour), [target_layer, neighbour_layer], "bilateral_layers_pair_accum")
         h, w = neighbour.shape[:2]
         W = np.ascontiguousarray(W, dtype=np.float32)
         d_in, d_n, d_w = self.upload(neighbour), self.upload(neighbour_layer), self.upload(W)
         d_t = d_n if target_layer is neighbour_layer else self.upload(target_layer)
-        p = BilateralParams(w, h, sigma_s, sigma_c, radius, LAYOUT_TEXTURE, _fmt_of(neighbour))
+        p = BilateralParams(w, h, sigma_s, sigma_c, radius, LAYOUT_TEXTURE, fmt)
         _check(lib.mid_bilateral_layers_pair_accum(self.handle, ctypes.byref(p), d_t.ptr, d_n.ptr, d_in.ptr, d_w.ptr, None),
                "mid_bilateral_layers_pair_accum")
         return self.download(d_w, (h, w, 8), np.float32)
 
     def bilateral_temporal(self, frames, k=0, first=0, count=None, radius=8, sigma_s=2.0, sigma_c=0.2, layers=None, out_dtype=None):
         """The bilateral over the frames t-k..t+k for `count` output frames, fused (mid_bilateral_temporal).
-        layers: None (plain form: the frames guide themselves), or one list per frame of equally many uint8 (h, w, 4) guide
-        layers; out_dtype: None = float32, uint8 or float16."""
+        layers: None (plain form: the frames guide themselves), or one list per frame of equally many (h, w, 4) guide
+        layers, uint8, float16 or float32 and all of one dtype; out_dtype: None = float32, uint8 or float16."""
         frames = _same_frames(frames, "bilateral_temporal")
         n = len(frames)
         count = n - first if count is None else count
         h, w = frames[0].shape[:2]
-        n_layers, flat = (0, None) if layers is None else _flat_layers(layers, n, h, w, "bilateral_temporal")
+        n_layers, flat = (0, None) if layers is None else _flat_layers(layers, n, h, w, "bilateral_temporal", _GUIDE_DTYPES)
         out_dtype = _out_dtype(False, out_dtype)
         out_fmt = {np.dtype(np.uint8): FMT_RGBA8, np.dtype(np.float16): FMT_RGBA16F, np.dtype(np.float32): FMT_RGBA32F}[out_dtype]
         d_fr = [self.upload(f) for f in frames]
         d_l = None if flat is None else [self.upload(l) for l in flat]
         d_out = [self.alloc(w * h * 4 * out_dtype.itemsize) for _ in range(max(count, 0))]
         tl = None if d_l is None else (ctypes.c_void_p * max(len(d_l), 1))(*[d.ptr for d in d_l])
-        p = BilateralParams(w, h, sigma_s, sigma_c, radius, LAYOUT_TEXTURE, _fmt_of(frames[0]))
+        p = BilateralParams(w, h, sigma_s, sigma_c, radius, LAYOUT_TEXTURE, _guide_fmt(_fmt_of(frames[0]), flat or [], "bilateral_temporal"))
         _check(lib.mid_bilateral_temporal(self.handle, ctypes.byref(p), (ctypes.c_void_p * n)(*[d.ptr for d in d_fr]), tl, n_layers, n,
                                           k, first, count, (ctypes.c_void_p * max(len(d_out), 1))(*[d.ptr for d in d_out]), out_fmt, None),
                "mid_bilateral_temporal")
@@ -513,7 +536,8 @@ class Context:
     def sequence_bilateral_pinned(self, hin, hout, w, h, fmt, radius, sigma_s=2.0, sigma_c=0.2, layout="texture", hlayers=None,
                                   n_layers=0, overlap=True, out_dtype=None):
         """mid_sequence_bilateral on host pointers the caller already holds: nothing but the C call, so a clock around it
-        measures what a C caller sees.  hlayers: None (plain bilateral) or len(hin) * n_layers RGBA8 host pointers, frame-major.
+        measures what a C caller sees.  hlayers: None (plain bilateral) or len(hin) * n_layers host pointers, frame-major: RGBA8
+        layers, or what fmt_with_guide(frames' format, layers' format) names in `fmt`.
         Returns (wall_ms of the whole call, kernel_ms, copy_ms)."""
         n = len(hin)
         if len(hout) < n:
@@ -538,26 +562,14 @@ class Context:
         """A whole animation through the overlapped pipeline with the bilateral as its compute stage (mid_sequence_bilateral):
         output i is ctx.bilateral(frames[i]) -- or, with `layers`, ctx.bilateral_layers(frames[i], layers[i]) -- packed to
         out_dtype (None = float32; uint8 = the reference's read-back conversion, float16 = round to nearest even) by the kernel.
-        layers: None, or one list per frame of equally many uint8 (h, w, 4) guide layers (texture layout only).
+        layers: None, or one list per frame of equally many (h, w, 4) guide layers, uint8, float16 or float32 and all of one
+        dtype (texture layout only).
         pinned / pinned_out = False: the NumPy arrays themselves (pageable memory) are the sources / destinations.
         Returns (outputs, (wall_ms, kernel_ms, copy_ms))."""
         frames = _same_frames(frames, "sequence_bilateral")
         n = len(frames)
         h, w = frames[0].shape[:2]
-        n_layers, flat = 0, None
-        if layers is not None:
-            if len(layers) != n:
-                raise ValueError(f"sequence_bilateral: {len(layers)} layer lists for {n} frames")
-            n_layers = len(layers[0])
-            flat = []
-            for i, ls in enumerate(layers):
-                if len(ls) != n_layers:
-                    raise ValueError(f"sequence_bilateral: frame {i} has {len(ls)} layers, frame 0 has {n_layers}")
-                for lyr in ls:
-                    lyr = _img(lyr)
-                    if lyr.dtype != np.uint8 or lyr.shape != (h, w, 4):
-                        raise ValueError(f"sequence_bilateral: the layers of frame {i} must be uint8 {(h, w, 4)}, got {lyr.dtype} {lyr.shape}")
-                    flat.append(lyr)
+        n_layers, flat = (0, None) if layers is None else _flat_layers(layers, n, h, w, "sequence_bilateral", _GUIDE_DTYPES)
         out_shape, out_dtype = (h, w, 4), _out_dtype(False, out_dtype)
         hin = hlay = hout = None
         try:
@@ -568,8 +580,8 @@ class Context:
             lptr = None if flat is None else (hlay.ptrs if hlay is not None else [lyr.ctypes.data for lyr in flat])
             t = self.sequence_bilateral_pinned(hin.ptrs if pinned else [f.ctypes.data for f in frames],
                                                hout.ptrs if pinned_out else [o.ctypes.data for o in outs], w, h,
-                                               _fmt_of(frames[0]), radius, sigma_s, sigma_c, layout, lptr, n_layers,
-                                               overlap, out_dtype)
+                                               _guide_fmt(_fmt_of(frames[0]), flat or [], "sequence_bilateral"), radius, sigma_s, sigma_c,
+                                               layout, lptr, n_layers, overlap, out_dtype)
             return (outs if outs is not None else [hout.array(i, out_shape, out_dtype) for i in range(n)]), t
         finally:
             for b in (hin, hlay, hout):
@@ -679,8 +691,8 @@ class Context:
     def sequence_bilateral_temporal_pinned(self, hin, hout, w, h, fmt, k, first=0, count=None, radius=8, sigma_s=2.0, sigma_c=0.2,
                                            hlayers=None, n_layers=0, overlap=True, out_dtype=None):
         """mid_sequence_bilateral_temporal on host pointers the caller already holds: nothing but the C call.  hin: all n frames
-        of the sequence (only those of [first-k, first+count+k) are read); hlayers: None (plain form) or n * n_layers RGBA8 host
-        pointers, frame-major; hout: `count` output buffers.  Returns (wall_ms of the whole call, kernel_ms, copy_ms)."""
+        of the sequence (only those of [first-k, first+count+k) are read); hlayers: None (plain form) or n * n_layers host
+        pointers, frame-major (RGBA8, or what fmt_with_guide names in `fmt`); hout: `count` output buffers.  Returns (wall_ms of the whole call, kernel_ms, copy_ms)."""
         n = len(hin)
         count = n - first if count is None else count
         if len(hout) < count:
@@ -710,7 +722,7 @@ class Context:
         n = len(frames)
         count = n - first if count is None else count
         h, w = frames[0].shape[:2]
-        n_layers, flat = (0, None) if layers is None else _flat_layers(layers, n, h, w, "sequence_bilateral_temporal")
+        n_layers, flat = (0, None) if layers is None else _flat_layers(layers, n, h, w, "sequence_bilateral_temporal", _GUIDE_DTYPES)
         out_shape, out_dtype = (h, w, 4), _out_dtype(False, out_dtype)
         hin = hlay = hout = None
         try:
@@ -721,8 +733,8 @@ class Context:
             lptr = None if flat is None else (hlay.ptrs if hlay is not None else [lyr.ctypes.data for lyr in flat])
             t = self.sequence_bilateral_temporal_pinned(hin.ptrs if pinned else [f.ctypes.data for f in frames],
                                                         hout.ptrs if pinned_out else [o.ctypes.data for o in outs], w, h,
-                                                        _fmt_of(frames[0]), k, first, count, radius, sigma_s, sigma_c, lptr, n_layers,
-                                                        overlap, out_dtype)
+                                                        _guide_fmt(_fmt_of(frames[0]), flat or [], "sequence_bilateral_temporal"), k, first,
+                                                        count, radius, sigma_s, sigma_c, lptr, n_layers, overlap, out_dtype)
             return (outs if outs is not None else [hout.array(i, out_shape, out_dtype) for i in range(count)]), t
         finally:
             for b in (hin, hlay, hout):
@@ -731,8 +743,10 @@ class Context:
 
 
 
-def _flat_layers(layers, n, h, w, who):
-    """(layers per frame, the frames' uint8 (h, w, 4) guide layers as one frame-major list) of one list of layers per frame."""
+def _flat_layers(layers, n, h, w, who, dtypes=(np.uint8,)):
+    """(layers per frame, the frames' (h, w, 4) guide layers as one frame-major list) of one list of layers per frame.  dtypes: what
+    the filter takes -- uint8 alone (layer-guided NLM), or uint8 / float16 / float32 (the bilateral family); all layers of a call
+    share one of them."""
     if len(layers) != n:
         raise ValueError(f"{who}: {len(layers)} layer lists for {n} frames")
     n_layers = len(layers[0])
@@ -742,8 +756,12 @@ def _flat_layers(layers, n, h, w, who):
             raise ValueError(f"{who}: frame {i} has {len(ls)} layers, frame 0 has {n_layers}")
         for lyr in ls:
             lyr = _img(lyr)
-            if lyr.dtype != np.uint8 or lyr.shape != (h, w, 4):
-                raise ValueError(f"{who}: the layers of frame {i} must be uint8 {(h, w, 4)}, got {lyr.dtype} {lyr.shape}")
+            if lyr.dtype not in [np.dtype(d) for d in dtypes] or lyr.shape != (h, w, 4):
+                raise ValueError(f"{who}: the layers of frame {i} must be {' / '.join(np.dtype(d).name for d in dtypes)} {(h, w, 4)}, "
+                                 f"got {lyr.dtype} {lyr.shape}")
+            if flat and lyr.dtype != flat[0].dtype:
+                raise ValueError(f"{who}: all guide layers of a call share one dtype: layer 0 of frame 0 is {flat[0].dtype}, "
+                                 f"a layer of frame {i} is {lyr.dtype}")
             flat.append(lyr)
     return n_layers, flat
 

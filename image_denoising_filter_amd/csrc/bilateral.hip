@@ -492,21 +492,27 @@ static int dispatch_radius(mid_ctx *ctx, int radius, BilArgs &a, hipStream_t s, 
         });
 }
 
-static int check_params(const mid_bilateral_params *p, const char *who)
+static int check_params(const mid_bilateral_params *p, const char *who, bool guide_ok = false)
 {
     MID_REQUIRE(p != nullptr, "%s: params is NULL", who);
     MID_REQUIRE(p->width > 0 && p->height > 0, "%s: bad size %dx%d", who, p->width, p->height);
     MID_REQUIRE((long)p->width * p->height < (1l << 30), "%s: image too large", who);
     MID_REQUIRE(p->spatialSigma > 0.f && p->colorSigma > 0.f, "%s: sigmas must be > 0", who);
     MID_REQUIRE(p->radius >= 1 && p->radius <= 24, "%s: radius %d outside 1..24", who, p->radius);
-    MID_REQUIRE(fmt_known(p->format), "%s: unknown format %d", who, p->format);
+    // the format word: the frames' format in bits 0..7, the guide layers' in bits 8..15 (MID_FMT_WITH_GUIDE), nothing above
+    MID_REQUIRE((p->format & ~0xffff) == 0 && fmt_known(fmt_frames(p->format)), "%s: unknown format %d", who, p->format);
+    if ((p->format >> 8) != 0) {
+        MID_REQUIRE(guide_ok, "%s: format 0x%x names a guide-layer format, and this call reads no guide layers of the bilateral family", who, p->format);
+        MID_REQUIRE(fmt_guide(p->format) >= 0, "%s: unknown guide-layer format code %d in format 0x%x", who, p->format >> 8, p->format);
+    }
     MID_REQUIRE(p->layout == MID_LAYOUT_TEXTURE || p->layout == MID_LAYOUT_LINEAR, "%s: unknown layout %d", who, p->layout);
     return MID_OK;
 }
 
-int bilateral_check_params(const mid_bilateral_params *p, const char *who) { return check_params(p, who); }
+int bilateral_check_params(const mid_bilateral_params *p, const char *who, bool guide_ok) { return check_params(p, who, guide_ok); }
 
-// The input's texel format as a template argument: one switch for every entry point (the guide layers are always RGBA8).
+// The input's texel format as a template argument: one switch for every entry point (the guide layers of these kernels are
+// always RGBA8: RGBA16F / RGBA32F guides run on bilateral_temporal.hip's kernels, see bilateral_out).
 template <bool LINEAR, int MODE, typename BT = BilOne>
 static int dispatch_format(mid_ctx *ctx, int format, int radius, BilArgs &a, hipStream_t s, const BT &bt = BT{}, int n_frames = 1)
 {
@@ -521,13 +527,15 @@ int bilateral_out(mid_ctx *ctx, const mid_bilateral_params *p, const void *in, c
     BilArgs a{};
     bil_fill_scales(p, a);
     a.in = in; a.out = out; a.out_fmt = out_fmt;
+    if (layers && fmt_guide(p->format) != MID_FMT_RGBA8)     // the k = 0 window of one frame: the identity DESIGN 3.7 pins bit for bit
+        return bilateral_temporal_out(ctx, p, &in, layers, n_layers, 1, 0, 0, 1, &out, out_fmt, s);
     if (!layers) {
         if (p->layout == MID_LAYOUT_LINEAR) return dispatch_format<true, 0>(ctx, p->format, p->radius, a, s);
         return dispatch_format<false, 0>(ctx, p->format, p->radius, a, s);
     }
     a.n_layers = n_layers;
     for (int i = 0; i < n_layers; ++i) a.layers[i] = layers[i];
-    return dispatch_format<false, 2>(ctx, p->format, p->radius, a, s);
+    return dispatch_format<false, 2>(ctx, fmt_frames(p->format), p->radius, a, s);
 }
 
 }  // namespace mid
@@ -551,15 +559,18 @@ extern "C" int mid_bilateral_layers_accum(mid_ctx *ctx, const mid_bilateral_para
 {
     Bind b(ctx, stream);
     if (b.rc) return b.rc;
-    if (int rc = check_params(p, "bilateral_layers_accum")) return rc;
+    if (int rc = check_params(p, "bilateral_layers_accum", true)) return rc;
     MID_REQUIRE(in && layer && W, "bilateral_layers_accum: NULL pointer");
-    MID_REQUIRE(fmt_aligned(p->format, in), "bilateral_layers_accum: RGBA16F input must be 8-byte aligned");
+    MID_REQUIRE(fmt_aligned(fmt_frames(p->format), in), "bilateral_layers_accum: RGBA16F input must be 8-byte aligned");
+    MID_REQUIRE(guide_aligned(fmt_guide(p->format), layer), "bilateral_layers_accum: an RGBA16F guide layer must be 8-byte aligned, an RGBA32F one 16-byte aligned");
     // NLM/layers are only ever bound to textures in the reference (src/main.cpp:1406-1428).
     MID_REQUIRE(p->layout == MID_LAYOUT_TEXTURE, "bilateral_layers_accum: layers exist for the texture layout only");
+    if (fmt_guide(p->format) != MID_FMT_RGBA8)              // the pair dispatch with target guide == neighbour guide: the same bits
+        return bilateral_layers_pair_out(ctx, p, layer, layer, in, W, b.s);
     BilArgs a{};
     bil_fill_scales(p, a);
     a.in = in; a.W = W; a.n_layers = 1; a.layers[0] = layer;
-    return dispatch_format<false, 1>(ctx, p->format, p->radius, a, b.s);
+    return dispatch_format<false, 1>(ctx, fmt_frames(p->format), p->radius, a, b.s);
 }
 
 extern "C" int mid_bilateral_layers(mid_ctx *ctx, const mid_bilateral_params *p, const void *in,
@@ -567,13 +578,15 @@ extern "C" int mid_bilateral_layers(mid_ctx *ctx, const mid_bilateral_params *p,
 {
     Bind b(ctx, stream);
     if (b.rc) return b.rc;
-    if (int rc = check_params(p, "bilateral_layers")) return rc;
+    if (int rc = check_params(p, "bilateral_layers", true)) return rc;
     MID_REQUIRE(in && layers && out, "bilateral_layers: NULL pointer");
-    MID_REQUIRE(fmt_aligned(p->format, in), "bilateral_layers: RGBA16F input must be 8-byte aligned");
+    MID_REQUIRE(fmt_aligned(fmt_frames(p->format), in), "bilateral_layers: RGBA16F input must be 8-byte aligned");
     MID_REQUIRE((const void *)out != in, "bilateral_layers: out is the input image (in-place filtering is not supported)");
     MID_REQUIRE(p->layout == MID_LAYOUT_TEXTURE, "bilateral_layers: layers exist for the texture layout only");
     MID_REQUIRE(n_layers >= 0 && n_layers <= kMaxLayers, "bilateral_layers: n_layers %d outside 0..16", n_layers);
     for (int i = 0; i < n_layers; ++i) MID_REQUIRE(layers[i] != nullptr, "bilateral_layers: layer %d is NULL", i);
+    for (int i = 0; i < n_layers; ++i)
+        MID_REQUIRE(guide_aligned(fmt_guide(p->format), layers[i]), "bilateral_layers: layer %d is not aligned for its format (RGBA16F: 8 bytes, RGBA32F: 16)", i);
     return bilateral_out(ctx, p, in, layers, n_layers, out, MID_FMT_RGBA32F, b.s);
 }
 

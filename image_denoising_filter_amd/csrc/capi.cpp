@@ -46,7 +46,7 @@ int check_no_alias(const char *who, const char *input_is, const void *const *in,
 }
 
 int check_temporal_window(const char *who, int fmt, const void *const *frames, const uint32_t *const *layers, int n_layers,
-                          int n_frames, int k, int first, int count, void *const *out, int out_fmt)
+                          int n_frames, int k, int first, int count, void *const *out, int out_fmt, int guide_fmt)
 {
     MID_REQUIRE(count >= 1 && first >= 0 && (long)first + count <= n_frames,
                 "%s: bad frame range (n=%d k=%d first=%d count=%d)", who, n_frames, k, first, count);
@@ -64,6 +64,8 @@ int check_temporal_window(const char *who, int fmt, const void *const *frames, c
         inputs.push_back(frames[f]);
         for (int l = 0; l < n_layers; ++l) {
             MID_REQUIRE(layers[(size_t)f * n_layers + l] != nullptr, "%s: layer %d of frame %d is NULL", who, l, f);
+            MID_REQUIRE(guide_aligned(guide_fmt, layers[(size_t)f * n_layers + l]), "%s: layer %d of frame %d is not %d-byte aligned (%s guide)",
+                        who, l, f, guide_fmt == MID_FMT_RGBA16F ? 8 : 16, guide_fmt == MID_FMT_RGBA16F ? "RGBA16F" : "RGBA32F");
             inputs.push_back(layers[(size_t)f * n_layers + l]);
         }
     }

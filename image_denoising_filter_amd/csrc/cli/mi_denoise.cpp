@@ -155,8 +155,11 @@ class DenoiseApplication {
     // half: an .exr as RGBA16F (--half): HALF channels bit for bit, FLOAT ones rounded to nearest even
     static HostImage load(const std::string &path, bool force_png, mid_ctx *ctx = nullptr, bool half = false)
     {
-        // layers are always decoded as PNG (src/main.cpp:1396 passes a_isHDR=false)
-        if (force_png && is_hdr(path)) throw std::runtime_error("layer " + path + " is not a PNG");
+        // The reference decodes layers as PNG (src/main.cpp:1396 passes a_isHDR=false).  The bilateral modes also take .exr layers
+        // (RGBA32F, or RGBA16F with --half: MID_FMT_WITH_GUIDE); layer-guided NLM keeps the rule, force_png
+        if (force_png && is_hdr(path))
+            throw std::runtime_error("layer " + path + " is not a PNG: layer-guided NLM takes RGBA8 guide layers only (its patch distances "
+                                     "are exact integer sums of byte values); .exr layers guide the bilateral modes");
         HostImage h;
         if (half) {
             if (ctx && mid_image_load_f16(ctx, path.c_str(), &h.img) == MID_OK) h.pin_ctx = ctx;
@@ -166,6 +169,18 @@ class DenoiseApplication {
             throw std::runtime_error(mid_last_error());        // lodepng error -> runtime_error, src/main.cpp:202
         h.w = h.img.width; h.h = h.img.height; h.format = h.img.format;
         return h;
+    }
+
+    // All guide layers of a run share one format, decided by the first file: .png = RGBA8, .exr = RGBA32F, or RGBA16F with --half.
+    // Refuses the run, naming the first file that differs, before anything is decoded.
+    int layer_format(const std::vector<std::string> &names) const
+    {
+        auto fmt_of = [&](const std::string &f) { return !is_hdr(f) ? MID_FMT_RGBA8 : opt.half ? MID_FMT_RGBA16F : MID_FMT_RGBA32F; };
+        for (const std::string &f : names)
+            if (fmt_of(f) != fmt_of(names[0]))
+                throw std::runtime_error("layer " + f + " is " + (is_hdr(f) ? "an .exr" : "a .png") + " but " + names[0] + " is " +
+                                         (is_hdr(names[0]) ? "an .exr" : "a .png") + ": all guide layers of a run must have one format");
+        return names.empty() ? MID_FMT_RGBA8 : fmt_of(names[0]);
     }
 
     std::string out_path(const std::string &name) const { return (fs::path(opt.outdir) / name).string(); }
@@ -331,8 +346,11 @@ public:
             } else if (useLayers) {                                                             // :1608-1623 + normalize
                 std::vector<void *> dLayers;
                 std::vector<HostImage> layerImgs(layerNames.size());
+                if (nlmFilter) for (const std::string &ln : layerNames) if (is_hdr(ln)) (void)load(ln, true);       // refuses, saying why
+                const int lfmt = layer_format(layerNames);
                 for_each_file(0, (int)layerNames.size(), [&](int i) {
-                    layerImgs[i] = load(layerNames[i], true, pin);
+                    layerImgs[i] = load(layerNames[i], nlmFilter, pin, lfmt == MID_FMT_RGBA16F);
+                    if (layerImgs[i].format != lfmt) throw std::runtime_error(layerNames[i] + ": the decoded layer is not in the run's guide format");
                 });
                 for (size_t li = 0; li < layerNames.size(); ++li) {
                     const std::string &ln = layerNames[li];
@@ -351,7 +369,8 @@ public:
                         MID_CHECK(mid_nlm_layers(ctx, &p, dIn, (const uint32_t *const *)dLayers.data(), (int)dLayers.size(), (mid_pixel *)dOut, nullptr));
                     });
                 } else {
-                    mid_bilateral_params p{w, h, opt.sigma_s, opt.sigma_c, opt.radius, MID_LAYOUT_TEXTURE, fmt};
+                    mid_bilateral_params p{w, h, opt.sigma_s, opt.sigma_c, opt.radius, MID_LAYOUT_TEXTURE,
+                                           lfmt == MID_FMT_RGBA8 ? fmt : MID_FMT_WITH_GUIDE(fmt, lfmt)};
                     timed(m_execMs, [&] {
                         MID_CHECK(mid_bilateral_layers(ctx, &p, dIn, (const uint32_t *const *)dLayers.data(), (int)dLayers.size(), (mid_pixel *)dOut, nullptr));
                     });
@@ -438,6 +457,11 @@ public:
                                          std::to_string(L) + ": every frame needs the same layers");
             L = li;
         }
+        // the layers' format, one for the run: .exr layers (RGBA32F, RGBA16F with --half) guide the bilateral filters only
+        std::vector<std::string> allLayers;
+        for (auto &fl : frameLayers) allLayers.insert(allLayers.end(), fl.begin(), fl.end());
+        if (nlm_layers || nlm_layers_t) for (const std::string &ln : allLayers) if (is_hdr(ln)) (void)load(ln, true);   // refuses, saying why
+        const int lfmt = layer_format(allLayers);
         std::cout << "\tloading " << n << " frames\n";
         // Frames are decoded STRAIGHT INTO pinned host memory (mid_image_load_pinned) and the results land in pinned
         // buffers too, so every copy of the pipeline is a true asynchronous DMA -- the reference memcpy's its decoded
@@ -497,7 +521,8 @@ public:
         decode(0, pinned_budget > 0);                       // (the first frame's size is not known yet: any non-zero budget admits it)
         frame_bytes_guess = (size_t)pin.frames[0].width * pin.frames[0].height *
                             (pin.frames[0].format == MID_FMT_RGBA32F ? 16 : pin.frames[0].format == MID_FMT_RGBA16F ? 8 : 4);
-        const size_t layer_bytes = (size_t)pin.frames[0].width * pin.frames[0].height * 4;       // (RGBA8; checked against the frame below)
+        const size_t layer_bytes = (size_t)pin.frames[0].width * pin.frames[0].height *
+                                   (lfmt == MID_FMT_RGBA32F ? 16 : lfmt == MID_FMT_RGBA16F ? 8 : 4);    // (its real size; checked against the frame below)
         // frames whose input AND output -- and their layers -- fit the budget
         const size_t n_pin = pinned_budget / (2 * frame_bytes_guess + (size_t)L * layer_bytes);
         const int io_threads = files_at_a_time(n);
@@ -507,14 +532,16 @@ public:
             if (a.width != b.width || a.height != b.height || a.format != b.format)
                 throw std::runtime_error(frameNames[i] + ": size/format differs from the first frame");
         });
-        // --animation-filter layers / nlm-layers: PNG layers decoded as RGBA8 like the single-frame mode, page-locked with their frame
+        // --animation-filter layers / nlm-layers: PNG layers decoded as RGBA8 like the single-frame mode (.exr layers of the bilateral
+        // filters as RGBA32F / RGBA16F), page-locked with their frame
         std::vector<HostImage> layerImgs((size_t)n * L);             // (released before `pin` and its context)
         for_each_file(0, (int)layerImgs.size(), [&](int j) {
             const int i = j / L;
-            layerImgs[j] = load(frameLayers[i][j % L], true, (size_t)i < n_pin ? io : nullptr);
+            layerImgs[j] = load(frameLayers[i][j % L], nlm_layers || nlm_layers_t, (size_t)i < n_pin ? io : nullptr, lfmt == MID_FMT_RGBA16F);
             const HostImage &l = layerImgs[j];
-            if (l.w != pin.frames[0].width || l.h != pin.frames[0].height || l.format != MID_FMT_RGBA8)
-                throw std::runtime_error(frameNames[i] + ": layer " + frameLayers[i][j % L] + " is not an RGBA8 image of the frame's size");
+            if (l.w != pin.frames[0].width || l.h != pin.frames[0].height || l.format != lfmt)
+                throw std::runtime_error(frameNames[i] + ": layer " + frameLayers[i][j % L] + " is not " +
+                                         (lfmt == MID_FMT_RGBA8 ? "an RGBA8" : lfmt == MID_FMT_RGBA16F ? "an RGBA16F" : "an RGBA32F") + " image of the frame's size");
         });
         std::vector<const void *> layer_ptrs(layerImgs.size());
         for (size_t j = 0; j < layerImgs.size(); ++j) layer_ptrs[j] = layerImgs[j].data();
@@ -549,7 +576,8 @@ public:
         std::vector<mid_ctx *> ctxs(G, nullptr);
         struct CtxGuard { std::vector<mid_ctx *> &v; ~CtxGuard() { for (auto c : v) if (c) mid_ctx_destroy(c); } } guard{ctxs};
         const mid_nlm_params p{w, h, opt.nlm_h, opt.search_lo, opt.search_hi, opt.patch_lo, opt.patch_hi, fmt};
-        const mid_bilateral_params bp{w, h, opt.sigma_s, opt.sigma_c, opt.radius, linear ? MID_LAYOUT_LINEAR : MID_LAYOUT_TEXTURE, fmt};
+        const mid_bilateral_params bp{w, h, opt.sigma_s, opt.sigma_c, opt.radius, linear ? MID_LAYOUT_LINEAR : MID_LAYOUT_TEXTURE,
+                                      use_layers && lfmt != MID_FMT_RGBA8 ? MID_FMT_WITH_GUIDE(fmt, lfmt) : fmt};
         const int out_fmt = hdr ? MID_FMT_RGBA32F : half ? MID_FMT_RGBA16F : MID_FMT_RGBA8;
         const auto tw0 = std::chrono::steady_clock::now();
         for (int g = 0; g < G; ++g) {
@@ -563,7 +591,7 @@ public:
             if (bil) {
                 mid_bilateral_params wbp = bp;
                 wbp.width = ww; wbp.height = wh;
-                std::vector<unsigned char> lz((size_t)ww * wh * 4, 0);
+                std::vector<unsigned char> lz((size_t)ww * wh * 16, 0);      // (a layer of any guide format)
                 const void *wl[16];
                 for (int l = 0; l < L; ++l) wl[l] = lz.data();
                 void *wo[1] = {o.data()};
@@ -577,7 +605,7 @@ public:
             } else if (bil_t) {
                 mid_bilateral_params wbp = bp;
                 wbp.width = ww; wbp.height = wh;
-                std::vector<unsigned char> lz((size_t)ww * wh * 4, 0);
+                std::vector<unsigned char> lz((size_t)ww * wh * 16, 0);      // (a layer of any guide format)
                 const void *wl[32];
                 for (int l = 0; l < 2 * L; ++l) wl[l] = lz.data();
                 void *wo[1] = {o.data()};
@@ -787,7 +815,11 @@ static void usage()
         "  --device N                HIP device (default 0)\n"
         "  --modes LIST              comma list of bilateral,layers,linear,nlm,multiframe,overlap (default all, reference order),\n"
         "                            and nlm-layers (not part of all): NLM with its weights taken from the image's RenderElements\n"
-        "                            layers (--nlm-h / --search / --patch apply), output output-nonlinear-nlm-layers.{png,exr}\n"
+        "                            layers (--nlm-h / --search / --patch apply), output output-nonlinear-nlm-layers.{png,exr}.\n"
+        "                            Layer files: .png (RGBA8) -- or, for the bilateral modes only (layers here, layers and\n"
+        "                            layers-temporal under --animation-filter), .exr: normals, depth, HDR albedo as rendered, read as\n"
+        "                            RGBA32F, or as RGBA16F with --half; all layers of a run must have one format; nlm-layers and\n"
+        "                            nlm-layers-temporal take .png layers only (their patch distances are integer sums of bytes)\n"
         "  --gpu-only | --cpu-only   run only the GPU modes / only the CPU runs\n"
         "  --radius R                bilateral window radius (default 20 = TEXEL_WINDOW)\n"
         "  --sigma-s S --sigma-c C   bilateral sigmas (default 2.0 0.2)\n"
@@ -797,7 +829,7 @@ static void usage()
         "  --animation               denoise EVERY sibling frame with temporal NLM (window +-K, default 2) instead of the mode list\n"
         "  --animation-filter F      animation mode: nlm (default: temporal NLM), or the bilateral of every frame -- bilateral\n"
         "                            (texture addressing), linear (linear addressing) or layers (guided by each frame's own\n"
-        "                            RenderElements layers, 1..16 per frame, the same count for all); --radius / --sigma-s / --sigma-c\n"
+        "                            RenderElements layers, 1..16 per frame, the same count for all, .png or .exr); --radius / --sigma-s / --sigma-c\n"
         "                            apply; outputs output-animation-{nonlinear-bialteral,linear-bialteral,nonlinear-bialteral-layers}-*;\n"
         "                            or nlm-layers: NLM of every frame guided by its own layers (the same layer rules as layers;\n"
         "                            --nlm-h / --search / --patch apply), outputs output-animation-nonlinear-nlm-layers-*\n"
@@ -821,11 +853,13 @@ static void usage()
         "  --pageable-host           the six GPU modes: decode into and read back to ordinary (not page-locked) memory; the library\n"
         "                            then moves every copy through its own pinned bounce buffers -- same files, slower copies\n"
         "  --pinned-mb M             animation mode: page-lock at most M MiB of host memory for frames in and out (default 16384);\n"
-        "                            frames beyond that, or whose page-locked allocation fails, use pageable memory\n"
+        "                            frames beyond that, or whose page-locked allocation fails, use pageable memory (a frame's\n"
+        "                            layers count at their real size: 4, 8 or 16 bytes per pixel)\n"
         "  --io-threads T            animation mode: decode / encode T files at a time, one per host thread (default min(16, hardware threads))\n"
         "  --half                    .exr inputs of the GPU modes and of --animation: load the frames as RGBA16F (half float: HALF\n"
         "                            channels bit for bit), filter them as such and write HALF EXR outputs (the fp32 result rounded\n"
-        "                            to nearest even).  PNG inputs and the CPU runs ignore it; not with --halo rccl\n"
+        "                            to nearest even).  PNG inputs and the CPU runs ignore it; not with --halo rccl.  .exr LAYERS of\n"
+        "                            the bilateral modes load as RGBA16F with it as well, whatever the frames are\n"
         "  --cpu-radius R --cpu-sigma-s S --cpu-sigma-c C   CPU path (default 10 10.0 0.2)\n"
         "  --cpu-threads A,B         thread counts of the CPU runs (default 1,8)\n"
         "  --cpu-fix-blue            use the blue channel in the CPU range distance (the reference does not)\n";

@@ -87,8 +87,9 @@ constexpr int kMaxLayers = 16;
 // [first - k, first + count - 1 + k] non-NULL (frames aligned for `fmt`), every output non-NULL and aligned for `out_fmt`, and
 // no output among the window's frames and layers (all outputs of the call may be in flight beside launches that still read
 // them).  layers[f * n_layers + l]; n_layers == 0 reads no layer table.  capi.cpp.
+// guide_fmt: the layers' MID_FMT_* -- RGBA16F layers must be 8-byte aligned, RGBA32F ones 16-byte aligned (guide_aligned).
 int check_temporal_window(const char *who, int fmt, const void *const *frames, const uint32_t *const *layers, int n_layers,
-                          int n_frames, int k, int first, int count, void *const *out, int out_fmt);
+                          int n_frames, int k, int first, int count, void *const *out, int out_fmt, int guide_fmt = MID_FMT_RGBA8);
 
 // The window of output frame t in the argument block of a kernel over neighbouring frames (NlmLayerPairArgs, BilPairArgs):
 // slot j holds frame max(0, t - k) + j followed by its n_layers guide layers, t_slot is the output frame's own slot.
@@ -160,9 +161,10 @@ inline bool stream_is_recording(hipStream_t s)
 int nlm_temporal_out(mid_ctx *ctx, const mid_nlm_params *p, const void *const *frames, int n_frames, int k,
                      int first, int count, void *const *out, int out_fmt, void *stream, int corunning = 0);
 
-// mid_bilateral (layers == nullptr) / mid_bilateral_layers (layers: n_layers RGBA8 guides, texture layout) with the output format as
+// mid_bilateral (layers == nullptr) / mid_bilateral_layers (layers: n_layers guides in fmt_guide(p->format), texture layout) with the output format as
 // an argument, as nlm_temporal_out: out_fmt = MID_FMT_RGBA8 / MID_FMT_RGBA16F writes pack_rgba8 / pack_rgba16f of the float4 result.
 // No checks: the caller has made those of the public entry points.  Used by the frame pipeline (mid_sequence_bilateral), not exported.
+// RGBA16F / RGBA32F guides run as the k = 0 window of one frame on bilateral_temporal.hip's kernels (bilateral_temporal_out).
 int bilateral_out(mid_ctx *ctx, const mid_bilateral_params *p, const void *in, const uint32_t *const *layers, int n_layers,
                   void *out, int out_fmt, hipStream_t s);
 
@@ -183,7 +185,9 @@ int nlm_layers_temporal_out(mid_ctx *ctx, const mid_nlm_params *p, const void *c
 int nlm_layers_temporal_fits(const char *who, int n_layers, int n_frames, int k);
 
 // The parameter checks of mid_bilateral (size, sigmas, radius, format, layout): bilateral.hip, shared with bilateral_temporal.hip.
-int bilateral_check_params(const mid_bilateral_params *p, const char *who);
+// guide_ok: the entry point reads guide layers of the bilateral family, so the format word may carry their format
+// (MID_FMT_WITH_GUIDE); everywhere else a non-zero guide field is refused.
+int bilateral_check_params(const mid_bilateral_params *p, const char *who, bool guide_ok = false);
 
 // mid_bilateral_temporal without its checks (the caller has made them), one launch per output frame on `s`; layers == nullptr is
 // the plain form: bilateral_temporal.hip; used by the frame pipeline (mid_sequence_bilateral_temporal), not exported.
@@ -192,6 +196,10 @@ int bilateral_check_params(const mid_bilateral_params *p, const char *who);
 int bilateral_temporal_out(mid_ctx *ctx, const mid_bilateral_params *p, const void *const *frames, const uint32_t *const *layers,
                            int n_layers, int n_frames, int k, int first, int count, void *const *out, int out_fmt, hipStream_t s);
 int bilateral_temporal_check(const mid_bilateral_params *p, const char *who, bool layered, int n_layers, int n_frames, int k);
+// mid_bilateral_layers_pair_accum without its checks; mid_bilateral_layers_accum with RGBA16F / RGBA32F guides is this dispatch
+// with target_layer == neighbour_layer.  bilateral_temporal.hip.
+int bilateral_layers_pair_out(mid_ctx *ctx, const mid_bilateral_params *p, const void *target_layer, const void *neighbour_layer,
+                              const void *neighbour_in, mid_weightinfo *W, hipStream_t s);
 
 // ROCTx ranges (csrc/markers.cpp): no-ops unless the process already holds a ROCTx (rocprofv3 --marker-trace preloads one).
 bool markers_active();
@@ -283,6 +291,19 @@ inline size_t fmt_bytes(int fmt) { return fmt == MID_FMT_RGBA8 ? 4 : fmt == MID_
 inline bool fmt_known(int fmt) { return fmt == MID_FMT_RGBA32F || fmt == MID_FMT_RGBA8 || fmt == MID_FMT_RGBA16F; }
 // Device pointers of RGBA16F images are read 8 bytes per texel: they must be 8-byte aligned (hipMalloc'd buffers are).
 inline bool fmt_aligned(int fmt, const void *p) { return fmt != MID_FMT_RGBA16F || ((uintptr_t)p & 7u) == 0; }
+// The two fields of mid_bilateral_params.format (MID_FMT_WITH_GUIDE): the frames' MID_FMT_* in bits 0..7, and in bits 8..15
+// 0 (guide layers RGBA8) or 1 + MID_FMT_* of the guide layers.  fmt_guide: -1 for a code that names no format.
+inline int fmt_frames(int format) { return format & 0xff; }
+inline int fmt_guide(int format)
+{
+    const int c = (format >> 8) & 0xff;
+    return c == 0 ? MID_FMT_RGBA8 : fmt_known(c - 1) ? c - 1 : -1;
+}
+// Guide layers are read one texel per load: RGBA16F ones must be 8-byte aligned, RGBA32F ones 16-byte aligned.
+inline bool guide_aligned(int guide_fmt, const void *p)
+{
+    return ((uintptr_t)p & (guide_fmt == MID_FMT_RGBA16F ? 7u : guide_fmt == MID_FMT_RGBA32F ? 15u : 0u)) == 0;
+}
 
 // 2-D fetch with the zero-texel policy for out-of-image coordinates (texelFetch of the
 // sampler2D shaders; SURVEY.md 8a: OOB = vec4(0)).

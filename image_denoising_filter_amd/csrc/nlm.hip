@@ -136,6 +136,9 @@ int nlm_check_params(const mid_nlm_params *p)
     MID_REQUIRE(p->search_lo <= 0 && p->search_hi >= 1 && p->patch_lo <= 0 && p->patch_hi >= 1,
                 "nlm: half-open ranges [lo,hi) must contain 0");
     MID_REQUIRE(p->search_hi - p->search_lo <= 64 && p->patch_hi - p->patch_lo <= 16, "nlm: window too large");
+    MID_REQUIRE((p->format & ~0xff) == 0 || !fmt_known(fmt_frames(p->format)) || (p->format & ~0xffff) != 0,
+                "nlm: format 0x%x names a guide-layer format: the NLM filters take RGBA8 guide layers only (half and float guides "
+                "exist for the bilateral family)", p->format);
     MID_REQUIRE(fmt_known(p->format), "nlm: unknown format %d", p->format);
     return MID_OK;
 }

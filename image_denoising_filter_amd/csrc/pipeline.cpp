@@ -108,7 +108,7 @@ struct Stage {
     const mid_nlm_params *nlm;                // temporal NLM, or
     const mid_bilateral_params *bil;          // bilateral (plain, or layer-guided when host_layers is set), or
     const mid_nlm_params *nlm_layers;         // layer-guided NLM
-    const void *const *host_layers;           // n_layers RGBA8 host layers per frame, frame-major; NULL: plain bilateral / no layers
+    const void *const *host_layers;           // n_layers host layers per frame, frame-major; NULL: plain bilateral / no layers
     int n_layers;
     bool temporal = false;                    // nlm_layers / bil over the frames t-k..t+k (mid_sequence_nlm_layers_temporal, mid_sequence_bilateral_temporal), any k
 };
@@ -122,7 +122,8 @@ static int run_pipeline(mid_ctx *ctx, const Stage &st, const void *const *host_f
     const int f_lo = first - k < 0 ? 0 : first - k;                                  // first frame ever uploaded
     const int f_hi = first + count - 1 + k > n - 1 ? n - 1 : first + count - 1 + k;  // last one
     const size_t npix = (size_t)st.width * st.height;
-    const size_t in_bytes = npix * fmt_bytes(st.format), layer_bytes = npix * 4;
+    // (guide layers: RGBA8, or with the bilateral what its format word names -- st.bil->format keeps both fields for the kernels)
+    const size_t in_bytes = npix * fmt_bytes(st.format), layer_bytes = npix * fmt_bytes(st.bil ? fmt_guide(st.bil->format) : MID_FMT_RGBA8);
     const int n_layers = st.host_layers ? st.n_layers : 0;
     const size_t dl_bytes = npix * fmt_bytes(out_fmt);            // one output frame, as it is written and downloaded
     const int n_up = f_hi - f_lo + 1;
@@ -433,7 +434,11 @@ extern "C" int mid_sequence_bilateral(mid_ctx *ctx, const mid_bilateral_params *
     MID_REQUIRE((long)p->width * p->height < (1l << 30), "sequence_bilateral: image too large");
     MID_REQUIRE(p->spatialSigma > 0.f && p->colorSigma > 0.f, "sequence_bilateral: sigmas must be > 0");
     MID_REQUIRE(p->radius >= 1 && p->radius <= 24, "sequence_bilateral: radius %d outside 1..24", p->radius);
-    MID_REQUIRE(fmt_known(p->format), "sequence_bilateral: unknown format %d", p->format);
+    MID_REQUIRE((p->format & ~0xffff) == 0 && fmt_known(fmt_frames(p->format)), "sequence_bilateral: unknown format %d", p->format);
+    if ((p->format >> 8) != 0) {
+        MID_REQUIRE(host_layers != nullptr, "sequence_bilateral: format 0x%x names a guide-layer format, and this call has no guide layers", p->format);
+        MID_REQUIRE(fmt_guide(p->format) >= 0, "sequence_bilateral: unknown guide-layer format code %d in format 0x%x", p->format >> 8, p->format);
+    }
     MID_REQUIRE(p->layout == MID_LAYOUT_TEXTURE || p->layout == MID_LAYOUT_LINEAR, "sequence_bilateral: unknown layout %d", p->layout);
     MID_REQUIRE(fmt_known(out_format), "sequence_bilateral: unknown output format %d", out_format);
     MID_REQUIRE(n_layers >= 0 && n_layers <= kMaxLayers, "sequence_bilateral: n_layers %d outside 0..16", n_layers);
@@ -452,7 +457,7 @@ extern "C" int mid_sequence_bilateral(mid_ctx *ctx, const mid_bilateral_params *
     }
     if (int rc = check_no_alias("sequence_bilateral", "an input frame or layer of this call", inputs.data(), (int)inputs.size(),
                                 (const void *const *)host_out, n_frames)) return rc;
-    const Stage st{"sequence_bilateral", p->width, p->height, p->format, nullptr, p, nullptr, host_layers, n_layers};
+    const Stage st{"sequence_bilateral", p->width, p->height, fmt_frames(p->format), nullptr, p, nullptr, host_layers, n_layers};
     return run_pipeline(ctx, st, host_frames, n_frames, 0, 0, n_frames, host_out, out_format, overlap, timings_ms);
 }
 
@@ -564,7 +569,7 @@ extern "C" int mid_sequence_bilateral_temporal(mid_ctx *ctx, const mid_bilateral
     for (int i = 0; i < count; ++i) MID_REQUIRE(host_out[i], "sequence_bilateral_temporal: output %d is NULL", i);
     if (int rc = check_no_alias("sequence_bilateral_temporal", "an input frame or layer of this call", inputs.data(), (int)inputs.size(),
                                 (const void *const *)host_out, count)) return rc;
-    const Stage st{"sequence_bilateral_temporal", p->width, p->height, p->format, nullptr, p, nullptr, host_layers, n_layers, true};
+    const Stage st{"sequence_bilateral_temporal", p->width, p->height, fmt_frames(p->format), nullptr, p, nullptr, host_layers, n_layers, true};
     return run_pipeline(ctx, st, host_frames, n_frames, k, first, count, host_out, out_format, overlap, timings_ms);
 }
 

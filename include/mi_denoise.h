@@ -62,6 +62,19 @@ typedef struct mid_weightinfo {
  * params.format is read. */
 enum { MID_FMT_RGBA32F = 0, MID_FMT_RGBA8 = 1, MID_FMT_RGBA16F = 2 };
 
+/* Guide-layer format of the layer-guided BILATERAL calls.  mid_bilateral_params.format is one word with two fields:
+ * format = MID_FMT_* of the frames in bits 0..7; bits 8..15 = 0 (guide layers RGBA8, as always) or 1 + MID_FMT_* of the guide layers.
+ * A caller that passes 0, 1 or 2 gets what it always got.  The guide field is read by mid_bilateral_layers_accum,
+ * mid_bilateral_layers, mid_bilateral_layers_pair_accum, mid_bilateral_temporal with a layer table, and mid_sequence_bilateral /
+ * mid_sequence_bilateral_temporal with host_layers; all layers of one call share the one format.  Every other entry point that
+ * reads a `format` -- the plain and linear bilateral, mid_bilateral_batch, mid_bilateral_pair_accum, the plain forms of
+ * mid_bilateral_temporal and the two pipelines, everything that takes mid_nlm_params -- refuses a non-zero guide field with
+ * MID_ERR_INVALID before anything is queued (layer-guided NLM takes RGBA8 guides only: its patch distances are exact integer
+ * sums of byte values).  Also MID_ERR_INVALID: a guide code that names no format, bits above 15, an RGBA16F guide layer that is
+ * not 8-byte aligned, an RGBA32F one that is not 16-byte aligned (device pointers; the pipelines' host layers need no alignment).
+ * What a guide texel means is said in section a3. */
+#define MID_FMT_WITH_GUIDE(fmt, guide_fmt) ((fmt) | (((guide_fmt) + 1) << 8))
+
 /* Addressing of the bilateral input: bialteral.comp (sampler2D, 2-D texelFetch, out-of-image
  * texel = 0) vs bialteral_linear.comp (samplerBuffer, flat index c + j + i*width: columns wrap
  * into the adjacent row, index outside [0,N) = 0).  m_linear = !nonlinear, src/main.cpp:1311. */
@@ -78,7 +91,7 @@ typedef struct mid_bilateral_params {
     float   colorSigma;
     int32_t radius;   /* window is (2*radius+1)^2; kernels exist for 1..24 */
     int32_t layout;   /* MID_LAYOUT_* (ignored by the layers kernels: always texture) */
-    int32_t format;   /* MID_FMT_* of `in` (RGBA32F, RGBA8 or RGBA16F; guide layers are always RGBA8) */
+    int32_t format;   /* MID_FMT_* of `in` (RGBA32F, RGBA8 or RGBA16F); guide layers are RGBA8 unless MID_FMT_WITH_GUIDE says otherwise */
 } mid_bilateral_params;
 
 /* Push-constant block of nonlocal.comp (shaders/nonlocal.comp:16-22: {int width; int height;
@@ -211,11 +224,26 @@ int mid_bilateral_batch(mid_ctx *ctx, const mid_bilateral_params *p, const void 
  * (RecordCommandsOfExecuteNLM(nlm=false), src/main.cpp:849-887): W[p] += sums, bindings
  * {0: WeightInfo W[N]; 1: inputTex; 2: layerTex (always RGBA8, src/main.cpp:1396,1419-1420)}.
  * mid_bilateral_layers = the whole per-layer loop src/main.cpp:1610-1623 plus normalize
- * (:1649-1652) fused in one kernel: no WeightInfo traffic. */
+ * (:1649-1652) fused in one kernel: no WeightInfo traffic.
+ * Half and float guide layers (p->format = MID_FMT_WITH_GUIDE(frames' format, MID_FMT_RGBA16F or MID_FMT_RGBA32F)): what a
+ * renderer writes beside an HDR beauty pass -- normals in [-1, 1], depth in scene units, HDR albedo -- guides the filter as it
+ * is.  A guide texel's r, g, b are read as IEEE values (half values are widened exactly, as for frames); the guide's alpha is
+ * ignored; an out-of-image guide texel is vec4(0).  The weight is the formula of the RGBA8 guides,
+ *   exp(-0.5 |G(p) - G(p+o)|^2_rgb / colorSigma^2),
+ * with NO clamping to [0, 1].  Non-finite guide texels follow IEEE arithmetic: an Inf against a finite value gives weight 0;
+ * Inf against Inf, or a NaN, poisons (NaN) the pixels whose windows hold it.  Precision: the kernels carry a guide value as the
+ * fp32 product g * sqrt(0.5 log2 e) / colorSigma -- as they always did for RGBA8 -- so the relative precision of a weight falls
+ * off as about 2^-24 |g| / colorSigma.  Up to |g| <= 16 colorSigma the results stay inside the bilateral tolerance of the
+ * RGBA8 guides (1e-5 relative); scale depth-like layers (subtract an offset, divide by the scene's extent) or colorSigma so
+ * that |g| / colorSigma stays moderate.  A float guide with rgb = the fp32 quotient c / 255 gives the bits of the RGBA8 guide c,
+ * and a half guide the bits of the float guide it widens to.
+ * The layer parameters keep their C type whatever the guide format: with RGBA16F / RGBA32F guides the caller casts its
+ * pointers (8 / 16 bytes per texel) to const uint32_t *. */
 int mid_bilateral_layers_accum(mid_ctx *ctx, const mid_bilateral_params *p, const void *in,
-                               const uint32_t *layer_rgba8, mid_weightinfo *W, void *stream);
+                               const uint32_t *layer_rgba8 /* or, cast, an RGBA16F / RGBA32F layer: MID_FMT_WITH_GUIDE */,
+                               mid_weightinfo *W, void *stream);
 int mid_bilateral_layers(mid_ctx *ctx, const mid_bilateral_params *p, const void *in,
-                         const uint32_t *const *layers_rgba8 /* host array of device ptrs */,
+                         const uint32_t *const *layers_rgba8 /* host array of device ptrs; cast RGBA16F / RGBA32F layers with MID_FMT_WITH_GUIDE */,
                          int n_layers, mid_pixel *out, void *stream);
 
 /* ---- a4: non-local means ----------------------------------------------------------------
@@ -291,8 +319,10 @@ int mid_nlm_layers_temporal(mid_ctx *ctx, const mid_nlm_params *p,
 
 /* ---- a4d: the bilateral filter over neighbouring frames -----------------------------------
  * mid_bilateral / mid_bilateral_layers with the neighbouring frames of an animation as further sources of samples.  Texture
- * addressing only (out-of-image texel = vec4(0)); guides RGBA8, texels c/255; frames in p->format; radius, spatialSigma and
- * colorSigma as in mid_bilateral.
+ * addressing only (out-of-image texel = vec4(0)); guides RGBA8, texels c/255 -- or, with MID_FMT_WITH_GUIDE in p->format, RGBA16F
+ * / RGBA32F guides with the semantics of section a3 (IEEE values, alpha ignored, no clamping, non-finite texels by IEEE
+ * arithmetic, |g| <= 16 colorSigma for the tolerance; the layer parameters keep their C type and the caller casts); frames in
+ * the frames' field of p->format; radius, spatialSigma and colorSigma as in mid_bilateral.
  * One pair dispatch has a target guide Gt, a neighbour guide Gn and a neighbour colour image In: for each pixel p and tap
  * o = (i, j), |i|, |j| <= radius,
  *   w = exp(-0.5 |o|^2 / spatialSigma^2) * exp(-0.5 |Gt(p) - Gn(p+o)|^2_rgb / colorSigma^2)
@@ -320,14 +350,16 @@ int mid_nlm_layers_temporal(mid_ctx *ctx, const mid_nlm_params *p,
  * (the limit and the rule of mid_nlm_layers_temporal), and for: the parameter checks of mid_bilateral; MID_LAYOUT_LINEAR (the
  * linear variant exists to time a buffer against a texture and has no temporal form); a NULL pointer; n_layers outside 0..16,
  * or not 0 in the plain form; k < 0, first < 0, count < 1, first + count > n_frames; an unknown out_format; an RGBA16F frame or
- * output that is not 8-byte aligned; an output that is also a frame or layer of the window, or appears twice. */
+ * output that is not 8-byte aligned; an output that is also a frame or layer of the window, or appears twice; a guide field in
+ * the plain forms, an unknown guide code, an RGBA16F guide layer that is not 8-byte aligned, an RGBA32F one not 16-byte aligned. */
 int mid_bilateral_pair_accum(mid_ctx *ctx, const mid_bilateral_params *p, const void *target, const void *neighbour,
                              mid_weightinfo *W, void *stream);
+/* (both layers in the guide format of p->format: RGBA8, or cast RGBA16F / RGBA32F layers with MID_FMT_WITH_GUIDE) */
 int mid_bilateral_layers_pair_accum(mid_ctx *ctx, const mid_bilateral_params *p, const uint32_t *target_layer_rgba8,
                                     const uint32_t *neighbour_layer_rgba8, const void *neighbour_in, mid_weightinfo *W, void *stream);
 int mid_bilateral_temporal(mid_ctx *ctx, const mid_bilateral_params *p,
                            const void *const *frames /* host array of n_frames device ptrs */,
-                           const uint32_t *const *layers_rgba8 /* host array of n_frames * n_layers device ptrs, or NULL */,
+                           const uint32_t *const *layers_rgba8 /* host array of n_frames * n_layers device ptrs, or NULL; cast RGBA16F / RGBA32F layers with MID_FMT_WITH_GUIDE */,
                            int n_layers, int n_frames, int k, int first, int count,
                            void *const *out /* host array of `count` device ptrs */, int out_format, void *stream);
 
@@ -393,13 +425,16 @@ int mid_sequence_nlm_range_f16(mid_ctx *ctx, const mid_nlm_params *p, const void
  * i, its n_layers layers) -- host_layers != NULL, texture layout -- followed by mid_pack_u8 / mid_pack_f16 when out_format is
  * MID_FMT_RGBA8 / MID_FMT_RGBA16F (the kernel's epilogue packs).  With host_layers set and n_layers == 0 every output pixel is the
  * magenta sentinel, as in mid_bilateral_layers.  host_frames: n_frames HOST pointers in p->format; host_layers: n_frames *
- * n_layers RGBA8 HOST pointers, frame-major (frame i's layers are uploaded with frame i); host_out: n_frames HOST pointers.
+ * n_layers HOST pointers, frame-major (frame i's layers are uploaded with frame i), RGBA8 -- or RGBA16F / RGBA32F layers when
+ * p->format = MID_FMT_WITH_GUIDE(frames' format, layers' format): the layer ring then holds 8 / 16 bytes per texel, host layers
+ * need no alignment, pageable ones go through the bounce buffers like frames; host_out: n_frames HOST pointers.
  * A packed output (RGBA8 or RGBA16F) is stored by the kernel itself when every output lies inside ONE page-locked allocation or
  * registration of this device; otherwise the outputs are downloaded from device slots (through the bounce buffers where an
  * output is not inside one mapping).  Frames are independent: a frame block is a sub-array, so there is no _range variant.
  * overlap and timings_ms as for mid_sequence_nlm.  MID_ERR_INVALID, before anything is queued, for: a NULL frame, layer or output;
  * n_layers outside 0..16; layers with MID_LAYOUT_LINEAR; an unknown out_format; an output that is also an input frame or layer
- * (or appears twice); the parameter checks of mid_bilateral; a call while the context's stream records. */
+ * (or appears twice); the parameter checks of mid_bilateral; a guide field in p->format without host_layers, or an unknown guide
+ * code; a call while the context's stream records. */
 int mid_sequence_bilateral(mid_ctx *ctx, const mid_bilateral_params *p, const void *const *host_frames, int n_frames,
                            const void *const *host_layers, int n_layers, void *const *host_out, int out_format,
                            int overlap, float *timings_ms);
@@ -436,7 +471,8 @@ int mid_sequence_nlm_layers_temporal(mid_ctx *ctx, const mid_nlm_params *p, cons
 
 /* The same pipeline with the bilateral over neighbouring frames as its compute stage: outputs [first, first+count) of the
  * sequence, output t with the bits of mid_bilateral_temporal(p, frames, layers, k) for frame t in out_format.  host_layers ==
- * NULL selects the plain form (n_layers must be 0).  Schedule, layer ring and output rule are mid_sequence_nlm_layers_temporal's:
+ * NULL selects the plain form (n_layers must be 0); host layers are RGBA8, or RGBA16F / RGBA32F with MID_FMT_WITH_GUIDE in p->format,
+ * as in mid_sequence_bilateral (a guide field in the plain form is MID_ERR_INVALID).  Schedule, layer ring and output rule are mid_sequence_nlm_layers_temporal's:
  * ring of 2k+4 frames, frame f's layers uploaded with frame f and alive as long as its slot, only the frames of
  * [first-k, first+count+k) read, packed outputs stored by the kernel only when every one lies inside ONE page-locked allocation
  * or registration.  MID_ERR_INVALID, before anything is queued, for: a NULL frame, layer or output of the range; n_layers
