@@ -421,6 +421,29 @@ class Context:
                "mid_bilateral_temporal")
         return [self.download(d, (h, w, 4), out_dtype) for d in d_out]
 
+    def bilateral_joint(self, frames, layers, sigmas=None, k=0, first=0, count=None, radius=8, sigma_s=2.0, sigma_c=0.2, out_dtype=None):
+        """The joint (cross) bilateral over the frames t-k..t+k for `count` output frames (mid_bilateral_joint): one weight per
+        tap, the product of the spatial term and one range term per guide layer.  layers: one list per frame of equally many
+        (1..16) (h, w, 4) guide layers, uint8, float16 or float32 and all of one dtype; sigmas: one sigma per layer, or None for
+        sigma_c in every layer; out_dtype: None = float32, uint8 or float16."""
+        frames = _same_frames(frames, "bilateral_joint")
+        n = len(frames)
+        count = n - first if count is None else count
+        h, w = frames[0].shape[:2]
+        n_layers, flat = _flat_layers(layers, n, h, w, "bilateral_joint", _GUIDE_DTYPES)
+        out_dtype = _out_dtype(False, out_dtype)
+        out_fmt = {np.dtype(np.uint8): FMT_RGBA8, np.dtype(np.float16): FMT_RGBA16F, np.dtype(np.float32): FMT_RGBA32F}[out_dtype]
+        d_fr = [self.upload(f) for f in frames]
+        d_l = [self.upload(l) for l in flat]
+        d_out = [self.alloc(w * h * 4 * out_dtype.itemsize) for _ in range(max(count, 0))]
+        p = BilateralParams(w, h, sigma_s, sigma_c, radius, LAYOUT_TEXTURE, _guide_fmt(_fmt_of(frames[0]), flat, "bilateral_joint"))
+        _check(lib.mid_bilateral_joint(self.handle, ctypes.byref(p), _layer_sigmas(sigmas, n_layers, "bilateral_joint"),
+                                       (ctypes.c_void_p * n)(*[d.ptr for d in d_fr]),
+                                       (ctypes.c_void_p * max(len(d_l), 1))(*[d.ptr for d in d_l]), n_layers, n, k, first, count,
+                                       (ctypes.c_void_p * max(len(d_out), 1))(*[d.ptr for d in d_out]), out_fmt, None),
+               "mid_bilateral_joint")
+        return [self.download(d, (h, w, 4), out_dtype) for d in d_out]
+
     def normalize(self, W):
         """normalize.comp."""
         W = np.ascontiguousarray(W, dtype=np.float32)
@@ -741,6 +764,66 @@ class Context:
                 if b is not None:
                     b.free()
 
+    def sequence_bilateral_joint_pinned(self, hin, hout, w, h, fmt, hlayers, n_layers, sigmas=None, k=0, first=0, count=None, radius=8,
+                                        sigma_s=2.0, sigma_c=0.2, overlap=True, out_dtype=None):
+        """mid_sequence_bilateral_joint on host pointers the caller already holds: nothing but the C call.  hin, hlayers, hout as
+        for sequence_bilateral_temporal_pinned (hlayers is required); sigmas: n_layers sigmas or None.
+        Returns (wall_ms of the whole call, kernel_ms, copy_ms)."""
+        n = len(hin)
+        count = n - first if count is None else count
+        if len(hout) < count:
+            raise ValueError(f"{count} outputs, {len(hout)} output buffers given")
+        if len(hlayers) != n * n_layers:
+            raise ValueError(f"{n} frames x {n_layers} layers, {len(hlayers)} layer pointers given")
+        prm = BilateralParams(w, h, sigma_s, sigma_c, radius, LAYOUT_TEXTURE, fmt)
+        out_fmt = {np.dtype(np.uint8): FMT_RGBA8, np.dtype(np.float16): FMT_RGBA16F,
+                   np.dtype(np.float32): FMT_RGBA32F}[_out_dtype(False, out_dtype)]
+        t = (ctypes.c_float * 3)()
+        _check(lib.mid_sequence_bilateral_joint(self.handle, ctypes.byref(prm), _layer_sigmas(sigmas, n_layers, "sequence_bilateral_joint"),
+                                                (ctypes.c_void_p * n)(*hin), n, (ctypes.c_void_p * max(len(hlayers), 1))(*hlayers),
+                                                n_layers, k, first, count, (ctypes.c_void_p * max(count, 1))(*hout[:max(count, 0)]),
+                                                out_fmt, 1 if overlap else 0, t),
+               "mid_sequence_bilateral_joint")
+        return tuple(t)
+
+    def sequence_bilateral_joint(self, frames, layers, sigmas=None, k=0, first=0, count=None, overlap=True, radius=8, sigma_s=2.0,
+                                 sigma_c=0.2, pinned=True, pinned_out=True, out_dtype=None):
+        """Outputs [first, first+count) of an animation through the overlapped pipeline with the joint bilateral over the frames
+        t-k..t+k as its compute stage (mid_sequence_bilateral_joint): output t is ctx.bilateral_joint(frames, layers, sigmas, k)
+        of frame t in out_dtype.  pinned, pinned_out, out_dtype as for sequence_bilateral.
+        Returns (outputs, (wall_ms, kernel_ms, copy_ms))."""
+        frames = _same_frames(frames, "sequence_bilateral_joint")
+        n = len(frames)
+        count = n - first if count is None else count
+        h, w = frames[0].shape[:2]
+        n_layers, flat = _flat_layers(layers, n, h, w, "sequence_bilateral_joint", _GUIDE_DTYPES)
+        out_shape, out_dtype = (h, w, 4), _out_dtype(False, out_dtype)
+        hin = hlay = hout = None
+        try:
+            hin = PinnedFrames(self, frames) if pinned else None
+            hlay = PinnedFrames(self, flat) if pinned and flat else None
+            hout = PinnedFrames(self, max(count, 1), w * h * 4 * out_dtype.itemsize) if pinned_out else None
+            outs = None if pinned_out else [np.empty(out_shape, out_dtype) for _ in range(max(count, 0))]
+            lptr = hlay.ptrs if hlay is not None else [lyr.ctypes.data for lyr in flat]
+            t = self.sequence_bilateral_joint_pinned(hin.ptrs if pinned else [f.ctypes.data for f in frames],
+                                                     hout.ptrs if pinned_out else [o.ctypes.data for o in outs], w, h,
+                                                     _guide_fmt(_fmt_of(frames[0]), flat, "sequence_bilateral_joint"), lptr, n_layers,
+                                                     sigmas, k, first, count, radius, sigma_s, sigma_c, overlap, out_dtype)
+            return (outs if outs is not None else [hout.array(i, out_shape, out_dtype) for i in range(count)]), t
+        finally:
+            for b in (hin, hlay, hout):
+                if b is not None:
+                    b.free()
+
+
+def _layer_sigmas(sigmas, n_layers, who):
+    """The layer_sigma argument of the joint bilateral: None, or a C array of n_layers floats."""
+    if sigmas is None:
+        return None
+    sigmas = [float(s) for s in sigmas]
+    if len(sigmas) != n_layers:
+        raise ValueError(f"{who}: {len(sigmas)} sigmas for {n_layers} layers")
+    return (ctypes.c_float * max(n_layers, 1))(*sigmas)
 
 
 def _flat_layers(layers, n, h, w, who, dtypes=(np.uint8,)):

@@ -50,6 +50,7 @@ struct Options {
     int device = 0;                 // deviceId{0}, src/main.cpp:1321
     int radius = 20;                // TEXEL_WINDOW, shaders/bialteral.comp:5
     float sigma_s = 2.0f, sigma_c = 0.2f;      // src/main.cpp:806,875
+    std::vector<float> sigma_layers;           // the joint modes: one range sigma per layer in discovery order (empty: sigma_c for all)
     float nlm_h = 0.5f;             // src/main.cpp:870
     int search_lo = -7, search_hi = 7, patch_lo = -3, patch_hi = 3;   // shaders/nonlocal.comp:5-6, half-open
     int temporal_k = -1;            // <0: the reference's frame list; >=0: window t-k..t+k of the sorted sequence
@@ -58,9 +59,9 @@ struct Options {
     bool cpu_blue_bug = true;       // pow(texColor.b - texColor.b, 2), src/main.cpp:1850
     std::vector<int> cpu_threads = {1, 8};     // src/main.cpp:1979,1984
     bool run_gpu = true, run_cpu = true;
-    std::string modes = "all";      // comma list of: bilateral,layers,linear,nlm,multiframe,overlap (all of them: "all"), nlm-layers
+    std::string modes = "all";      // comma list of: bilateral,layers,linear,nlm,multiframe,overlap (all of them: "all"), nlm-layers, joint
     bool animation = false;         // new capability: temporal NLM of EVERY frame of the sequence
-    std::string animation_filter = "nlm";   // animation mode: nlm | bilateral | linear | layers (the bilateral of every frame) | nlm-layers | nlm-layers-temporal | bilateral-temporal | layers-temporal
+    std::string animation_filter = "nlm";   // animation mode: nlm | bilateral | linear | layers (the bilateral of every frame) | nlm-layers | nlm-layers-temporal | bilateral-temporal | layers-temporal | joint | joint-temporal
     int gpus = 1;                   // animation mode: frame blocks over this many devices
     bool share_device = false;      // animation mode: every block on --device (rehearsal of --gpus N on fewer devices)
     bool halo_rccl = false;         // animation mode: blocks resident in HBM, halo frames GPU to GPU over RCCL (mid_nlm_temporal_sharded)
@@ -183,6 +184,19 @@ class DenoiseApplication {
         return names.empty() ? MID_FMT_RGBA8 : fmt_of(names[0]);
     }
 
+    // The joint modes' range sigmas, one per layer file in discovery (sorted) order: --sigma-layers, or --sigma-c for all of them.
+    // Prints the banner's `layer <file> sigma <value>` lines.
+    std::vector<float> layer_sigmas(const std::vector<std::string> &names) const
+    {
+        if (!opt.sigma_layers.empty() && opt.sigma_layers.size() != names.size())
+            throw std::runtime_error("--sigma-layers gives " + std::to_string(opt.sigma_layers.size()) + " sigma(s), but " +
+                                     std::to_string(names.size()) + " layer file(s) were found: one sigma per layer, in sorted order");
+        std::vector<float> s(names.size(), opt.sigma_c);
+        if (!opt.sigma_layers.empty()) s = opt.sigma_layers;
+        for (size_t l = 0; l < names.size(); ++l) std::cout << "\tlayer " << names[l] << " sigma " << s[l] << "\n";
+        return s;
+    }
+
     std::string out_path(const std::string &name) const { return (fs::path(opt.outdir) / name).string(); }
 
     // Files of a sequence are decoded / encoded CONCURRENTLY, one file per worker thread: the reference does its image I/O on one
@@ -251,7 +265,8 @@ public:
     }
 
     // RunOnGPU, src/main.cpp:1307-1730
-    void RunOnGPU(bool nlmFilter, bool nonlinear, bool multiframe, bool execAndCopyOverlap, bool useLayers)
+    // joint (with useLayers): the joint bilateral, one weight from all layers (mid_bilateral_joint), instead of the sum of one filter per layer
+    void RunOnGPU(bool nlmFilter, bool nonlinear, bool multiframe, bool execAndCopyOverlap, bool useLayers, bool joint = false)
     {
         const bool linear = !nonlinear;                                              // :1311
         TraceRange mode_range(std::string("RunOnGPU ") + (linear ? "linear" : "nonlinear") + (nlmFilter ? " nlm" : " bialteral") +
@@ -348,6 +363,12 @@ public:
                 std::vector<HostImage> layerImgs(layerNames.size());
                 if (nlmFilter) for (const std::string &ln : layerNames) if (is_hdr(ln)) (void)load(ln, true);       // refuses, saying why
                 const int lfmt = layer_format(layerNames);
+                std::vector<float> jointSigma;
+                if (joint) {
+                    if (layerNames.empty() || layerNames.size() > 16)
+                        throw std::runtime_error(opt.image + ": " + std::to_string(layerNames.size()) + " layer file(s) found, --modes joint needs 1..16");
+                    jointSigma = layer_sigmas(layerNames);
+                }
                 for_each_file(0, (int)layerNames.size(), [&](int i) {
                     layerImgs[i] = load(layerNames[i], nlmFilter, pin, lfmt == MID_FMT_RGBA16F);
                     if (layerImgs[i].format != lfmt) throw std::runtime_error(layerNames[i] + ": the decoded layer is not in the run's guide format");
@@ -367,6 +388,15 @@ public:
                     mid_nlm_params p{w, h, opt.nlm_h, opt.search_lo, opt.search_hi, opt.patch_lo, opt.patch_hi, fmt};
                     timed(m_execMs, [&] {
                         MID_CHECK(mid_nlm_layers(ctx, &p, dIn, (const uint32_t *const *)dLayers.data(), (int)dLayers.size(), (mid_pixel *)dOut, nullptr));
+                    });
+                } else if (joint) {
+                    mid_bilateral_params p{w, h, opt.sigma_s, opt.sigma_c, opt.radius, MID_LAYOUT_TEXTURE,
+                                           lfmt == MID_FMT_RGBA8 ? fmt : MID_FMT_WITH_GUIDE(fmt, lfmt)};
+                    const void *fr[1] = {dIn};
+                    void *ou[1] = {dOut};
+                    timed(m_execMs, [&] {
+                        MID_CHECK(mid_bilateral_joint(ctx, &p, jointSigma.data(), fr, (const uint32_t *const *)dLayers.data(), (int)dLayers.size(), 1, 0, 0, 1,
+                                                      ou, MID_FMT_RGBA32F, nullptr));
                     });
                 } else {
                     mid_bilateral_params p{w, h, opt.sigma_s, opt.sigma_c, opt.radius, MID_LAYOUT_TEXTURE,
@@ -393,7 +423,7 @@ public:
         outputFileName += nlmFilter ? "-nlm" : "-bialteral";
         outputFileName += multiframe ? "-multiframe" : "";
         outputFileName += execAndCopyOverlap ? "-overlap" : "";
-        outputFileName += useLayers ? "-layers" : "";
+        outputFileName += joint ? "-joint" : useLayers ? "-layers" : "";
         if (half) {   // --half: the fp32 result rounded to RGBA16F on the device (mid_pack_f16), written as HALF EXR
             std::vector<uint16_t> px(npix * 4);
             void *dF = nullptr, *dH = nullptr;
@@ -430,12 +460,15 @@ public:
         std::vector<std::string> frameNames, layerNames;
         discover(frameNames, layerNames, true, false);
         if (frameNames.empty()) throw std::runtime_error("no frames next to " + opt.image);
-        const int n = (int)frameNames.size(), k = opt.temporal_k < 0 ? 2 : opt.temporal_k;
+        // --animation-filter joint | joint-temporal: the joint bilateral of every frame, alone (k = 0) or over the frames t-k..t+k
+        // (mid_sequence_bilateral_joint: the schedule of layers-temporal)
+        const bool joint = opt.animation_filter == "joint" || opt.animation_filter == "joint-temporal";
+        const int n = (int)frameNames.size(), k = opt.animation_filter == "joint" ? 0 : opt.temporal_k < 0 ? 2 : opt.temporal_k;
         const bool nlm_layers = opt.animation_filter == "nlm-layers";                   // layer-guided NLM of every frame
         const bool nlm_layers_t = opt.animation_filter == "nlm-layers-temporal";        // ... over the frames t-k..t+k and their layers
-        const bool bil_t = opt.animation_filter == "bilateral-temporal" || opt.animation_filter == "layers-temporal";   // the bilateral over the frames t-k..t+k
+        const bool bil_t = opt.animation_filter == "bilateral-temporal" || opt.animation_filter == "layers-temporal" || joint;   // the bilateral over the frames t-k..t+k
         const bool bil = opt.animation_filter != "nlm" && !nlm_layers && !nlm_layers_t && !bil_t;
-        const bool use_layers = opt.animation_filter == "layers" || nlm_layers || nlm_layers_t || opt.animation_filter == "layers-temporal";
+        const bool use_layers = opt.animation_filter == "layers" || nlm_layers || nlm_layers_t || opt.animation_filter == "layers-temporal" || joint;
         const bool linear = opt.animation_filter == "linear";
         if ((bil || nlm_layers) && opt.halo_rccl)
             throw std::runtime_error("--halo rccl is not available with --animation-filter " + opt.animation_filter +
@@ -462,6 +495,7 @@ public:
         for (auto &fl : frameLayers) allLayers.insert(allLayers.end(), fl.begin(), fl.end());
         if (nlm_layers || nlm_layers_t) for (const std::string &ln : allLayers) if (is_hdr(ln)) (void)load(ln, true);   // refuses, saying why
         const int lfmt = layer_format(allLayers);
+        const std::vector<float> jointSigma = joint ? layer_sigmas(frameLayers[0]) : std::vector<float>();   // (every frame has frame 0's layers)
         std::cout << "\tloading " << n << " frames\n";
         // Frames are decoded STRAIGHT INTO pinned host memory (mid_image_load_pinned) and the results land in pinned
         // buffers too, so every copy of the pipeline is a true asynchronous DMA -- the reference memcpy's its decoded
@@ -609,7 +643,8 @@ public:
                 const void *wl[32];
                 for (int l = 0; l < 2 * L; ++l) wl[l] = lz.data();
                 void *wo[1] = {o.data()};
-                MID_CHECK(mid_sequence_bilateral_temporal(ctxs[g], &wbp, wi, 2, use_layers ? wl : nullptr, L, k > 0 ? 1 : 0, 0, 1, wo, out_fmt, 1, nullptr));
+                if (joint) MID_CHECK(mid_sequence_bilateral_joint(ctxs[g], &wbp, jointSigma.data(), wi, 2, wl, L, k > 0 ? 1 : 0, 0, 1, wo, out_fmt, 1, nullptr));
+                else MID_CHECK(mid_sequence_bilateral_temporal(ctxs[g], &wbp, wi, 2, use_layers ? wl : nullptr, L, k > 0 ? 1 : 0, 0, 1, wo, out_fmt, 1, nullptr));
             } else if (nlm_layers_t) {
                 std::vector<unsigned char> lz((size_t)ww * wh * 4, 0);
                 const void *wl[32];
@@ -720,6 +755,9 @@ public:
                     } else if (nlm_layers_t) { // this device's block plus k halo frames on either side, and their layers, from the host
                         MID_CHECK(mid_sequence_nlm_layers_temporal(ctx, &p, in.data(), n, layer_ptrs.data(), L, k, start, count,
                                                                    pin.outs.data() + start, out_fmt, 1, t));
+                    } else if (joint) {        // likewise, one weight from all layers
+                        MID_CHECK(mid_sequence_bilateral_joint(ctx, &bp, jointSigma.data(), in.data(), n, layer_ptrs.data(), L, k, start, count,
+                                                               pin.outs.data() + start, out_fmt, 1, t));
                     } else if (bil_t) {        // likewise, plain or with the layers
                         MID_CHECK(mid_sequence_bilateral_temporal(ctx, &bp, in.data(), n, use_layers ? layer_ptrs.data() : nullptr, L, k, start, count,
                                                                   pin.outs.data() + start, out_fmt, 1, t));
@@ -745,11 +783,11 @@ public:
         m_execMs = *std::max_element(kern.begin(), kern.end());
         m_transferMs = *std::max_element(copy.begin(), copy.end());
         std::cout << "\tdecoded " << n << " frames into pinned memory in " << load_sec << " sec (" << io_threads << " file(s) at a time); device set-up + warm-up " << warm_sec << " sec\n";
-        std::cout << "\t" << n << " frames, " << (bil ? opt.animation_filter + " bilateral r=" + std::to_string(opt.radius) : nlm_layers ? "nonlocal + " + std::to_string(L) + " layers" : nlm_layers_t ? "nonlocal + " + std::to_string(L) + " layers, k=" + std::to_string(k) : bil_t ? "bilateral r=" + std::to_string(opt.radius) + (use_layers ? " + " + std::to_string(L) + " layers" : "") + ", k=" + std::to_string(k) : "k=" + std::to_string(k))
+        std::cout << "\t" << n << " frames, " << (bil ? opt.animation_filter + " bilateral r=" + std::to_string(opt.radius) : nlm_layers ? "nonlocal + " + std::to_string(L) + " layers" : nlm_layers_t ? "nonlocal + " + std::to_string(L) + " layers, k=" + std::to_string(k) : bil_t ? std::string(joint ? "joint " : "") + "bilateral r=" + std::to_string(opt.radius) + (use_layers ? " + " + std::to_string(L) + " layers" : "") + ", k=" + std::to_string(k) : "k=" + std::to_string(k))
                   << ", " << G << " device(s): " << sec << " sec, "
                   << (double)n * w * h / 1e6 / sec << " Mpixel/s end to end (host frames in -> host frames out)\n";
         // SaveEXR :1699 / lodepng::encode :1717, straight from the pinned results -- one file per worker thread, like the decode
-        const std::string mode_name = nlm_layers ? "nonlinear-nlm-layers-" : nlm_layers_t ? "nonlinear-nlm-layers-multiframe-" : bil_t ? (use_layers ? "nonlinear-bialteral-layers-multiframe-" : "nonlinear-bialteral-multiframe-") : !bil ? "" : linear ? "linear-bialteral-" : use_layers ? "nonlinear-bialteral-layers-" : "nonlinear-bialteral-";
+        const std::string mode_name = nlm_layers ? "nonlinear-nlm-layers-" : nlm_layers_t ? "nonlinear-nlm-layers-multiframe-" : joint ? (k == 0 && opt.animation_filter == "joint" ? "nonlinear-bialteral-joint-" : "nonlinear-bialteral-joint-multiframe-") : bil_t ? (use_layers ? "nonlinear-bialteral-layers-multiframe-" : "nonlinear-bialteral-multiframe-") : !bil ? "" : linear ? "linear-bialteral-" : use_layers ? "nonlinear-bialteral-layers-" : "nonlinear-bialteral-";
         const auto te0 = std::chrono::steady_clock::now();
         for_each_file(0, n, [&](int i) {
             const std::string name = "output-animation-" + mode_name + fs::path(frameNames[i]).stem().string() + (hdr || half ? ".exr" : ".png");
@@ -815,14 +853,22 @@ static void usage()
         "  --device N                HIP device (default 0)\n"
         "  --modes LIST              comma list of bilateral,layers,linear,nlm,multiframe,overlap (default all, reference order),\n"
         "                            and nlm-layers (not part of all): NLM with its weights taken from the image's RenderElements\n"
-        "                            layers (--nlm-h / --search / --patch apply), output output-nonlinear-nlm-layers.{png,exr}.\n"
-        "                            Layer files: .png (RGBA8) -- or, for the bilateral modes only (layers here, layers and\n"
-        "                            layers-temporal under --animation-filter), .exr: normals, depth, HDR albedo as rendered, read as\n"
+        "                            layers (--nlm-h / --search / --patch apply), output output-nonlinear-nlm-layers.{png,exr};\n"
+        "                            and joint (not part of all): the joint (cross) bilateral, ONE weight per tap from all of the\n"
+        "                            image's layers -- the product of the spatial term and one range term per layer, each layer\n"
+        "                            with its own sigma (--sigma-layers, else --sigma-c for all; --radius / --sigma-s apply),\n"
+        "                            output output-nonlinear-bialteral-joint.{png,exr}.\n"
+        "                            Layer files: .png (RGBA8) -- or, for the bilateral modes only (layers and joint here, layers,\n"
+        "                            layers-temporal, joint and joint-temporal under --animation-filter), .exr: normals, depth, HDR albedo as rendered, read as\n"
         "                            RGBA32F, or as RGBA16F with --half; all layers of a run must have one format; nlm-layers and\n"
         "                            nlm-layers-temporal take .png layers only (their patch distances are integer sums of bytes)\n"
         "  --gpu-only | --cpu-only   run only the GPU modes / only the CPU runs\n"
         "  --radius R                bilateral window radius (default 20 = TEXEL_WINDOW)\n"
         "  --sigma-s S --sigma-c C   bilateral sigmas (default 2.0 0.2)\n"
+        "  --sigma-layers A,B,...    the joint modes: one range sigma per layer, in the sorted order the layer files are found in (the\n"
+        "                            run prints one `layer <file> sigma <value>` line each); a count other than the layer count\n"
+        "                            is refused.  Default: --sigma-c for every layer.  Scale it to the layer's units: normals ~0.3,\n"
+        "                            depth in scene units, HDR albedo ~0.5\n"
         "  --nlm-h H                 NLM filtering parameter (default 0.5)\n"
         "  --search LO,HI --patch LO,HI   half-open NLM ranges (default -7,7 and -3,3; 21x21/7x7 is -10,11 and -3,4)\n"
         "  --temporal-k K            multiframe: frames t-K..t+K of the sorted sequence instead of the reference's list\n"
@@ -842,7 +888,12 @@ static void usage()
         "                            guided by each frame's layers (K = --temporal-k, default 2; --radius / --sigma-s / --sigma-c\n"
         "                            apply; halo frames and their layers from the host, not with --halo rccl), outputs\n"
         "                            output-animation-nonlinear-bialteral-multiframe-* and\n"
-        "                            output-animation-nonlinear-bialteral-layers-multiframe-*\n"
+        "                            output-animation-nonlinear-bialteral-layers-multiframe-*;\n"
+        "                            or joint / joint-temporal: the joint bilateral (one weight from all of a frame's layers,\n"
+        "                            --sigma-layers) of every frame alone (joint ignores --temporal-k) or over the frames t-K..t+K\n"
+        "                            (K = --temporal-k, default 2; the layer rules, frame blocks and halo of layers-temporal),\n"
+        "                            outputs output-animation-nonlinear-bialteral-joint-* and\n"
+        "                            output-animation-nonlinear-bialteral-joint-multiframe-*\n"
         "  --gpus N                  animation mode: split the sequence into N frame blocks, one per device\n"
         "  --halo host|rccl          animation mode with --gpus N: 'host' (default) streams every block plus its K halo frames from host\n"
         "                            memory through the overlapped pipeline; 'rccl' keeps each block resident in its GPU's HBM and\n"
@@ -883,6 +934,13 @@ int main(int argc, char **argv)
         else if (a == "--radius") opt.radius = atoi(next());
         else if (a == "--sigma-s") opt.sigma_s = (float)atof(next());
         else if (a == "--sigma-c") opt.sigma_c = (float)atof(next());
+        else if (a == "--sigma-layers") {
+            opt.sigma_layers.clear();
+            const std::string s = next();
+            size_t pos = 0;
+            while (pos < s.size()) { size_t c = s.find(',', pos); if (c == std::string::npos) c = s.size(); opt.sigma_layers.push_back((float)atof(s.substr(pos, c - pos).c_str())); pos = c + 1; }
+            if (opt.sigma_layers.empty()) { std::cerr << "--sigma-layers needs a comma list of sigmas\n"; usage(); return EXIT_FAILURE; }
+        }
         else if (a == "--nlm-h") opt.nlm_h = (float)atof(next());
         else if (a == "--search") { if (!pair_arg(next(), opt.search_lo, opt.search_hi)) { usage(); return EXIT_FAILURE; } }
         else if (a == "--patch") { if (!pair_arg(next(), opt.patch_lo, opt.patch_hi)) { usage(); return EXIT_FAILURE; } }
@@ -891,8 +949,8 @@ int main(int argc, char **argv)
         else if (a == "--animation-filter") {
             opt.animation_filter = next();
             const std::string &f = opt.animation_filter;
-            if (f != "nlm" && f != "bilateral" && f != "linear" && f != "layers" && f != "nlm-layers" && f != "nlm-layers-temporal" && f != "bilateral-temporal" && f != "layers-temporal") {
-                std::cerr << "unknown --animation-filter " << f << " (nlm, bilateral, linear, layers, nlm-layers, nlm-layers-temporal, bilateral-temporal, layers-temporal)\n"; usage(); return EXIT_FAILURE; }
+            if (f != "nlm" && f != "bilateral" && f != "linear" && f != "layers" && f != "nlm-layers" && f != "nlm-layers-temporal" && f != "bilateral-temporal" && f != "layers-temporal" && f != "joint" && f != "joint-temporal") {
+                std::cerr << "unknown --animation-filter " << f << " (nlm, bilateral, linear, layers, nlm-layers, nlm-layers-temporal, bilateral-temporal, layers-temporal, joint, joint-temporal)\n"; usage(); return EXIT_FAILURE; }
         }
         else if (a == "--half") opt.half = true;
         else if (a == "--gpus") opt.gpus = atoi(next());
@@ -927,7 +985,7 @@ int main(int argc, char **argv)
         if (opt.animation) {
             const std::string &f = opt.animation_filter;
             std::cout << "######\nRunning on GPU (animation, " << (f == "nlm" ? "temporal nonlocal" : f == "linear" ? "linear bialteral" :
-                                                                 f == "layers" ? "nonlinear bialteral + layers" : f == "nlm-layers" ? "nonlocal + layers" : f == "nlm-layers-temporal" ? "nonlocal + layers, multiframe" : f == "bilateral-temporal" ? "nonlinear bialteral, multiframe" : f == "layers-temporal" ? "nonlinear bialteral + layers, multiframe" : "nonlinear bialteral") << ")\n######\n";
+                                                                 f == "layers" ? "nonlinear bialteral + layers" : f == "nlm-layers" ? "nonlocal + layers" : f == "nlm-layers-temporal" ? "nonlocal + layers, multiframe" : f == "bilateral-temporal" ? "nonlinear bialteral, multiframe" : f == "layers-temporal" ? "nonlinear bialteral + layers, multiframe" : f == "joint" ? "joint bialteral" : f == "joint-temporal" ? "joint bialteral, multiframe" : "nonlinear bialteral") << ")\n######\n";
             app.RunAnimation();
             print_time();
             return EXIT_SUCCESS;
@@ -941,6 +999,7 @@ int main(int argc, char **argv)
             if (want("overlap")) { std::cout << "######\nRunning on GPU (multiframe nonlocal + overlapping)\n######\n"; app.RunOnGPU(true, true, true, true, false); print_time(); }
             // (not part of `all`: the reference has no NLM with layers, and the default run writes exactly the reference's files)
             if (listed("nlm-layers")) { std::cout << "######\nRunning on GPU (nonlocal + layers)\n######\n"; app.RunOnGPU(true, true, false, false, true); print_time(); }
+            if (listed("joint")) { std::cout << "######\nRunning on GPU (joint bialteral)\n######\n"; app.RunOnGPU(false, true, false, false, true, true); print_time(); }
         }
         if (opt.run_cpu) {
             for (int threads : opt.cpu_threads) {

@@ -201,6 +201,16 @@ int bilateral_temporal_check(const mid_bilateral_params *p, const char *who, boo
 int bilateral_layers_pair_out(mid_ctx *ctx, const mid_bilateral_params *p, const void *target_layer, const void *neighbour_layer,
                               const void *neighbour_in, mid_weightinfo *W, hipStream_t s);
 
+// mid_bilateral_joint without its checks (the caller has made them), one launch per output frame on `s`: bilateral_joint.hip;
+// used by the frame pipeline (mid_sequence_bilateral_joint), not exported.  layer_sigma: n_layers host floats, or NULL for
+// p->colorSigma in every layer.  bilateral_joint_check: what both entry points check after their own tables -- n_layers in
+// 1..16, a layer table, bilateral_temporal_check, every sigma > 0.
+int bilateral_joint_out(mid_ctx *ctx, const mid_bilateral_params *p, const float *layer_sigma, const void *const *frames,
+                        const uint32_t *const *layers, int n_layers, int n_frames, int k, int first, int count, void *const *out,
+                        int out_fmt, hipStream_t s);
+int bilateral_joint_check(const mid_bilateral_params *p, const char *who, const float *layer_sigma, bool have_layers, int n_layers,
+                          int n_frames, int k);
+
 // ROCTx ranges (csrc/markers.cpp): no-ops unless the process already holds a ROCTx (rocprofv3 --marker-trace preloads one).
 bool markers_active();
 void range_push(const char *name);

@@ -111,6 +111,7 @@ struct Stage {
     const void *const *host_layers;           // n_layers host layers per frame, frame-major; NULL: plain bilateral / no layers
     int n_layers;
     bool temporal = false;                    // nlm_layers / bil over the frames t-k..t+k (mid_sequence_nlm_layers_temporal, mid_sequence_bilateral_temporal), any k
+    const float *joint_sigma = nullptr;       // bil, temporal: the joint bilateral with these n_layers sigmas (mid_sequence_bilateral_joint)
 };
 
 // Outputs [first, first+count) of an n-frame host sequence; frames outside that range are only
@@ -341,8 +342,11 @@ static int run_pipeline(mid_ctx *ctx, const Stage &st, const void *const *host_f
                 const uint32_t *lt[MID_NLM_LAYERS_TEMPORAL_MAX_POINTERS];      // the window's layers, frame-major like tbl
                 for (int f = lo; f <= need; ++f)
                     for (int l = 0; l < n_layers; ++l) lt[(f - lo) * n_layers + l] = (const uint32_t *)layer_slot(f, l);
-                if (int rc = bilateral_temporal_out(ctx, st.bil, tbl, st.host_layers ? lt : nullptr, n_layers, need - lo + 1, k, b0 - lo, bn,
-                                                    (void *const *)o, out_fmt, cs)) return rc;
+                if (st.joint_sigma) {
+                    if (int rc = bilateral_joint_out(ctx, st.bil, st.joint_sigma, tbl, lt, n_layers, need - lo + 1, k, b0 - lo, bn,
+                                                     (void *const *)o, out_fmt, cs)) return rc;
+                } else if (int rc = bilateral_temporal_out(ctx, st.bil, tbl, st.host_layers ? lt : nullptr, n_layers, need - lo + 1, k, b0 - lo, bn,
+                                                           (void *const *)o, out_fmt, cs)) return rc;
             } else for (int i = 0; i < bn; ++i) { // (k = 0: output b0 + i reads ring slot b0 + i and its layers only)
                 const uint32_t *lt[kMaxLayers];
                 for (int l = 0; l < n_layers; ++l) lt[l] = (const uint32_t *)layer_slot(b0 + i, l);
@@ -536,41 +540,61 @@ extern "C" int mid_sequence_nlm_layers_temporal(mid_ctx *ctx, const mid_nlm_para
 }
 
 // The bilateral over neighbouring frames: mid_sequence_nlm_layers_temporal's schedule, layer ring and refusals with
-// bilateral_temporal_out as the compute stage; host_layers == NULL is the plain form.
-extern "C" int mid_sequence_bilateral_temporal(mid_ctx *ctx, const mid_bilateral_params *p, const void *const *host_frames, int n_frames,
-                                               const void *const *host_layers, int n_layers, int k, int first, int count,
-                                               void *const *host_out, int out_format, int overlap, float *timings_ms)
+// bilateral_temporal_out as the compute stage; host_layers == NULL is the plain form.  joint: mid_sequence_bilateral_joint, the
+// same call with bilateral_joint_out as the compute stage and its checks (layer_sigma: n_layers floats or NULL).
+static int sequence_bilateral_temporal(mid_ctx *ctx, const char *who, bool joint, const mid_bilateral_params *p, const float *layer_sigma,
+                                       const void *const *host_frames, int n_frames, const void *const *host_layers, int n_layers, int k,
+                                       int first, int count, void *const *host_out, int out_format, int overlap, float *timings_ms)
 {
     Bind b(ctx, nullptr);
     if (b.rc) return b.rc;
-    if (int rc = refuse_if_recording(ctx->compute, "mid_sequence_bilateral_temporal (four streams, host-side waits)")) return rc;
-    MID_REQUIRE(p && host_frames && host_out, "sequence_bilateral_temporal: NULL argument");
-    MID_REQUIRE(n_frames >= 1 && k >= 0 && 2 * (long)k + 2 <= kMaxFrames, "sequence_bilateral_temporal: bad n_frames=%d k=%d", n_frames, k);
+    if (int rc = refuse_if_recording(ctx->compute, joint ? "mid_sequence_bilateral_joint (four streams, host-side waits)" : "mid_sequence_bilateral_temporal (four streams, host-side waits)")) return rc;
+    MID_REQUIRE(p && host_frames && host_out, "%s: NULL argument", who);
+    MID_REQUIRE(n_frames >= 1 && k >= 0 && 2 * (long)k + 2 <= kMaxFrames, "%s: bad n_frames=%d k=%d", who, n_frames, k);
     MID_REQUIRE(first >= 0 && count >= 1 && (long)first + count <= n_frames,
-                "sequence_bilateral_temporal: bad range first=%d count=%d n_frames=%d", first, count, n_frames);
-    if (int rc = bilateral_temporal_check(p, "sequence_bilateral_temporal", host_layers != nullptr, n_layers, n_frames, k)) return rc;
-    MID_REQUIRE(fmt_known(out_format), "sequence_bilateral_temporal: unknown output format %d", out_format);
+                "%s: bad range first=%d count=%d n_frames=%d", who, first, count, n_frames);
+    if (int rc = joint ? bilateral_joint_check(p, who, layer_sigma, host_layers != nullptr, n_layers, n_frames, k)
+                       : bilateral_temporal_check(p, who, host_layers != nullptr, n_layers, n_frames, k)) return rc;
+    MID_REQUIRE(fmt_known(out_format), "%s: unknown output format %d", who, out_format);
     const int f_lo = first - k < 0 ? 0 : first - k;
     const int f_hi = first + count - 1 + k > n_frames - 1 ? n_frames - 1 : first + count - 1 + k;
     std::vector<const void *> inputs;
     try {
         inputs.reserve((size_t)(f_hi - f_lo + 1) * (n_layers + 1));
     } catch (...) {
-        return set_error(MID_ERR_INVALID, "sequence_bilateral_temporal: no host memory for the alias check");
+        return set_error(MID_ERR_INVALID, "%s: no host memory for the alias check", who);
     }
     for (int f = f_lo; f <= f_hi; ++f) {
-        MID_REQUIRE(host_frames[f], "sequence_bilateral_temporal: frame %d is NULL", f);
+        MID_REQUIRE(host_frames[f], "%s: frame %d is NULL", who, f);
         inputs.push_back(host_frames[f]);
         for (int l = 0; l < n_layers; ++l) {
-            MID_REQUIRE(host_layers[(size_t)f * n_layers + l], "sequence_bilateral_temporal: layer %d of frame %d is NULL", l, f);
+            MID_REQUIRE(host_layers[(size_t)f * n_layers + l], "%s: layer %d of frame %d is NULL", who, l, f);
             inputs.push_back(host_layers[(size_t)f * n_layers + l]);
         }
     }
-    for (int i = 0; i < count; ++i) MID_REQUIRE(host_out[i], "sequence_bilateral_temporal: output %d is NULL", i);
-    if (int rc = check_no_alias("sequence_bilateral_temporal", "an input frame or layer of this call", inputs.data(), (int)inputs.size(),
+    for (int i = 0; i < count; ++i) MID_REQUIRE(host_out[i], "%s: output %d is NULL", who, i);
+    if (int rc = check_no_alias(who, "an input frame or layer of this call", inputs.data(), (int)inputs.size(),
                                 (const void *const *)host_out, count)) return rc;
-    const Stage st{"sequence_bilateral_temporal", p->width, p->height, fmt_frames(p->format), nullptr, p, nullptr, host_layers, n_layers, true};
+    float sigma[kMaxLayers];                  // the joint stage always carries its sigmas: NULL means colorSigma in every layer
+    for (int l = 0; joint && l < n_layers; ++l) sigma[l] = layer_sigma ? layer_sigma[l] : p->colorSigma;
+    const Stage st{who, p->width, p->height, fmt_frames(p->format), nullptr, p, nullptr, host_layers, n_layers, true, joint ? sigma : nullptr};
     return run_pipeline(ctx, st, host_frames, n_frames, k, first, count, host_out, out_format, overlap, timings_ms);
+}
+
+extern "C" int mid_sequence_bilateral_temporal(mid_ctx *ctx, const mid_bilateral_params *p, const void *const *host_frames, int n_frames,
+                                               const void *const *host_layers, int n_layers, int k, int first, int count,
+                                               void *const *host_out, int out_format, int overlap, float *timings_ms)
+{
+    return sequence_bilateral_temporal(ctx, "sequence_bilateral_temporal", false, p, nullptr, host_frames, n_frames, host_layers, n_layers, k,
+                                       first, count, host_out, out_format, overlap, timings_ms);
+}
+
+extern "C" int mid_sequence_bilateral_joint(mid_ctx *ctx, const mid_bilateral_params *p, const float *layer_sigma,
+                                            const void *const *host_frames, int n_frames, const void *const *host_layers, int n_layers,
+                                            int k, int first, int count, void *const *host_out, int out_format, int overlap, float *timings_ms)
+{
+    return sequence_bilateral_temporal(ctx, "sequence_bilateral_joint", true, p, layer_sigma, host_frames, n_frames, host_layers, n_layers, k,
+                                       first, count, host_out, out_format, overlap, timings_ms);
 }
 
 // Device timeline of the context's last mid_sequence_nlm*, mid_sequence_bilateral or mid_sequence_nlm_layers[_temporal] call, read back from the events the call left in the context's

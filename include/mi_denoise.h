@@ -363,6 +363,51 @@ int mid_bilateral_temporal(mid_ctx *ctx, const mid_bilateral_params *p,
                            int n_layers, int n_frames, int k, int first, int count,
                            void *const *out /* host array of `count` device ptrs */, int out_format, void *stream);
 
+/* ---- a4e: the joint (cross) bilateral: one weight from all guide layers ---------------------
+ * mid_bilateral_temporal's layered form runs one complete filter per layer with one colorSigma and adds them.  The joint filter
+ * forms ONE weight per tap, the product of the spatial term and one range term per layer, each layer l with its own sigma_l:
+ *   w(p, f, o) = exp(-0.5 |o|^2 / spatialSigma^2) * prod_l exp(-0.5 |G[t][l](p) - G[f][l](p+o)|^2_rgb / sigma_l^2)
+ *   out_t(p)   = sum_{f, o} w * In_f(p+o)  /  sum_{f, o} w          (magenta (1,0,1,1) where the denominator is 0)
+ * f = max(0,t-k) .. min(n_frames-1,t+k), o = (i, j) with |i|, |j| <= radius, l = 0 .. n_layers-1; out-of-image texels are
+ * vec4(0) in frames and guides; only the centre G[t][l](p) comes from the target frame's layers.  One frame: n_frames = 1, k = 0.
+ * There is no accumulate form: a product of weights cannot be chained through WeightInfo.
+ * Everything else is mid_bilateral_temporal's layered form: frame-major tables of device pointers, the window rule ("only the
+ * frames and layers of [first-k, first+count+k) are read"), out_format, the alias rules, the pointer limit
+ * MID_NLM_LAYERS_TEMPORAL_MAX_POINTERS, texture layout only, radius 1..24, the frames' format and -- through MID_FMT_WITH_GUIDE --
+ * the guide format with the semantics of section a3 (IEEE values, alpha ignored, no clamping, non-finite texels by IEEE
+ * arithmetic), RGBA16F guides 8-byte and RGBA32F guides 16-byte aligned.
+ * layer_sigma: n_layers host floats, read during the call; NULL: every layer uses p->colorSigma.  Each entry must be > 0, as
+ * colorSigma must (which is checked as well, also when it is not used).
+ * Arithmetic: layer l is scaled by sc_l = (float)(sqrt(0.5 * log2 e) / (double)sigma_l); a guide value g enters as the fp32 product
+ * g * sc_l, and the exponent of a tap is one chain of FMAs from the spatial term through layer 0's x, y, z, layer 1's, ...,
+ * followed by one 2^x.  Per neighbour frame the taps are summed on their own and then added to the totals.
+ * Precision: results are within 1e-5 * max(1, |ref|) of the formula in float64 while |g| <= 16 sigma_l for every layer l (as a3).
+ * Bit identities:
+ *   - n_layers == 1 with layer_sigma = {s}, or NULL and colorSigma = s: the bits of mid_bilateral_temporal's layered form with
+ *     that layer and colorSigma = s, at every radius, k, frame, guide and output format;
+ *   - appending all-zero layers (any sigmas) to a layer set leaves the bits, as long as both sets run tiled (below);
+ *   - an RGBA16F guide gives the bits of the RGBA32F guide it widens to, an RGBA32F guide c/255 the bits of the RGBA8 guide c.
+ * Classes: LDS-tiled while n_layers <= 4 and the colour tile (16 B per texel) plus n_layers guide tiles (12 B per texel) of
+ * (64 + 2 radius) x (T + 2 radius) texels fit 160 KB -- T = 16 rows, 32 at radius 10, 8 at radius 20 -- which is every radius
+ * <= 8 at n_layers <= 4, radius <= 9 at 3, radius <= 14 except 10 at 2; with one layer, the radii mid_bilateral_temporal's
+ * layered form runs tiled (<= 17 and 20).  Radii 4, 8, 10 and 20 run on tuned kernels, the others on a run-time-radius one;
+ * everything else -- n_layers > 4 included -- on a per-pixel kernel.
+ * MID_ERR_INVALID before anything is queued, outputs untouched: n_layers outside 1..16 (an empty product would be a plain
+ * Gaussian blur, so 0 is refused rather than given the magenta meaning); a NULL layer table; a sigma that is not > 0; and every
+ * refusal of mid_bilateral_temporal's layered form. */
+int mid_bilateral_joint(mid_ctx *ctx, const mid_bilateral_params *p, const float *layer_sigma /* n_layers host floats, or NULL */,
+                        const void *const *frames /* host array of n_frames device ptrs */,
+                        const uint32_t *const *layers /* host array of n_frames * n_layers device ptrs; cast RGBA16F / RGBA32F layers with MID_FMT_WITH_GUIDE */,
+                        int n_layers, int n_frames, int k, int first, int count,
+                        void *const *out /* host array of `count` device ptrs */, int out_format, void *stream);
+/* mid_sequence_bilateral_temporal (section a8) with mid_bilateral_joint as the compute stage: host frames and host layers in,
+ * host frames out, output t with the bits of mid_bilateral_joint for frame t.  Same ring, same layer ring (4 / 8 / 16 B per
+ * texel), same direct-store rule, same refusals (a call inside a recording among them), same timings_ms and timeline export;
+ * plus the refusals above, which leave host_out and timings_ms untouched. */
+int mid_sequence_bilateral_joint(mid_ctx *ctx, const mid_bilateral_params *p, const float *layer_sigma,
+                                 const void *const *host_frames, int n_frames, const void *const *host_layers, int n_layers,
+                                 int k, int first, int count, void *const *host_out, int out_format, int overlap, float *timings_ms);
+
 /* ---- a5: normalize ----------------------------------------------------------------------
  * One dispatch of shaders/normalize.comp (RecordCommandsOfExecuteAndTransfer(normKernel=true)):
  * out = weightColor / normWeight, or (1,0,1,1) where normWeight == 0; bindings {0: out; 1: W}. */
