@@ -12,7 +12,10 @@
 // Device buffers and events of the frame pipeline (csrc/pipeline.cpp), kept from call to call so that a steady stream of
 // sequences pays for hipMalloc / hipEventCreate once: grown on demand, released by mid_ctx_release_cached and mid_ctx_destroy.
 struct mid_pipe_set { std::vector<void *> p; size_t bytes = 0; };
-struct mid_pipe_last { int n_up = 0, nb = 0, f_lo = 0, first = 0, batch = 1; bool direct = false; };   // event layout of the last mid_sequence_nlm* / mid_sequence_bilateral call
+struct mid_pipe_last {                  // event layout of the last mid_sequence_nlm* / mid_sequence_bilateral call
+    int n_up = 0, nb = 0, f_lo = 0, first = 0, batch = 1; bool direct = false;
+    std::vector<float> up_ms, out_ms;   // its timeline, kept from the first mid_pipe_last_timeline on: every later read gives these numbers
+};
 struct mid_pipe_cache {
     std::mutex mu;                      // one pipeline call per context at a time: the calls share the context's four streams
     mid_pipe_set ring, out;             // mid_sequence_nlm* / mid_sequence_bilateral: uploaded frames (2k + 4), output slots (4)

@@ -607,22 +607,31 @@ extern "C" int mid_pipe_last_timeline(mid_ctx *ctx, int cap, float *upload_ms, i
     MID_REQUIRE(upload_ms && n_uploads && first_upload_frame && output_ms && n_outputs && first_output_frame && cap >= 0,
                 "pipe_last_timeline: bad argument");
     std::lock_guard<std::mutex> pipe_lock(ctx->pipe.mu);
-    const mid_pipe_last &L = ctx->pipe.last;
+    mid_pipe_last &L = ctx->pipe.last;
     MID_REQUIRE(L.n_up > 0, "pipe_last_timeline: no mid_sequence_nlm* or mid_sequence_bilateral call has completed on this context");
     MID_REQUIRE(cap >= L.n_up && cap >= L.nb, "pipe_last_timeline: cap=%d, need %d uploads and %d outputs", cap, L.n_up, L.nb);
     MID_REQUIRE(ctx->pipe.ev.size() >= 2 * (size_t)L.n_up + 4 * (size_t)L.nb, "pipe_last_timeline: the event cache was released");
-    hipEvent_t *up0 = ctx->pipe.ev.data(), *up1 = up0 + L.n_up, *c0 = up1 + L.n_up, *c1 = c0 + L.nb, *d0 = c1 + L.nb, *d1 = d0 + L.nb;
-    for (int i = 0; i < L.n_up; ++i) {
-        MID_HIP(hipEventElapsedTime(&upload_ms[2 * i], up0[0], up0[i]));
-        MID_HIP(hipEventElapsedTime(&upload_ms[2 * i + 1], up0[0], up1[i]));
+    // The events are read back once per call of the pipeline.  hipEventElapsedTime of the same two events is not the same float
+    // every time it is asked (the runtime may convert the timestamps anew, a nanosecond apart, after work on other streams), and
+    // "the timeline of the last call" must not change while no pipeline call has run: a refused call leaves it alone.
+    if (L.up_ms.empty()) {
+        std::vector<float> up(2 * (size_t)L.n_up), out(4 * (size_t)L.nb);
+        hipEvent_t *up0 = ctx->pipe.ev.data(), *up1 = up0 + L.n_up, *c0 = up1 + L.n_up, *c1 = c0 + L.nb, *d0 = c1 + L.nb, *d1 = d0 + L.nb;
+        for (int i = 0; i < L.n_up; ++i) {
+            MID_HIP(hipEventElapsedTime(&up[2 * i], up0[0], up0[i]));
+            MID_HIP(hipEventElapsedTime(&up[2 * i + 1], up0[0], up1[i]));
+        }
+        for (int i = 0; i < L.nb; ++i) {
+            MID_HIP(hipEventElapsedTime(&out[4 * i], up0[0], c0[i]));
+            MID_HIP(hipEventElapsedTime(&out[4 * i + 1], up0[0], c1[i]));
+            // direct (kernel-stored) outputs have no download stage: reported as an empty interval at the end of the launch
+            MID_HIP(hipEventElapsedTime(&out[4 * i + 2], up0[0], L.direct ? c1[i] : d0[i]));
+            MID_HIP(hipEventElapsedTime(&out[4 * i + 3], up0[0], L.direct ? c1[i] : d1[i]));
+        }
+        L.up_ms.swap(up); L.out_ms.swap(out);
     }
-    for (int i = 0; i < L.nb; ++i) {
-        MID_HIP(hipEventElapsedTime(&output_ms[4 * i], up0[0], c0[i]));
-        MID_HIP(hipEventElapsedTime(&output_ms[4 * i + 1], up0[0], c1[i]));
-        // direct (kernel-stored) outputs have no download stage: reported as an empty interval at the end of the launch
-        MID_HIP(hipEventElapsedTime(&output_ms[4 * i + 2], up0[0], L.direct ? c1[i] : d0[i]));
-        MID_HIP(hipEventElapsedTime(&output_ms[4 * i + 3], up0[0], L.direct ? c1[i] : d1[i]));
-    }
+    memcpy(upload_ms, L.up_ms.data(), L.up_ms.size() * sizeof(float));
+    memcpy(output_ms, L.out_ms.data(), L.out_ms.size() * sizeof(float));
     *n_uploads = L.n_up; *first_upload_frame = L.f_lo; *n_outputs = L.nb; *first_output_frame = L.first;
     return MID_OK;
 }

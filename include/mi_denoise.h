@@ -536,6 +536,8 @@ int mid_sequence_bilateral_temporal(mid_ctx *ctx, const mid_bilateral_params *p,
  * start, kernel end, download start, download end of output frame first_output_frame + j (output j runs on kernel stream
  * j & 1; an output stored by the kernel reports an empty download interval at its kernel's end; the upload interval of a
  * layer-guided mid_sequence_bilateral frame spans the frame and its layers).  cap = rows either array can hold.  Valid until the next pipeline call or mid_ctx_release_cached on the context.
+ * The events are read once, by the first call after a pipeline call; until the next pipeline call completes every call returns those
+ * same numbers, whatever else ran on the context in between (a refused pipeline call does not replace them).
  * Stands where the reference prints its per-submit timestamps (src/main.cpp:1095-1101). */
 int mid_pipe_last_timeline(mid_ctx *ctx, int cap, float *upload_ms /* cap x 2 */, int *n_uploads, int *first_upload_frame,
                            float *output_ms /* cap x 4 */, int *n_outputs, int *first_output_frame);

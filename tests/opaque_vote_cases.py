@@ -1,4 +1,5 @@
-"""Cases for the opaque-tile vote of the tuned kernels (tests/test_opaque_vote_cases.py on the CPU, tests/test_gpu_opaque_vote.py on the GPU).
+"""Cases for the opaque-tile vote of the tuned kernels (tests/test_opaque_vote_cases.py on the CPU, tests/test_gpu_opaque_vote.py and
+tests/test_gpu_bilateral_joint_vote.py on the GPU).
 
 Every tuned kernel stages a colour tile in LDS with fill_tile, and-s "every texel this thread stored has alpha == 1.0f" into a flag,
 lets the workgroup vote on it and, on a yes, runs a tap loop without the alpha accumulator (bilateral: acc.w = accw; NLM:
@@ -9,6 +10,7 @@ texel's image positions from it, builds flat frames in which a far halo tap stil
 Tile geometry (origin relative to the tile's first output pixel; LW x LH slots; threads that fill it):
 
   bilateral, radius R, shape BilShape<R, P, NW>   origin (-R, -R)            LW = 64 + 2R        LH = NW*P + 2R       NW*64 threads
+  joint bilateral (bilateral_joint.hip)           the bilateral's colour tile, with up to four guide tiles of three float planes beside it
   NLM strip, search [SLO,SHI), patch [PLO,PHI)    origin (PLO+SLO, PLO+SLO)  LW = 64 + SW - 1    LH = 32 + PW-1 + SW-1  256 (HALF: 512)
   layer-guided NLM (colour tile: centres only)    origin (PLO+SLO, SLO)      LW = 64 + SW - 1    LHC = 64 + SW - 1    kLNW*64 = 512
 
@@ -271,6 +273,106 @@ def placement(n, k, f_odd, t):
     if f_odd == t:
         return "target"
     return "first" if f_odd == lo else "last" if f_odd == hi else "middle"
+
+
+# ---- the joint (cross) bilateral (bilateral_joint.hip) -------------------------------------------------------------------------------
+# Its colour tile is the bilateral's, bil_tile(R); the tuned kernels hold one opaque tap loop per layer count they can keep in LDS.
+# The vote goes through the first word of the guide tiles -- layer 0's x of slot 0, which thread 0 keeps in a register (`held`) and
+# stores once the vote is read -- so "slot 0" also proves that word: a wrong value there changes the weight of the one tap of output
+# (X0, Y0) that reads the odd texel (test_opaque_vote_cases.py asserts the size of that change on the reference).
+JOINT_LDS_MAX = 160 * 1024                                 # bytes of LDS a workgroup may have on the MI355X
+JOINT_TILED_LAYERS = 4                                     # kJointTiledLayers
+BIL_RT_SHAPE = (2, 8)                                      # kBilRtP, kBilRtNW: the run-time-radius kernels' 16-row tile
+JOINT_LAYERS = {4: (1, 2, 3, 4), 8: (1, 2, 3, 4), 10: (1,), 20: (1,)}      # R: the layer counts its tuned kernel runs tiled
+JOINT_SEQUENCES = {4: (0, 1, 2, 3, 4), 8: (0, 1, 2, 3, 4), 10: (0, 2), 20: (0,)}   # R: indices into SEQUENCES, RGBA32F frames
+JOINT_U8_SEQUENCES = {4: (0,), 8: (0,), 10: (), 20: ()}                    # the same, RGBA8 frames
+JOINT_SIGMAS = (0.1, 0.15, 0.2, 0.12)                      # one per layer
+
+
+def joint_lds_bytes(radius, n_layers):
+    """bilateral_joint.hip's joint_lds_bytes at the radius's tile: a float4 colour tile and n_layers guide tiles of three floats."""
+    P, NW = BIL_SHAPES.get(radius, BIL_RT_SHAPE)
+    return (64 + 2 * radius) * (NW * P + 2 * radius) * (16 + 12 * n_layers)
+
+
+def joint_class(radius, n_layers, lds_max=JOINT_LDS_MAX):
+    """'tuned', 'run-time radius' or 'per pixel': dispatch_joint / launch_joint_tiled / joint_tiled restated.  One layer: the LDS test of
+    the layered form's two float4 tiles; a tuned radius never falls back to the run-time-radius kernel."""
+    P, NW = BIL_SHAPES.get(radius, BIL_RT_SHAPE)
+    texels = (64 + 2 * radius) * (NW * P + 2 * radius)
+    fits = n_layers <= JOINT_TILED_LAYERS and (texels * 32 if n_layers == 1 else joint_lds_bytes(radius, n_layers)) <= lds_max
+    if radius in BIL_SHAPES:
+        max_l = max(l for l in range(1, JOINT_TILED_LAYERS + 1) if l == 1 or joint_lds_bytes(radius, l) <= 160 * 1024)   # joint_max_layers
+        return "tuned" if fits and n_layers <= max_l else "per pixel"
+    return "run-time radius" if fits else "per pixel"
+
+
+def odd_value(dtype):
+    """The odd texel's alpha as the kernels decode it."""
+    return float(decode(np.array([ODD_ALPHA[np.dtype(dtype)]], dtype))[0])
+
+
+def joint_layers(t, n=5):
+    """n lists of four RGBA8 guide layers for tile t: base_frames' two, whose draws stay what they are, and two more flat guides from
+    a generator of their own."""
+    _, layers = base_frames(t, np.uint8, n)
+    rng = np.random.default_rng(zlib.crc32((t.name + ": joint layers 2 and 3").encode()))
+    h, w = frame_size(t)
+    return [ls + [flat_guide(rng, h, w) for _ in range(2)] for ls in layers]
+
+
+_JOINT_REFS = {}
+
+
+def joint_refs(R, L):
+    """{(frame dtype, sequence index): (positions, [per output t: {position name: ref [h, w, 4] float64}])} of np_bilateral_joint for
+    the joint cases of radius R with L layers: RGBA32F frames in JOINT_SEQUENCES[R], RGBA8 frames in JOINT_U8_SEQUENCES[R], guides
+    joint_layers(bil_tile(R))[f][:L] with JOINT_SIGMAS[:L] (RGBA8; as float32 c / 255 they decode to the same texels).
+
+    The weights depend on neither the frames nor their alpha, and every sequence draws on the same five frames, so each pair
+    (output t, neighbour f) is worked out ONCE by np_bilateral_joint.pair_sums -- the loop bilateral_joint itself is made of -- on an
+    image that carries, beside frame f's rgb in both formats, one alpha plane per case in which f is the odd frame."""
+    if (R, L) in _JOINT_REFS:
+        return _JOINT_REFS[(R, L)]
+    import np_bilateral_joint as chk
+    t = bil_tile(R)
+    h, w = frame_size(t)
+    f32, u8 = np.dtype(np.float32), np.dtype(np.uint8)
+    rgb = {dt: [decode(f)[..., :3] for f in base_frames(t, dt)[0]] for dt in (f32, u8)}
+    layers = [ls[:L] for ls in joint_layers(t)]
+    runs = [(f32, i) for i in JOINT_SEQUENCES[R]] + [(u8, i) for i in JOINT_U8_SEQUENCES[R]]
+    col = {dt: slice(3 * c, 3 * c + 3) for c, dt in enumerate((f32, u8))}
+    planes = [{} for _ in range(5)]                                      # per frame: (dtype, position name) -> channel
+    for dt, i in runs:
+        for p in seq_positions(t, i):
+            planes[SEQUENCES[i][2]].setdefault((dt, p.name), (p, 6 + len(planes[SEQUENCES[i][2]])))
+    pairs = {}
+
+    def pair(t_out, f):
+        if (t_out, f) not in pairs:
+            img = np.ones((h, w, 6 + len(planes[f])), np.float32)
+            img[..., col[f32]], img[..., col[u8]] = rgb[f32][f], rgb[u8][f]
+            for (dt, _), (p, c) in planes[f].items():
+                img[p.xy[1], p.xy[0], c] = odd_value(dt)
+            pairs[(t_out, f)] = chk.pair_sums(img, layers[t_out], layers[f], R, sigma_s(R), JOINT_SIGMAS[:L])
+        return pairs[(t_out, f)]
+    out = {}
+    for dt, i in runs:
+        n, k, f_odd = SEQUENCES[i]
+        group = seq_positions(t, i)
+        refs = []
+        for t_out in range(n):
+            win = range(max(0, t_out - k), min(n - 1, t_out + k) + 1)
+            den = sum(pair(t_out, f)[1] for f in win)
+            colour = sum(pair(t_out, f)[0][..., col[dt]] for f in win)
+            refs.append({})
+            for p in group:
+                # a frame without an odd texel adds its weights to the alpha sum (alpha 1.0 under every tap), the odd frame its plane's sums
+                alpha = sum(pair(t_out, f)[0][..., planes[f][(dt, p.name)][1]] if f == f_odd else pair(t_out, f)[1] for f in win)
+                refs[-1][p.name] = np.concatenate([colour, alpha[..., None]], -1) / den[..., None]
+        out[(dt, i)] = (group, refs)
+    _JOINT_REFS[(R, L)] = out
+    return out
 
 
 # ---- the NLM dispatcher's arithmetic (nlm.hip: dispatch_ranges, nlm_small.hip: nlm_dispatch_small / tail_split) ---------------------

@@ -15,6 +15,7 @@ import pytest
 import torch
 
 import f64_checker
+import np_bilateral_joint
 import np_bilateral_temporal as nbt
 import np_nlm_layers
 import np_nlm_layers_temporal as nlt
@@ -53,6 +54,26 @@ def test_bilateral_shapes_are_the_sources():
         assert re.search(r"constexpr int TILE_W = 64, TILE_H = NW \* P;", k), name
         assert re.search(r"constexpr int LW = TILE_W \+ 2 \* R, LH = TILE_H \+ 2 \* R;", k), name
         assert re.search(r"X0 - R, Y0 - R, tid, NW \* 64,[^;]*&mine\)", k), name
+
+
+def test_joint_bilateral_shapes_are_the_sources():
+    """bilateral_joint.hip takes its shapes from bilateral_shapes.hpp (no list of its own) and fills LW x LH from (X0 - R, Y0 - R) with
+    NW * 64 threads in trips of four texels: the colour tile and layer 0 in one loop, with the vote flag and the held word, further
+    layers into the planes behind."""
+    k = _src("bilateral_joint.hip")
+    assert '#include "bilateral_shapes.hpp"' in k and "BilShape<" not in k
+    assert re.search(r"return bil_for_radius\(radius,\s*\[&\]\(auto sh\) \{ return launch_joint_tiled<decltype\(sh\)::R, decltype\(sh\)::P, decltype\(sh\)::NW>\(ctx, a, s\); \},", k)
+    assert re.search(r"template <int R, int P, int NW, int MAXL>\s*__global__ __launch_bounds__\(NW \* 64\) void bilateral_joint_kernel\(", k)
+    assert re.search(r"constexpr int TILE_W = 64, TILE_H = NW \* P;", k)
+    assert re.search(r"constexpr int LW = TILE_W \+ 2 \* R, LH = TILE_H \+ 2 \* R, N = LW \* LH;", k)
+    assert re.search(r"fill_colour_and_planes_any\(img_t, gde_t, LW, LH, nb_frame\(a, f\), a\.fmt, nb_layer\(a, f, 0\), a\.gfmt, w, h, X0 - R, Y0 - R, tid, NW \* 64,"
+                     r"\s*a\.scl\[0\], &mine, &held\);", k)
+    assert re.search(r"fill_planes_any\(gde_t \+ \(size_t\)3 \* l \* N, LW, LH, nb_layer\(a, f, l\), a\.gfmt, w, h, X0 - R, Y0 - R, tid, NW \* 64, a\.scl\[l\]\);", k)
+    assert len(re.findall(r"for \(int t0 = tid; t0 < n; t0 \+= 4 \* nthreads\)", k)) == 2, "both fills: four texels per thread and trip"
+    assert re.search(r"if \(held && t == 0\) \*held = v\[j\]\.x \* sc; else g\[t\] = v\[j\]\.x \* sc;", k), "slot 0 of layer 0's x plane carries the vote"
+    assert int(re.search(r"constexpr int kJointTiledLayers = (\d+);", k).group(1)) == ov.JOINT_TILED_LAYERS
+    assert re.search(r"constexpr int kBilRtP = (\d+), kBilRtNW = (\d+);", _src("bilateral_shapes.hpp")).groups() == tuple(str(x) for x in ov.BIL_RT_SHAPE)
+    assert {R: tuple(L for L in range(1, 5) if ov.joint_class(R, L) == "tuned") for R in ov.BIL_SHAPES} == ov.JOINT_LAYERS
 
 
 def test_nlm_layer_shapes_are_the_sources():
@@ -382,3 +403,126 @@ def test_check_alpha_refuses_a_blind_case():
     ref = (num / den[..., None]).numpy()
     with pytest.raises(AssertionError, match="blind case"):
         ov.check_alpha(ref, ref, [p.xy], t.reach, ov.BIL_TOL)
+
+
+# ---- the joint (cross) bilateral ------------------------------------------------------------------------------------------------------
+# The references here are the ones tests/test_gpu_bilateral_joint_vote.py compares the kernels with (opaque_vote_cases.joint_refs, cached):
+# RGBA8 frames carry the hardest odd texel, alpha 0; the float frames' -3 moves alpha four times as far, so their cases are checked a
+# second time with the deviation divided by four, which is what an alpha-0 texel would give.
+JOINT_CASES = [(R, L) for R in ov.JOINT_LAYERS for L in ov.JOINT_LAYERS[R]]
+
+
+def _joint_seen(R, L):
+    """(dtype, sequence, position, output t, placement, ref) of every comparison of a joint case in which the output sees the odd frame."""
+    for (dt, i), (group, refs) in ov.joint_refs(R, L).items():
+        n, k, f_odd = ov.SEQUENCES[i]
+        for t_out in range(n):
+            place = ov.placement(n, k, f_odd, t_out)
+            for p in group:
+                yield dt, i, p, t_out, place, refs[t_out][p.name]
+
+
+@pytest.mark.parametrize("R,L", JOINT_CASES)
+def test_joint_bilateral_cases_are_observable(R, L):
+    t = ov.bil_tile(R)
+    worst, placements = np.inf, set()
+    for dt, i, p, t_out, place, ref in _joint_seen(R, L):
+        if place == "unseen":
+            assert np.all(np.abs(ref[..., 3][ov.interior_mask(*ref.shape[:2], t.reach)] - 1.0) <= 1e-12)
+            continue
+        placements.add(place)
+        dev = ov.check_alpha(ref, ref, [p.xy], t.reach, ov.BIL_TOL)[1]
+        if dt == np.float32:
+            zero = ref.copy()
+            zero[..., 3] = 1.0 - (1.0 - ref[..., 3]) / (1.0 - ov.odd_value(dt))
+            dev = ov.check_alpha(zero, zero, [p.xy], t.reach, ov.BIL_TOL)[1]
+        worst = min(worst, dev)
+    assert placements == ({"first", "last", "target"} | ({"middle"} if R != 20 else set()))
+    print(f"joint bilateral r={R} L={L}: smallest window deviation {worst:.3g} (odd alpha 0)")
+
+
+def test_joint_reference_pairs_add_up_to_the_checkers_outputs():
+    """joint_refs adds np_bilateral_joint.pair_sums per (output, neighbour); bilateral_joint is the reference: the same numbers, for
+    the rgb of the frames as drawn and for a case's alpha, in a five-frame sequence at k = 2 and an RGBA8 one at k = 1."""
+    R, L = 4, 4
+    t = ov.bil_tile(R)
+    layers = [ls[:L] for ls in ov.joint_layers(t)]
+    for dt, i in ((np.dtype(np.float32), 2), (np.dtype(np.uint8), 0)):
+        n, k, f_odd = ov.SEQUENCES[i]
+        group, refs = ov.joint_refs(R, L)[(dt, i)]
+        frames = ov.base_frames(t, dt)[0][:n]
+        p = group[2]
+        want = np_bilateral_joint.bilateral_joint([ov.with_odd(f, p.xy) if j == f_odd else f for j, f in enumerate(frames)], layers[:n],
+                                                  ov.JOINT_SIGMAS[:L], k, R, ov.sigma_s(R))
+        for t_out in range(n):
+            assert np.max(np.abs(refs[t_out][p.name] - want[t_out])) < 1e-13, (dt, t_out)
+    assert len({id(ls[l]) for ls in layers for l in range(L)}) == 5 * L
+    two = ov.base_frames(t, np.uint8)[1]
+    assert all(np.array_equal(a, b) for ls, bs in zip(ov.joint_layers(t), two) for a, b in zip(ls, bs)), "layers 0 and 1 are base_frames' draws"
+
+
+@pytest.mark.parametrize("R,L", JOINT_CASES)
+def test_joint_bilateral_held_word_is_observable(R, L):
+    """The odd texel at slot 0 is read by ONE output of the interior tile, (X0, Y0), through ONE tap, whose guide value in layer 0's x
+    plane is the word the vote went through.  Were that word anything but the texel's value -- 0, or the vote's own 0 / 1 as bits --
+    the tap's weight would change and with it the alpha of (X0, Y0): by at least 5 x tol, so that check_alpha's window comparison
+    fails.  Worked out by the checker on the (2R+1)^2 window of that output alone, which is all the output reads."""
+    t = ov.bil_tile(R)
+    _, _, X0, Y0 = ov.interior_tile(t)
+    crop = (slice(Y0 - R, Y0 + R + 1), slice(X0 - R, X0 + R + 1))
+    layers = [[g[crop] for g in ls[:L]] for ls in ov.joint_layers(t)]
+    smallest = np.inf
+    for i in ov.JOINT_SEQUENCES[R]:
+        n, k, f_odd = ov.SEQUENCES[i]
+        p = ov.seq_positions(t, i)[0]
+        assert p.name == "slot 0" and p.xy == (X0 - R, Y0 - R)
+        alpha = [np.ones((2 * R + 1, 2 * R + 1, 4), np.float32) for _ in range(n)]
+        alpha[f_odd][0, 0, :] = 0.0
+        wrong = [[g.copy() for g in ls] for ls in layers[:n]]
+        assert wrong[f_odd][0][0, 0, 0] >= 126
+        wrong[f_odd][0][0, 0, 0] = 0
+        args = (ov.JOINT_SIGMAS[:L], k, R, ov.sigma_s(R))
+        drawn, zeroed = np_bilateral_joint.bilateral_joint(alpha, layers[:n], *args), np_bilateral_joint.bilateral_joint(alpha, wrong, *args)
+        for t_out in range(n):
+            if ov.placement(n, k, f_odd, t_out) in ("unseen", "target"):      # (the target's own centre comes from global memory, not from the tile)
+                continue
+            full = ov.joint_refs(R, L)[(np.dtype(np.float32), i)][1][t_out][p.name][Y0, X0, 3]
+            assert abs((1.0 - drawn[t_out][R, R, 3]) * (1.0 - ov.odd_value(np.float32)) - (1.0 - full)) < 1e-12, "the window is the whole of what (X0, Y0) reads"
+            smallest = min(smallest, abs(drawn[t_out][R, R, 3] - zeroed[t_out][R, R, 3]))
+    assert smallest >= 5 * ov.BIL_TOL, f"a wrong held word moves alpha at (X0, Y0) by {smallest:.3g} only"
+    print(f"joint bilateral r={R} L={L}: a zero in the held word moves alpha at (X0, Y0) by at least {smallest:.3g}")
+
+
+@pytest.mark.parametrize("R,L", [(4, 4), (8, 2), (10, 1), (20, 1)])
+def test_check_alpha_raises_on_a_joint_tile_that_voted_opaque(R, L):
+    """The interior tile runs the opaque tap loop although its colour tile holds the odd texel: acc.w = accw for that neighbour, so
+    every output of the tile has alpha exactly 1.0; every other tile is right."""
+    t = ov.bil_tile(R)
+    hit = 0
+    for dt, i, p, t_out, place, ref in _joint_seen(R, L):
+        if i != 0 or place == "unseen" or p.name not in ("slot 0", "slot n-1"):
+            continue
+        bad = ref.copy()
+        bad[_tile_block(t, ref[..., 3]) + (3,)] = 1.0
+        with pytest.raises(AssertionError, match="alpha off by"):
+            ov.check_alpha(bad, ref, [p.xy], t.reach, ov.BIL_TOL)
+        hit += 1
+    assert hit == (12 if ov.JOINT_U8_SEQUENCES[R] else 6)
+
+
+@pytest.mark.parametrize("R,L,seq", [(4, 4, (3, 2, 2)), (8, 2, (3, 2, 2)), (8, 4, (5, 2, 2)), (10, 1, (5, 2, 2))])
+def test_check_alpha_raises_on_a_joint_vote_left_over_from_the_previous_neighbour(R, L, seq):
+    """The odd frame follows an opaque neighbour in the window (placement 'last' or 'middle').  A vote kept from that neighbour runs the
+    odd frame's taps in the opaque form: its alpha sum is its weight sum, and the tile's alpha, sum over the window of both, is 1.0."""
+    t = ov.bil_tile(R)
+    i = ov.SEQUENCES.index(seq)
+    hit = 0
+    for dt, j, p, t_out, place, ref in _joint_seen(R, L):
+        if j != i or place not in ("last", "middle") or p.name not in ("slot 0", "slot n-1"):
+            continue
+        bad = ref.copy()
+        bad[_tile_block(t, ref[..., 3]) + (3,)] = 1.0
+        with pytest.raises(AssertionError, match="alpha off by"):
+            ov.check_alpha(bad, ref, [p.xy], t.reach, ov.BIL_TOL)
+        hit += 1
+    assert hit == 2 * sum(ov.placement(*seq, t_out) in ("last", "middle") for t_out in range(seq[0]))
