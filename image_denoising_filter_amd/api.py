@@ -105,6 +105,7 @@ def _fmt_of(a):
 
 
 _GUIDE_DTYPES = (np.uint8, np.float16, np.float32)
+_OUT_FMT = {np.dtype(np.uint8): FMT_RGBA8, np.dtype(np.float16): FMT_RGBA16F, np.dtype(np.float32): FMT_RGBA32F}
 
 
 def _guide_fmt(fmt, layers, who):
@@ -496,23 +497,65 @@ class Context:
                                       out.ctypes.data, 1 if overlap else 0, t), "mid_nlm_multiframe")
         return out, tuple(t)
 
+    def _sequence_call(self, entry, where, prm, hin, hout, count, asked, overlap, layers=(), plain=False, window=(), out_dtype=(), sigmas=()):
+        """What every sequence_*_pinned method does: check the buffer counts, build the pointer tables and make the C call
+        entry(ctx, prm, [layer_sigma], frames, n, [layers, n_layers], [k, first, count], outputs, [out_format], overlap, timings).
+        layers: () or (hlayers, n_layers), hlayers None being the form without layers where the method has one (plain);
+        window: () or (k, first, count); out_dtype: () or (the outputs' dtype or None,); sigmas: () or (n_layers sigmas or None,);
+        asked: how the method's ValueError names the outputs it was asked for."""
+        n = len(hin)
+        if len(hout) < count:
+            raise ValueError(f"{asked}, {len(hout)} output buffers given")
+        if layers and not (plain and layers[0] is None):
+            hlayers, n_layers = layers
+            if len(hlayers) != n * n_layers:
+                raise ValueError(f"{n} frames x {n_layers} layers, {len(hlayers)} layer pointers given")
+            layers = ((ctypes.c_void_p * max(len(hlayers), 1))(*hlayers), n_layers)
+        out_fmt = [_OUT_FMT[_out_dtype(False, dt)] for dt in out_dtype]
+        pre = [_layer_sigmas(sg, layers[1], where[len("mid_"):]) for sg in sigmas]
+        t = (ctypes.c_float * 3)()
+        # (the output table holds at least one entry, so that count = 0 still reaches the library's refusal)
+        _check(getattr(lib, entry)(self.handle, ctypes.byref(prm), *pre, (ctypes.c_void_p * n)(*hin), n, *layers, *window,
+                                   (ctypes.c_void_p * max(count, 1))(*hout[:max(count, 0)]), *out_fmt, 1 if overlap else 0, t), where)
+        return tuple(t)
+
+    def _sequence_host(self, who, call, frames, layers, dtypes, first, count, pinned, pinned_out, out_dtype, plain=False, inside=False):
+        """What every host wrapper of the frame pipeline does: check the frames and the layers (dtypes: what the filter takes;
+        plain: layers may be None, the form without layers), pin them and the outputs or borrow the NumPy arrays, make
+        call(hin, hout, w, h, fmt, hlayers, n_layers, count) -- the method's own *_pinned -- and return (outputs, timings).
+        inside: refuse an output range that leaves the sequence here (sequence_nlm) instead of in the library."""
+        frames = _same_frames(frames, who)
+        n = len(frames)
+        count = n - first if count is None else count
+        if inside and not (0 <= first and count >= 1 and first + count <= n):
+            raise ValueError(f"outputs [{first}, {first + count}) are not inside the {n} frames given")
+        h, w = frames[0].shape[:2]
+        n_layers, flat = (0, None) if plain and layers is None else _flat_layers(layers, n, h, w, who, dtypes)
+        out_shape = (h, w, 4)
+        hin = hlay = hout = None
+        try:
+            hin = PinnedFrames(self, frames) if pinned else None
+            hlay = PinnedFrames(self, flat) if pinned and flat else None
+            hout = PinnedFrames(self, max(count, 1), w * h * 4 * out_dtype.itemsize) if pinned_out else None
+            outs = None if pinned_out else [np.empty(out_shape, out_dtype) for _ in range(max(count, 0))]
+            lptr = None if flat is None else (hlay.ptrs if hlay is not None else [lyr.ctypes.data for lyr in flat])
+            t = call(hin.ptrs if pinned else [f.ctypes.data for f in frames], hout.ptrs if pinned_out else [o.ctypes.data for o in outs],
+                     w, h, _guide_fmt(_fmt_of(frames[0]), flat or [], who), lptr, n_layers, count)
+            return (outs if outs is not None else [hout.array(i, out_shape, out_dtype) for i in range(count)]), t
+        finally:
+            for b in (hin, hlay, hout):
+                if b is not None:
+                    b.free()
+
     def sequence_nlm_pinned(self, hin, hout, w, h, fmt, k=2, first=0, count=None, overlap=True, hparam=0.5,
                             search=(-7, 7), patch=(-3, 3), out_u8=False, out_dtype=None):
         """mid_sequence_nlm_range[_u8|_f16] on host pointers the caller already holds (PinnedFrames.ptrs): nothing but the C call,
         so a clock around it measures what a C caller sees.  out_dtype=np.float16 selects the RGBA16F outputs.
         Returns (wall_ms of the whole call, kernel_ms, copy_ms)."""
-        n = len(hin)
-        count = n - first if count is None else count
-        if len(hout) < count:
-            raise ValueError(f"{count} outputs asked for, {len(hout)} output buffers given")
-        prm = NlmParams(w, h, hparam, search[0], search[1], patch[0], patch[1], fmt)
-        t = (ctypes.c_float * 3)()
-        out_dtype = _out_dtype(out_u8, out_dtype)
-        entry = {np.dtype(np.uint8): lib.mid_sequence_nlm_range_u8, np.dtype(np.float16): lib.mid_sequence_nlm_range_f16,
-                 np.dtype(np.float32): lib.mid_sequence_nlm_range}[out_dtype]
-        _check(entry(self.handle, ctypes.byref(prm), (ctypes.c_void_p * n)(*hin), n, k, first, count,
-                     (ctypes.c_void_p * count)(*hout[:count]), 1 if overlap else 0, t), "mid_sequence_nlm_range")
-        return tuple(t)
+        count = len(hin) - first if count is None else count
+        entry = "mid_sequence_nlm_range" + {FMT_RGBA8: "_u8", FMT_RGBA16F: "_f16", FMT_RGBA32F: ""}[_OUT_FMT[_out_dtype(out_u8, out_dtype)]]
+        return self._sequence_call(entry, "mid_sequence_nlm_range", NlmParams(w, h, hparam, search[0], search[1], patch[0], patch[1], fmt),
+                                   hin, hout, count, f"{count} outputs asked for", overlap, window=(k, first, count))
 
     def pipe_last_timeline(self, cap=4096):
         """mid_pipe_last_timeline: the device timeline of this context's last mid_sequence_nlm* / mid_sequence_bilateral call,
@@ -535,26 +578,10 @@ class Context:
         pinned / pinned_out = False: the NumPy arrays themselves (pageable memory) are the sources / destinations, which
         the library moves through its bounce buffers (csrc/hostcopy.cpp).
         Returns (outputs for frames first..first+count-1, (wall_ms, kernel_ms, copy_ms))."""
-        frames = _same_frames(frames, "sequence_nlm")
-        n = len(frames)
-        count = n - first if count is None else count
-        if not (0 <= first and count >= 1 and first + count <= n):
-            raise ValueError(f"outputs [{first}, {first + count}) are not inside the {n} frames given")
-        h, w = frames[0].shape[:2]
-        out_shape, out_dtype = (h, w, 4), _out_dtype(out_u8, out_dtype)
-        hin = PinnedFrames(self, frames) if pinned else None
-        hout = PinnedFrames(self, count, w * h * 4 * out_dtype.itemsize) if pinned_out else None
-        outs = None if pinned_out else [np.empty(out_shape, out_dtype) for _ in range(count)]
-        try:
-            t = self.sequence_nlm_pinned(hin.ptrs if pinned else [f.ctypes.data for f in frames],
-                                         hout.ptrs if pinned_out else [o.ctypes.data for o in outs], w, h, _fmt_of(frames[0]),
-                                         k, first, count, overlap, hparam, search, patch, out_dtype=out_dtype)
-            return (outs if outs is not None else [hout.array(i, out_shape, out_dtype) for i in range(count)]), t
-        finally:
-            if hin is not None:
-                hin.free()
-            if hout is not None:
-                hout.free()
+        out_dtype = _out_dtype(out_u8, out_dtype)
+        return self._sequence_host("sequence_nlm", lambda hin, hout, w, h, fmt, hlayers, n_layers, count: self.sequence_nlm_pinned(
+            hin, hout, w, h, fmt, k, first, count, overlap, hparam, search, patch, out_dtype=out_dtype),
+            frames, None, None, first, count, pinned, pinned_out, out_dtype, plain=True, inside=True)
 
     def sequence_bilateral_pinned(self, hin, hout, w, h, fmt, radius, sigma_s=2.0, sigma_c=0.2, layout="texture", hlayers=None,
                                   n_layers=0, overlap=True, out_dtype=None):
@@ -562,23 +589,9 @@ class Context:
         measures what a C caller sees.  hlayers: None (plain bilateral) or len(hin) * n_layers host pointers, frame-major: RGBA8
         layers, or what fmt_with_guide(frames' format, layers' format) names in `fmt`.
         Returns (wall_ms of the whole call, kernel_ms, copy_ms)."""
-        n = len(hin)
-        if len(hout) < n:
-            raise ValueError(f"{n} frames, {len(hout)} output buffers given")
         lay = {"texture": LAYOUT_TEXTURE, "linear": LAYOUT_LINEAR}[layout]
-        prm = BilateralParams(w, h, sigma_s, sigma_c, radius, lay, fmt)
-        out_fmt = {np.dtype(np.uint8): FMT_RGBA8, np.dtype(np.float16): FMT_RGBA16F,
-                   np.dtype(np.float32): FMT_RGBA32F}[_out_dtype(False, out_dtype)]
-        tl = None
-        if hlayers is not None:
-            if len(hlayers) != n * n_layers:
-                raise ValueError(f"{n} frames x {n_layers} layers, {len(hlayers)} layer pointers given")
-            tl = (ctypes.c_void_p * max(len(hlayers), 1))(*hlayers)
-        t = (ctypes.c_float * 3)()
-        _check(lib.mid_sequence_bilateral(self.handle, ctypes.byref(prm), (ctypes.c_void_p * n)(*hin), n, tl, n_layers,
-                                          (ctypes.c_void_p * n)(*hout[:n]), out_fmt, 1 if overlap else 0, t),
-               "mid_sequence_bilateral")
-        return tuple(t)
+        return self._sequence_call("mid_sequence_bilateral", "mid_sequence_bilateral", BilateralParams(w, h, sigma_s, sigma_c, radius, lay, fmt),
+                                   hin, hout, len(hin), f"{len(hin)} frames", overlap, layers=(hlayers, n_layers), plain=True, out_dtype=(out_dtype,))
 
     def sequence_bilateral(self, frames, radius, sigma_s=2.0, sigma_c=0.2, layout="texture", layers=None, overlap=True,
                            pinned=True, pinned_out=True, out_dtype=None):
@@ -589,47 +602,19 @@ class Context:
         dtype (texture layout only).
         pinned / pinned_out = False: the NumPy arrays themselves (pageable memory) are the sources / destinations.
         Returns (outputs, (wall_ms, kernel_ms, copy_ms))."""
-        frames = _same_frames(frames, "sequence_bilateral")
-        n = len(frames)
-        h, w = frames[0].shape[:2]
-        n_layers, flat = (0, None) if layers is None else _flat_layers(layers, n, h, w, "sequence_bilateral", _GUIDE_DTYPES)
-        out_shape, out_dtype = (h, w, 4), _out_dtype(False, out_dtype)
-        hin = hlay = hout = None
-        try:
-            hin = PinnedFrames(self, frames) if pinned else None
-            hlay = PinnedFrames(self, flat) if pinned and flat else None
-            hout = PinnedFrames(self, n, w * h * 4 * out_dtype.itemsize) if pinned_out else None
-            outs = None if pinned_out else [np.empty(out_shape, out_dtype) for _ in range(n)]
-            lptr = None if flat is None else (hlay.ptrs if hlay is not None else [lyr.ctypes.data for lyr in flat])
-            t = self.sequence_bilateral_pinned(hin.ptrs if pinned else [f.ctypes.data for f in frames],
-                                               hout.ptrs if pinned_out else [o.ctypes.data for o in outs], w, h,
-                                               _guide_fmt(_fmt_of(frames[0]), flat or [], "sequence_bilateral"), radius, sigma_s, sigma_c,
-                                               layout, lptr, n_layers, overlap, out_dtype)
-            return (outs if outs is not None else [hout.array(i, out_shape, out_dtype) for i in range(n)]), t
-        finally:
-            for b in (hin, hlay, hout):
-                if b is not None:
-                    b.free()
+        out_dtype = _out_dtype(False, out_dtype)
+        return self._sequence_host("sequence_bilateral", lambda hin, hout, w, h, fmt, hlayers, n_layers, count: self.sequence_bilateral_pinned(
+            hin, hout, w, h, fmt, radius, sigma_s, sigma_c, layout, hlayers, n_layers, overlap, out_dtype),
+            frames, layers, _GUIDE_DTYPES, 0, None, pinned, pinned_out, out_dtype, plain=True)
 
     def sequence_nlm_layers_pinned(self, hin, hout, w, h, fmt, hlayers, n_layers, overlap=True, hparam=0.5, search=(-7, 7),
                                    patch=(-3, 3), out_dtype=None):
         """mid_sequence_nlm_layers on host pointers the caller already holds: nothing but the C call, so a clock around it
         measures what a C caller sees.  hlayers: len(hin) * n_layers RGBA8 host pointers, frame-major.
         Returns (wall_ms of the whole call, kernel_ms, copy_ms)."""
-        n = len(hin)
-        if len(hout) < n:
-            raise ValueError(f"{n} frames, {len(hout)} output buffers given")
-        if len(hlayers) != n * n_layers:
-            raise ValueError(f"{n} frames x {n_layers} layers, {len(hlayers)} layer pointers given")
-        prm = NlmParams(w, h, hparam, search[0], search[1], patch[0], patch[1], fmt)
-        out_fmt = {np.dtype(np.uint8): FMT_RGBA8, np.dtype(np.float16): FMT_RGBA16F,
-                   np.dtype(np.float32): FMT_RGBA32F}[_out_dtype(False, out_dtype)]
-        tl = (ctypes.c_void_p * max(len(hlayers), 1))(*hlayers)
-        t = (ctypes.c_float * 3)()
-        _check(lib.mid_sequence_nlm_layers(self.handle, ctypes.byref(prm), (ctypes.c_void_p * n)(*hin), n, tl, n_layers,
-                                           (ctypes.c_void_p * n)(*hout[:n]), out_fmt, 1 if overlap else 0, t),
-               "mid_sequence_nlm_layers")
-        return tuple(t)
+        return self._sequence_call("mid_sequence_nlm_layers", "mid_sequence_nlm_layers",
+                                   NlmParams(w, h, hparam, search[0], search[1], patch[0], patch[1], fmt), hin, hout, len(hin),
+                                   f"{len(hin)} frames", overlap, layers=(hlayers, n_layers), out_dtype=(out_dtype,))
 
     def sequence_nlm_layers(self, frames, layers, overlap=True, hparam=0.5, search=(-7, 7), patch=(-3, 3), pinned=True,
                             pinned_out=True, out_dtype=None):
@@ -639,48 +624,20 @@ class Context:
         layers: one list per frame of equally many uint8 (h, w, 4) guide layers.
         pinned / pinned_out = False: the NumPy arrays themselves (pageable memory) are the sources / destinations.
         Returns (outputs, (wall_ms, kernel_ms, copy_ms))."""
-        frames = _same_frames(frames, "sequence_nlm_layers")
-        n = len(frames)
-        h, w = frames[0].shape[:2]
-        n_layers, flat = _flat_layers(layers, n, h, w, "sequence_nlm_layers")
-        out_shape, out_dtype = (h, w, 4), _out_dtype(False, out_dtype)
-        hin = hlay = hout = None
-        try:
-            hin = PinnedFrames(self, frames) if pinned else None
-            hlay = PinnedFrames(self, flat) if pinned and flat else None
-            hout = PinnedFrames(self, n, w * h * 4 * out_dtype.itemsize) if pinned_out else None
-            outs = None if pinned_out else [np.empty(out_shape, out_dtype) for _ in range(n)]
-            lptr = hlay.ptrs if hlay is not None else [lyr.ctypes.data for lyr in flat]
-            t = self.sequence_nlm_layers_pinned(hin.ptrs if pinned else [f.ctypes.data for f in frames],
-                                                hout.ptrs if pinned_out else [o.ctypes.data for o in outs], w, h,
-                                                _fmt_of(frames[0]), lptr, n_layers, overlap, hparam, search, patch, out_dtype)
-            return (outs if outs is not None else [hout.array(i, out_shape, out_dtype) for i in range(n)]), t
-        finally:
-            for b in (hin, hlay, hout):
-                if b is not None:
-                    b.free()
+        out_dtype = _out_dtype(False, out_dtype)
+        return self._sequence_host("sequence_nlm_layers", lambda hin, hout, w, h, fmt, hlayers, n_layers, count: self.sequence_nlm_layers_pinned(
+            hin, hout, w, h, fmt, hlayers, n_layers, overlap, hparam, search, patch, out_dtype),
+            frames, layers, (np.uint8,), 0, None, pinned, pinned_out, out_dtype)
 
     def sequence_nlm_layers_temporal_pinned(self, hin, hout, w, h, fmt, hlayers, n_layers, k, first=0, count=None, overlap=True,
                                             hparam=0.5, search=(-7, 7), patch=(-3, 3), out_dtype=None):
         """mid_sequence_nlm_layers_temporal on host pointers the caller already holds: nothing but the C call.  hin: all n frames of
         the sequence (only those of [first-k, first+count+k) are read); hlayers: n * n_layers RGBA8 host pointers, frame-major;
         hout: `count` output buffers.  Returns (wall_ms of the whole call, kernel_ms, copy_ms)."""
-        n = len(hin)
-        count = n - first if count is None else count
-        if len(hout) < count:
-            raise ValueError(f"{count} outputs, {len(hout)} output buffers given")
-        if len(hlayers) != n * n_layers:
-            raise ValueError(f"{n} frames x {n_layers} layers, {len(hlayers)} layer pointers given")
-        prm = NlmParams(w, h, hparam, search[0], search[1], patch[0], patch[1], fmt)
-        out_fmt = {np.dtype(np.uint8): FMT_RGBA8, np.dtype(np.float16): FMT_RGBA16F,
-                   np.dtype(np.float32): FMT_RGBA32F}[_out_dtype(False, out_dtype)]
-        tl = (ctypes.c_void_p * max(len(hlayers), 1))(*hlayers)
-        t = (ctypes.c_float * 3)()
-        _check(lib.mid_sequence_nlm_layers_temporal(self.handle, ctypes.byref(prm), (ctypes.c_void_p * n)(*hin), n, tl, n_layers, k,
-                                                    first, count, (ctypes.c_void_p * max(count, 1))(*hout[:max(count, 0)]), out_fmt,
-                                                    1 if overlap else 0, t),
-               "mid_sequence_nlm_layers_temporal")
-        return tuple(t)
+        count = len(hin) - first if count is None else count
+        return self._sequence_call("mid_sequence_nlm_layers_temporal", "mid_sequence_nlm_layers_temporal",
+                                   NlmParams(w, h, hparam, search[0], search[1], patch[0], patch[1], fmt), hin, hout, count,
+                                   f"{count} outputs", overlap, layers=(hlayers, n_layers), window=(k, first, count), out_dtype=(out_dtype,))
 
     def sequence_nlm_layers_temporal(self, frames, layers, k=2, first=0, count=None, overlap=True, hparam=0.5, search=(-7, 7),
                                      patch=(-3, 3), pinned=True, pinned_out=True, out_dtype=None):
@@ -688,52 +645,20 @@ class Context:
         t-k..t+k as its compute stage (mid_sequence_nlm_layers_temporal): output t is ctx.nlm_layers_temporal(frames, layers, k)
         of frame t in out_dtype.  layers, pinned, pinned_out, out_dtype as for sequence_nlm_layers.
         Returns (outputs, (wall_ms, kernel_ms, copy_ms))."""
-        frames = _same_frames(frames, "sequence_nlm_layers_temporal")
-        n = len(frames)
-        count = n - first if count is None else count
-        h, w = frames[0].shape[:2]
-        n_layers, flat = _flat_layers(layers, n, h, w, "sequence_nlm_layers_temporal")
-        out_shape, out_dtype = (h, w, 4), _out_dtype(False, out_dtype)
-        hin = hlay = hout = None
-        try:
-            hin = PinnedFrames(self, frames) if pinned else None
-            hlay = PinnedFrames(self, flat) if pinned and flat else None
-            hout = PinnedFrames(self, max(count, 1), w * h * 4 * out_dtype.itemsize) if pinned_out else None
-            outs = None if pinned_out else [np.empty(out_shape, out_dtype) for _ in range(max(count, 0))]
-            lptr = hlay.ptrs if hlay is not None else [lyr.ctypes.data for lyr in flat]
-            t = self.sequence_nlm_layers_temporal_pinned(hin.ptrs if pinned else [f.ctypes.data for f in frames],
-                                                         hout.ptrs if pinned_out else [o.ctypes.data for o in outs], w, h,
-                                                         _fmt_of(frames[0]), lptr, n_layers, k, first, count, overlap, hparam,
-                                                         search, patch, out_dtype)
-            return (outs if outs is not None else [hout.array(i, out_shape, out_dtype) for i in range(count)]), t
-        finally:
-            for b in (hin, hlay, hout):
-                if b is not None:
-                    b.free()
+        out_dtype = _out_dtype(False, out_dtype)
+        return self._sequence_host("sequence_nlm_layers_temporal", lambda hin, hout, w, h, fmt, hlayers, n_layers, count: self.sequence_nlm_layers_temporal_pinned(
+            hin, hout, w, h, fmt, hlayers, n_layers, k, first, count, overlap, hparam, search, patch, out_dtype),
+            frames, layers, (np.uint8,), first, count, pinned, pinned_out, out_dtype)
 
     def sequence_bilateral_temporal_pinned(self, hin, hout, w, h, fmt, k, first=0, count=None, radius=8, sigma_s=2.0, sigma_c=0.2,
                                            hlayers=None, n_layers=0, overlap=True, out_dtype=None):
         """mid_sequence_bilateral_temporal on host pointers the caller already holds: nothing but the C call.  hin: all n frames
         of the sequence (only those of [first-k, first+count+k) are read); hlayers: None (plain form) or n * n_layers host
         pointers, frame-major (RGBA8, or what fmt_with_guide names in `fmt`); hout: `count` output buffers.  Returns (wall_ms of the whole call, kernel_ms, copy_ms)."""
-        n = len(hin)
-        count = n - first if count is None else count
-        if len(hout) < count:
-            raise ValueError(f"{count} outputs, {len(hout)} output buffers given")
-        tl = None
-        if hlayers is not None:
-            if len(hlayers) != n * n_layers:
-                raise ValueError(f"{n} frames x {n_layers} layers, {len(hlayers)} layer pointers given")
-            tl = (ctypes.c_void_p * max(len(hlayers), 1))(*hlayers)
-        prm = BilateralParams(w, h, sigma_s, sigma_c, radius, LAYOUT_TEXTURE, fmt)
-        out_fmt = {np.dtype(np.uint8): FMT_RGBA8, np.dtype(np.float16): FMT_RGBA16F,
-                   np.dtype(np.float32): FMT_RGBA32F}[_out_dtype(False, out_dtype)]
-        t = (ctypes.c_float * 3)()
-        _check(lib.mid_sequence_bilateral_temporal(self.handle, ctypes.byref(prm), (ctypes.c_void_p * n)(*hin), n, tl, n_layers, k,
-                                                   first, count, (ctypes.c_void_p * max(count, 1))(*hout[:max(count, 0)]), out_fmt,
-                                                   1 if overlap else 0, t),
-               "mid_sequence_bilateral_temporal")
-        return tuple(t)
+        count = len(hin) - first if count is None else count
+        return self._sequence_call("mid_sequence_bilateral_temporal", "mid_sequence_bilateral_temporal",
+                                   BilateralParams(w, h, sigma_s, sigma_c, radius, LAYOUT_TEXTURE, fmt), hin, hout, count,
+                                   f"{count} outputs", overlap, layers=(hlayers, n_layers), plain=True, window=(k, first, count), out_dtype=(out_dtype,))
 
     def sequence_bilateral_temporal(self, frames, k=2, first=0, count=None, overlap=True, radius=8, sigma_s=2.0, sigma_c=0.2,
                                     layers=None, pinned=True, pinned_out=True, out_dtype=None):
@@ -741,50 +666,21 @@ class Context:
         t-k..t+k as its compute stage (mid_sequence_bilateral_temporal): output t is ctx.bilateral_temporal(frames, k,
         layers=layers) of frame t in out_dtype.  layers, pinned, pinned_out, out_dtype as for sequence_bilateral.
         Returns (outputs, (wall_ms, kernel_ms, copy_ms))."""
-        frames = _same_frames(frames, "sequence_bilateral_temporal")
-        n = len(frames)
-        count = n - first if count is None else count
-        h, w = frames[0].shape[:2]
-        n_layers, flat = (0, None) if layers is None else _flat_layers(layers, n, h, w, "sequence_bilateral_temporal", _GUIDE_DTYPES)
-        out_shape, out_dtype = (h, w, 4), _out_dtype(False, out_dtype)
-        hin = hlay = hout = None
-        try:
-            hin = PinnedFrames(self, frames) if pinned else None
-            hlay = PinnedFrames(self, flat) if pinned and flat else None
-            hout = PinnedFrames(self, max(count, 1), w * h * 4 * out_dtype.itemsize) if pinned_out else None
-            outs = None if pinned_out else [np.empty(out_shape, out_dtype) for _ in range(max(count, 0))]
-            lptr = None if flat is None else (hlay.ptrs if hlay is not None else [lyr.ctypes.data for lyr in flat])
-            t = self.sequence_bilateral_temporal_pinned(hin.ptrs if pinned else [f.ctypes.data for f in frames],
-                                                        hout.ptrs if pinned_out else [o.ctypes.data for o in outs], w, h,
-                                                        _guide_fmt(_fmt_of(frames[0]), flat or [], "sequence_bilateral_temporal"), k, first,
-                                                        count, radius, sigma_s, sigma_c, lptr, n_layers, overlap, out_dtype)
-            return (outs if outs is not None else [hout.array(i, out_shape, out_dtype) for i in range(count)]), t
-        finally:
-            for b in (hin, hlay, hout):
-                if b is not None:
-                    b.free()
+        out_dtype = _out_dtype(False, out_dtype)
+        return self._sequence_host("sequence_bilateral_temporal", lambda hin, hout, w, h, fmt, hlayers, n_layers, count: self.sequence_bilateral_temporal_pinned(
+            hin, hout, w, h, fmt, k, first, count, radius, sigma_s, sigma_c, hlayers, n_layers, overlap, out_dtype),
+            frames, layers, _GUIDE_DTYPES, first, count, pinned, pinned_out, out_dtype, plain=True)
 
     def sequence_bilateral_joint_pinned(self, hin, hout, w, h, fmt, hlayers, n_layers, sigmas=None, k=0, first=0, count=None, radius=8,
                                         sigma_s=2.0, sigma_c=0.2, overlap=True, out_dtype=None):
         """mid_sequence_bilateral_joint on host pointers the caller already holds: nothing but the C call.  hin, hlayers, hout as
         for sequence_bilateral_temporal_pinned (hlayers is required); sigmas: n_layers sigmas or None.
         Returns (wall_ms of the whole call, kernel_ms, copy_ms)."""
-        n = len(hin)
-        count = n - first if count is None else count
-        if len(hout) < count:
-            raise ValueError(f"{count} outputs, {len(hout)} output buffers given")
-        if len(hlayers) != n * n_layers:
-            raise ValueError(f"{n} frames x {n_layers} layers, {len(hlayers)} layer pointers given")
-        prm = BilateralParams(w, h, sigma_s, sigma_c, radius, LAYOUT_TEXTURE, fmt)
-        out_fmt = {np.dtype(np.uint8): FMT_RGBA8, np.dtype(np.float16): FMT_RGBA16F,
-                   np.dtype(np.float32): FMT_RGBA32F}[_out_dtype(False, out_dtype)]
-        t = (ctypes.c_float * 3)()
-        _check(lib.mid_sequence_bilateral_joint(self.handle, ctypes.byref(prm), _layer_sigmas(sigmas, n_layers, "sequence_bilateral_joint"),
-                                                (ctypes.c_void_p * n)(*hin), n, (ctypes.c_void_p * max(len(hlayers), 1))(*hlayers),
-                                                n_layers, k, first, count, (ctypes.c_void_p * max(count, 1))(*hout[:max(count, 0)]),
-                                                out_fmt, 1 if overlap else 0, t),
-               "mid_sequence_bilateral_joint")
-        return tuple(t)
+        count = len(hin) - first if count is None else count
+        return self._sequence_call("mid_sequence_bilateral_joint", "mid_sequence_bilateral_joint",
+                                   BilateralParams(w, h, sigma_s, sigma_c, radius, LAYOUT_TEXTURE, fmt), hin, hout, count,
+                                   f"{count} outputs", overlap, layers=(hlayers, n_layers), window=(k, first, count), out_dtype=(out_dtype,),
+                                   sigmas=(sigmas,))
 
     def sequence_bilateral_joint(self, frames, layers, sigmas=None, k=0, first=0, count=None, overlap=True, radius=8, sigma_s=2.0,
                                  sigma_c=0.2, pinned=True, pinned_out=True, out_dtype=None):
@@ -792,28 +688,10 @@ class Context:
         t-k..t+k as its compute stage (mid_sequence_bilateral_joint): output t is ctx.bilateral_joint(frames, layers, sigmas, k)
         of frame t in out_dtype.  pinned, pinned_out, out_dtype as for sequence_bilateral.
         Returns (outputs, (wall_ms, kernel_ms, copy_ms))."""
-        frames = _same_frames(frames, "sequence_bilateral_joint")
-        n = len(frames)
-        count = n - first if count is None else count
-        h, w = frames[0].shape[:2]
-        n_layers, flat = _flat_layers(layers, n, h, w, "sequence_bilateral_joint", _GUIDE_DTYPES)
-        out_shape, out_dtype = (h, w, 4), _out_dtype(False, out_dtype)
-        hin = hlay = hout = None
-        try:
-            hin = PinnedFrames(self, frames) if pinned else None
-            hlay = PinnedFrames(self, flat) if pinned and flat else None
-            hout = PinnedFrames(self, max(count, 1), w * h * 4 * out_dtype.itemsize) if pinned_out else None
-            outs = None if pinned_out else [np.empty(out_shape, out_dtype) for _ in range(max(count, 0))]
-            lptr = hlay.ptrs if hlay is not None else [lyr.ctypes.data for lyr in flat]
-            t = self.sequence_bilateral_joint_pinned(hin.ptrs if pinned else [f.ctypes.data for f in frames],
-                                                     hout.ptrs if pinned_out else [o.ctypes.data for o in outs], w, h,
-                                                     _guide_fmt(_fmt_of(frames[0]), flat, "sequence_bilateral_joint"), lptr, n_layers,
-                                                     sigmas, k, first, count, radius, sigma_s, sigma_c, overlap, out_dtype)
-            return (outs if outs is not None else [hout.array(i, out_shape, out_dtype) for i in range(count)]), t
-        finally:
-            for b in (hin, hlay, hout):
-                if b is not None:
-                    b.free()
+        out_dtype = _out_dtype(False, out_dtype)
+        return self._sequence_host("sequence_bilateral_joint", lambda hin, hout, w, h, fmt, hlayers, n_layers, count: self.sequence_bilateral_joint_pinned(
+            hin, hout, w, h, fmt, hlayers, n_layers, sigmas, k, first, count, radius, sigma_s, sigma_c, overlap, out_dtype),
+            frames, layers, _GUIDE_DTYPES, first, count, pinned, pinned_out, out_dtype)
 
 
 def _layer_sigmas(sigmas, n_layers, who):

@@ -76,6 +76,38 @@ struct Options {
         if ((call) != 0) throw std::runtime_error(std::string(#call) + ": " + mid_last_error()); \
     } while (0)
 
+// --animation-filter, parsed once: the mid_sequence_* family a value runs, what that family reads, and the words of the value.
+enum SeqFamily { SEQ_NLM, SEQ_BILATERAL, SEQ_NLM_LAYERS, SEQ_NLM_LAYERS_TEMPORAL, SEQ_BILATERAL_TEMPORAL, SEQ_BILATERAL_JOINT };
+struct AnimationFilter {
+    const char *name;
+    SeqFamily family;
+    bool layers;            // every frame is guided by its own RenderElements layers
+    bool temporal;          // the frames t-k..t+k (--temporal-k); false: k = 0
+    bool linear;            // MID_LAYOUT_LINEAR
+    const char *infix;      // output-animation-<infix><frame file name>
+    const char *words;      // of the summary line, before r= / the layers / k=
+    const char *banner;     // "Running on GPU (animation, <banner>)"
+    bool bilateral() const { return family == SEQ_BILATERAL || family == SEQ_BILATERAL_TEMPORAL || family == SEQ_BILATERAL_JOINT; }
+    bool windowed() const { return family != SEQ_BILATERAL && family != SEQ_NLM_LAYERS; }     // blocks with k halo frames on either side
+};
+static const AnimationFilter kAnimationFilters[] = {
+    {"nlm", SEQ_NLM, false, true, false, "", "", "temporal nonlocal"},
+    {"bilateral", SEQ_BILATERAL, false, false, false, "nonlinear-bialteral-", "bilateral bilateral", "nonlinear bialteral"},
+    {"linear", SEQ_BILATERAL, false, false, true, "linear-bialteral-", "linear bilateral", "linear bialteral"},
+    {"layers", SEQ_BILATERAL, true, false, false, "nonlinear-bialteral-layers-", "layers bilateral", "nonlinear bialteral + layers"},
+    {"nlm-layers", SEQ_NLM_LAYERS, true, false, false, "nonlinear-nlm-layers-", "nonlocal", "nonlocal + layers"},
+    {"nlm-layers-temporal", SEQ_NLM_LAYERS_TEMPORAL, true, true, false, "nonlinear-nlm-layers-multiframe-", "nonlocal", "nonlocal + layers, multiframe"},
+    {"bilateral-temporal", SEQ_BILATERAL_TEMPORAL, false, true, false, "nonlinear-bialteral-multiframe-", "bilateral", "nonlinear bialteral, multiframe"},
+    {"layers-temporal", SEQ_BILATERAL_TEMPORAL, true, true, false, "nonlinear-bialteral-layers-multiframe-", "bilateral", "nonlinear bialteral + layers, multiframe"},
+    {"joint", SEQ_BILATERAL_JOINT, true, false, false, "nonlinear-bialteral-joint-", "joint bilateral", "joint bialteral"},
+    {"joint-temporal", SEQ_BILATERAL_JOINT, true, true, false, "nonlinear-bialteral-joint-multiframe-", "joint bilateral", "joint bialteral, multiframe"},
+};
+static const AnimationFilter *animation_filter(const std::string &name)
+{
+    for (const AnimationFilter &f : kAnimationFilters) if (name == f.name) return &f;
+    return nullptr;
+}
+
 // ---- RunOnCPU, src/main.cpp:1732-1921 -----------------------------------------------------------------
 // The reference's CPU bilateral: window `radius`, double-precision pow/sqrt/exp stored to float, float
 // accumulators, rows [radius, h-radius] and columns [radius, w-radius] INCLUSIVE (the last row/column
@@ -460,20 +492,15 @@ public:
         std::vector<std::string> frameNames, layerNames;
         discover(frameNames, layerNames, true, false);
         if (frameNames.empty()) throw std::runtime_error("no frames next to " + opt.image);
-        // --animation-filter joint | joint-temporal: the joint bilateral of every frame, alone (k = 0) or over the frames t-k..t+k
-        // (mid_sequence_bilateral_joint: the schedule of layers-temporal)
-        const bool joint = opt.animation_filter == "joint" || opt.animation_filter == "joint-temporal";
-        const int n = (int)frameNames.size(), k = opt.animation_filter == "joint" ? 0 : opt.temporal_k < 0 ? 2 : opt.temporal_k;
-        const bool nlm_layers = opt.animation_filter == "nlm-layers";                   // layer-guided NLM of every frame
-        const bool nlm_layers_t = opt.animation_filter == "nlm-layers-temporal";        // ... over the frames t-k..t+k and their layers
-        const bool bil_t = opt.animation_filter == "bilateral-temporal" || opt.animation_filter == "layers-temporal" || joint;   // the bilateral over the frames t-k..t+k
-        const bool bil = opt.animation_filter != "nlm" && !nlm_layers && !nlm_layers_t && !bil_t;
-        const bool use_layers = opt.animation_filter == "layers" || nlm_layers || nlm_layers_t || opt.animation_filter == "layers-temporal" || joint;
-        const bool linear = opt.animation_filter == "linear";
-        if ((bil || nlm_layers) && opt.halo_rccl)
+        // (joint | joint-temporal: the joint bilateral of every frame, alone (k = 0) or over the frames t-k..t+k -- mid_sequence_bilateral_joint,
+        // the schedule of layers-temporal)
+        const AnimationFilter &af = *animation_filter(opt.animation_filter);        // (main has refused unknown names)
+        const int n = (int)frameNames.size(), k = !af.temporal ? 0 : opt.temporal_k < 0 ? 2 : opt.temporal_k;
+        const bool use_layers = af.layers, nlm_guides = af.family == SEQ_NLM_LAYERS || af.family == SEQ_NLM_LAYERS_TEMPORAL;
+        if (!af.windowed() && opt.halo_rccl)
             throw std::runtime_error("--halo rccl is not available with --animation-filter " + opt.animation_filter +
                                      ": its frames read no other frame, there is no halo to exchange");
-        if ((nlm_layers_t || bil_t) && opt.halo_rccl)
+        if (af.family != SEQ_NLM && opt.halo_rccl)
             throw std::runtime_error("--halo rccl is not available with --animation-filter " + opt.animation_filter + ": the halo would have to "
                                      "carry every halo frame's layers as well, and that exchange is not built (use --halo host)");
         // every frame's own layers, all of them checked before anything is decoded: 1..16 per frame, the same count for all
@@ -493,9 +520,9 @@ public:
         // the layers' format, one for the run: .exr layers (RGBA32F, RGBA16F with --half) guide the bilateral filters only
         std::vector<std::string> allLayers;
         for (auto &fl : frameLayers) allLayers.insert(allLayers.end(), fl.begin(), fl.end());
-        if (nlm_layers || nlm_layers_t) for (const std::string &ln : allLayers) if (is_hdr(ln)) (void)load(ln, true);   // refuses, saying why
+        if (nlm_guides) for (const std::string &ln : allLayers) if (is_hdr(ln)) (void)load(ln, true);   // refuses, saying why
         const int lfmt = layer_format(allLayers);
-        const std::vector<float> jointSigma = joint ? layer_sigmas(frameLayers[0]) : std::vector<float>();   // (every frame has frame 0's layers)
+        const std::vector<float> jointSigma = af.family == SEQ_BILATERAL_JOINT ? layer_sigmas(frameLayers[0]) : std::vector<float>();   // (every frame has frame 0's layers)
         std::cout << "\tloading " << n << " frames\n";
         // Frames are decoded STRAIGHT INTO pinned host memory (mid_image_load_pinned) and the results land in pinned
         // buffers too, so every copy of the pipeline is a true asynchronous DMA -- the reference memcpy's its decoded
@@ -571,7 +598,7 @@ public:
         std::vector<HostImage> layerImgs((size_t)n * L);             // (released before `pin` and its context)
         for_each_file(0, (int)layerImgs.size(), [&](int j) {
             const int i = j / L;
-            layerImgs[j] = load(frameLayers[i][j % L], nlm_layers || nlm_layers_t, (size_t)i < n_pin ? io : nullptr, lfmt == MID_FMT_RGBA16F);
+            layerImgs[j] = load(frameLayers[i][j % L], nlm_guides, (size_t)i < n_pin ? io : nullptr, lfmt == MID_FMT_RGBA16F);
             const HostImage &l = layerImgs[j];
             if (l.w != pin.frames[0].width || l.h != pin.frames[0].height || l.format != lfmt)
                 throw std::runtime_error(frameNames[i] + ": layer " + frameLayers[i][j % L] + " is not " +
@@ -610,9 +637,32 @@ public:
         std::vector<mid_ctx *> ctxs(G, nullptr);
         struct CtxGuard { std::vector<mid_ctx *> &v; ~CtxGuard() { for (auto c : v) if (c) mid_ctx_destroy(c); } } guard{ctxs};
         const mid_nlm_params p{w, h, opt.nlm_h, opt.search_lo, opt.search_hi, opt.patch_lo, opt.patch_hi, fmt};
-        const mid_bilateral_params bp{w, h, opt.sigma_s, opt.sigma_c, opt.radius, linear ? MID_LAYOUT_LINEAR : MID_LAYOUT_TEXTURE,
+        const mid_bilateral_params bp{w, h, opt.sigma_s, opt.sigma_c, opt.radius, af.linear ? MID_LAYOUT_LINEAR : MID_LAYOUT_TEXTURE,
                                       use_layers && lfmt != MID_FMT_RGBA8 ? MID_FMT_WITH_GUIDE(fmt, lfmt) : fmt};
         const int out_fmt = hdr ? MID_FMT_RGBA32F : half ? MID_FMT_RGBA16F : MID_FMT_RGBA8;
+        // One stage call of this run's filter: outputs [start, start + count) of the nf frames (L layers each, frame-major) into outs[0..count).
+        // The k = 0 families take the block as a sub-array of frames, layers and outputs; the others the whole sequence, of which they
+        // upload the block plus kk halo frames on either side, and their layers, from the host.
+        auto run_stage = [&](mid_ctx *c, const mid_nlm_params &np, const mid_bilateral_params &bpp, const void *const *frames, int nf,
+                             const void *const *layers, int kk, int start, int count, void *const *outs, float *t) {
+            const void *const *lp = use_layers ? layers : nullptr;
+            switch (af.family) {
+            case SEQ_BILATERAL:
+                MID_CHECK(mid_sequence_bilateral(c, &bpp, frames + start, count, lp ? lp + (size_t)start * L : nullptr, L, outs, out_fmt, 1, t)); break;
+            case SEQ_NLM_LAYERS:
+                MID_CHECK(mid_sequence_nlm_layers(c, &np, frames + start, count, lp + (size_t)start * L, L, outs, out_fmt, 1, t)); break;
+            case SEQ_NLM_LAYERS_TEMPORAL:
+                MID_CHECK(mid_sequence_nlm_layers_temporal(c, &np, frames, nf, lp, L, kk, start, count, outs, out_fmt, 1, t)); break;
+            case SEQ_BILATERAL_JOINT:      // one weight from all layers
+                MID_CHECK(mid_sequence_bilateral_joint(c, &bpp, jointSigma.data(), frames, nf, lp, L, kk, start, count, outs, out_fmt, 1, t)); break;
+            case SEQ_BILATERAL_TEMPORAL:   // plain or with the layers
+                MID_CHECK(mid_sequence_bilateral_temporal(c, &bpp, frames, nf, lp, L, kk, start, count, outs, out_fmt, 1, t)); break;
+            case SEQ_NLM:     // (one entry per output format; the casts only name the element type the library stores: every pointer of outs is a void *)
+                if (hdr) MID_CHECK(mid_sequence_nlm_range(c, &np, frames, nf, kk, start, count, (mid_pixel *const *)outs, 1, t));
+                else if (half) MID_CHECK(mid_sequence_nlm_range_f16(c, &np, frames, nf, kk, start, count, (uint16_t *const *)outs, 1, t));
+                else MID_CHECK(mid_sequence_nlm_range_u8(c, &np, frames, nf, kk, start, count, (uint8_t *const *)outs, 1, t));
+            }
+        };
         const auto tw0 = std::chrono::steady_clock::now();
         for (int g = 0; g < G; ++g) {
             MID_CHECK(mid_ctx_create(opt.share_device ? opt.device : opt.device + g, &ctxs[g]));
@@ -620,40 +670,14 @@ public:
             const int ww = 64, wh = 32;
             mid_nlm_params wp = p;
             wp.width = ww; wp.height = wh;
-            std::vector<unsigned char> a((size_t)ww * wh * 16, 0), o((size_t)ww * wh * 16);
+            mid_bilateral_params wbp = bp;
+            wbp.width = ww; wbp.height = wh;
+            std::vector<unsigned char> a((size_t)ww * wh * 16, 0), o((size_t)ww * wh * 16), lz((size_t)ww * wh * 16, 0);   // (lz: a layer of any guide format)
             const void *wi[2] = {a.data(), a.data()};
-            if (bil) {
-                mid_bilateral_params wbp = bp;
-                wbp.width = ww; wbp.height = wh;
-                std::vector<unsigned char> lz((size_t)ww * wh * 16, 0);      // (a layer of any guide format)
-                const void *wl[16];
-                for (int l = 0; l < L; ++l) wl[l] = lz.data();
-                void *wo[1] = {o.data()};
-                MID_CHECK(mid_sequence_bilateral(ctxs[g], &wbp, wi, 1, use_layers ? wl : nullptr, L, wo, out_fmt, 1, nullptr));
-            } else if (nlm_layers) {
-                std::vector<unsigned char> lz((size_t)ww * wh * 4, 0);
-                const void *wl[16];
-                for (int l = 0; l < L; ++l) wl[l] = lz.data();
-                void *wo[1] = {o.data()};
-                MID_CHECK(mid_sequence_nlm_layers(ctxs[g], &wp, wi, 1, wl, L, wo, out_fmt, 1, nullptr));
-            } else if (bil_t) {
-                mid_bilateral_params wbp = bp;
-                wbp.width = ww; wbp.height = wh;
-                std::vector<unsigned char> lz((size_t)ww * wh * 16, 0);      // (a layer of any guide format)
-                const void *wl[32];
-                for (int l = 0; l < 2 * L; ++l) wl[l] = lz.data();
-                void *wo[1] = {o.data()};
-                if (joint) MID_CHECK(mid_sequence_bilateral_joint(ctxs[g], &wbp, jointSigma.data(), wi, 2, wl, L, k > 0 ? 1 : 0, 0, 1, wo, out_fmt, 1, nullptr));
-                else MID_CHECK(mid_sequence_bilateral_temporal(ctxs[g], &wbp, wi, 2, use_layers ? wl : nullptr, L, k > 0 ? 1 : 0, 0, 1, wo, out_fmt, 1, nullptr));
-            } else if (nlm_layers_t) {
-                std::vector<unsigned char> lz((size_t)ww * wh * 4, 0);
-                const void *wl[32];
-                for (int l = 0; l < 2 * L; ++l) wl[l] = lz.data();
-                void *wo[1] = {o.data()};
-                MID_CHECK(mid_sequence_nlm_layers_temporal(ctxs[g], &wp, wi, 2, wl, L, k > 0 ? 1 : 0, 0, 1, wo, out_fmt, 1, nullptr));
-            } else if (hdr) { mid_pixel *wo[2] = {(mid_pixel *)o.data(), (mid_pixel *)o.data()}; MID_CHECK(mid_sequence_nlm_range(ctxs[g], &wp, wi, 2, k > 0 ? 1 : 0, 0, 1, wo, 1, nullptr)); }
-            else if (half) { uint16_t *wo[2] = {(uint16_t *)o.data(), (uint16_t *)o.data()}; MID_CHECK(mid_sequence_nlm_range_f16(ctxs[g], &wp, wi, 2, k > 0 ? 1 : 0, 0, 1, wo, 1, nullptr)); }
-            else { uint8_t *wo[2] = {o.data(), o.data()}; MID_CHECK(mid_sequence_nlm_range_u8(ctxs[g], &wp, wi, 2, k > 0 ? 1 : 0, 0, 1, wo, 1, nullptr)); }
+            const void *wl[32];
+            for (int l = 0; l < 2 * L; ++l) wl[l] = lz.data();
+            void *wo[1] = {o.data()};
+            run_stage(ctxs[g], wp, wbp, wi, 2, wl, k > 0 ? 1 : 0, 0, 1, wo, nullptr);
             // (b) the pinned-memory DMA path in both directions at the real frame size (its first use in a process
             // costs several ms): frame 0 up into a scratch buffer, and back down into the first result buffer
             void *scratch = nullptr;
@@ -746,34 +770,7 @@ public:
                     if (count == 0) return;
                     mid_ctx *ctx = ctxs[g];
                     float t[3] = {0, 0, 0};
-                    if (bil) {            // frames are independent: this device's block is a sub-array of frames, layers and outputs
-                        const void *const *lp = use_layers ? layer_ptrs.data() + (size_t)start * L : nullptr;
-                        MID_CHECK(mid_sequence_bilateral(ctx, &bp, in.data() + start, count, lp, L, pin.outs.data() + start, out_fmt, 1, t));
-                    } else if (nlm_layers) {   // likewise
-                        MID_CHECK(mid_sequence_nlm_layers(ctx, &p, in.data() + start, count, layer_ptrs.data() + (size_t)start * L, L,
-                                                          pin.outs.data() + start, out_fmt, 1, t));
-                    } else if (nlm_layers_t) { // this device's block plus k halo frames on either side, and their layers, from the host
-                        MID_CHECK(mid_sequence_nlm_layers_temporal(ctx, &p, in.data(), n, layer_ptrs.data(), L, k, start, count,
-                                                                   pin.outs.data() + start, out_fmt, 1, t));
-                    } else if (joint) {        // likewise, one weight from all layers
-                        MID_CHECK(mid_sequence_bilateral_joint(ctx, &bp, jointSigma.data(), in.data(), n, layer_ptrs.data(), L, k, start, count,
-                                                               pin.outs.data() + start, out_fmt, 1, t));
-                    } else if (bil_t) {        // likewise, plain or with the layers
-                        MID_CHECK(mid_sequence_bilateral_temporal(ctx, &bp, in.data(), n, use_layers ? layer_ptrs.data() : nullptr, L, k, start, count,
-                                                                  pin.outs.data() + start, out_fmt, 1, t));
-                    } else if (hdr) {
-                        std::vector<mid_pixel *> o(count);
-                        for (int i = 0; i < count; ++i) o[i] = (mid_pixel *)pin.outs[start + i];
-                        MID_CHECK(mid_sequence_nlm_range(ctx, &p, in.data(), n, k, start, count, o.data(), 1, t));
-                    } else if (half) {
-                        std::vector<uint16_t *> o(count);
-                        for (int i = 0; i < count; ++i) o[i] = (uint16_t *)pin.outs[start + i];
-                        MID_CHECK(mid_sequence_nlm_range_f16(ctx, &p, in.data(), n, k, start, count, o.data(), 1, t));
-                    } else {
-                        std::vector<uint8_t *> o(count);
-                        for (int i = 0; i < count; ++i) o[i] = (uint8_t *)pin.outs[start + i];
-                        MID_CHECK(mid_sequence_nlm_range_u8(ctx, &p, in.data(), n, k, start, count, o.data(), 1, t));
-                    }
+                    run_stage(ctx, p, bp, in.data(), n, layer_ptrs.data(), k, start, count, pin.outs.data() + start, t);
                     kern[g] = t[1]; copy[g] = t[2];
                 } catch (const std::exception &e) { errors[g] = e.what(); }
             });
@@ -783,11 +780,15 @@ public:
         m_execMs = *std::max_element(kern.begin(), kern.end());
         m_transferMs = *std::max_element(copy.begin(), copy.end());
         std::cout << "\tdecoded " << n << " frames into pinned memory in " << load_sec << " sec (" << io_threads << " file(s) at a time); device set-up + warm-up " << warm_sec << " sec\n";
-        std::cout << "\t" << n << " frames, " << (bil ? opt.animation_filter + " bilateral r=" + std::to_string(opt.radius) : nlm_layers ? "nonlocal + " + std::to_string(L) + " layers" : nlm_layers_t ? "nonlocal + " + std::to_string(L) + " layers, k=" + std::to_string(k) : bil_t ? std::string(joint ? "joint " : "") + "bilateral r=" + std::to_string(opt.radius) + (use_layers ? " + " + std::to_string(L) + " layers" : "") + ", k=" + std::to_string(k) : "k=" + std::to_string(k))
+        std::string words = af.words;
+        if (af.bilateral()) words += " r=" + std::to_string(opt.radius);
+        if (use_layers && af.family != SEQ_BILATERAL) words += " + " + std::to_string(L) + " layers";
+        if (af.windowed()) words += (words.empty() ? "k=" : ", k=") + std::to_string(k);
+        std::cout << "\t" << n << " frames, " << words
                   << ", " << G << " device(s): " << sec << " sec, "
                   << (double)n * w * h / 1e6 / sec << " Mpixel/s end to end (host frames in -> host frames out)\n";
         // SaveEXR :1699 / lodepng::encode :1717, straight from the pinned results -- one file per worker thread, like the decode
-        const std::string mode_name = nlm_layers ? "nonlinear-nlm-layers-" : nlm_layers_t ? "nonlinear-nlm-layers-multiframe-" : joint ? (k == 0 && opt.animation_filter == "joint" ? "nonlinear-bialteral-joint-" : "nonlinear-bialteral-joint-multiframe-") : bil_t ? (use_layers ? "nonlinear-bialteral-layers-multiframe-" : "nonlinear-bialteral-multiframe-") : !bil ? "" : linear ? "linear-bialteral-" : use_layers ? "nonlinear-bialteral-layers-" : "nonlinear-bialteral-";
+        const std::string mode_name = af.infix;
         const auto te0 = std::chrono::steady_clock::now();
         for_each_file(0, n, [&](int i) {
             const std::string name = "output-animation-" + mode_name + fs::path(frameNames[i]).stem().string() + (hdr || half ? ".exr" : ".png");
@@ -948,9 +949,10 @@ int main(int argc, char **argv)
         else if (a == "--animation") opt.animation = true;
         else if (a == "--animation-filter") {
             opt.animation_filter = next();
-            const std::string &f = opt.animation_filter;
-            if (f != "nlm" && f != "bilateral" && f != "linear" && f != "layers" && f != "nlm-layers" && f != "nlm-layers-temporal" && f != "bilateral-temporal" && f != "layers-temporal" && f != "joint" && f != "joint-temporal") {
-                std::cerr << "unknown --animation-filter " << f << " (nlm, bilateral, linear, layers, nlm-layers, nlm-layers-temporal, bilateral-temporal, layers-temporal, joint, joint-temporal)\n"; usage(); return EXIT_FAILURE; }
+            if (!animation_filter(opt.animation_filter)) {
+                std::string names;
+                for (const AnimationFilter &f : kAnimationFilters) names += std::string(names.empty() ? "" : ", ") + f.name;
+                std::cerr << "unknown --animation-filter " << opt.animation_filter << " (" << names << ")\n"; usage(); return EXIT_FAILURE; }
         }
         else if (a == "--half") opt.half = true;
         else if (a == "--gpus") opt.gpus = atoi(next());
@@ -983,9 +985,7 @@ int main(int argc, char **argv)
         };
         if (!opt.animation && opt.animation_filter != "nlm") { std::cerr << "--animation-filter needs --animation\n"; return EXIT_FAILURE; }
         if (opt.animation) {
-            const std::string &f = opt.animation_filter;
-            std::cout << "######\nRunning on GPU (animation, " << (f == "nlm" ? "temporal nonlocal" : f == "linear" ? "linear bialteral" :
-                                                                 f == "layers" ? "nonlinear bialteral + layers" : f == "nlm-layers" ? "nonlocal + layers" : f == "nlm-layers-temporal" ? "nonlocal + layers, multiframe" : f == "bilateral-temporal" ? "nonlinear bialteral, multiframe" : f == "layers-temporal" ? "nonlinear bialteral + layers, multiframe" : f == "joint" ? "joint bialteral" : f == "joint-temporal" ? "joint bialteral, multiframe" : "nonlinear bialteral") << ")\n######\n";
+            std::cout << "######\nRunning on GPU (animation, " << animation_filter(opt.animation_filter)->banner << ")\n######\n";
             app.RunAnimation();
             print_time();
             return EXIT_SUCCESS;

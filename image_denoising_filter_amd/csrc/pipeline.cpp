@@ -5,14 +5,15 @@
 // followed, without a barrier, by "copy staging -> texture B", descriptor sets swapped by
 // parity, and a fence wait after every submit).  Here the stages run concurrently on their own HIP streams:
 //
-//   upload   : hipMemcpyAsync host frame f -> device ring slot f % RING (mid_sequence_bilateral with guide layers and
-//              mid_sequence_nlm_layers[_temporal]: and frame f's layers -> the layer ring's slot f % RING, in the same upload interval)
-//   compute  : temporal NLM of output frame t over ring slots t-k..t+k (two kernel streams, frames alternate), or -- for
-//              mid_sequence_bilateral, window k = 0 -- the bilateral (plain, or guided by the layers) of ring slot t alone, or --
-//              for mid_sequence_nlm_layers, k = 0 -- NLM of ring slot t guided by its layers, or -- for
-//              mid_sequence_nlm_layers_temporal -- layer-guided NLM of output t over ring slots t-k..t+k and the layers uploaded
-//              with them, or -- for mid_sequence_bilateral_temporal -- the bilateral (plain or layer-guided) of output t over the
-//              same ring slots and layers
+//   upload   : hipMemcpyAsync host frame f -> device ring slot f % RING; a stage with guide layers uploads frame f's layers into
+//              the layer ring's slot f % RING in the same upload interval
+//   compute  : one launch per output frame t over the ring slots t-k..t+k and the layers uploaded with them (k = 0: slot t alone).
+//              The schedule knows a stage only by its description (struct Stage: sizes, layers, output rule, marker name) and by
+//              one callable that queues a batch's outputs; each entry point supplies that callable around its own filter --
+//              temporal NLM (mid_sequence_nlm*), the bilateral plain or layer-guided (mid_sequence_bilateral, k = 0), layer-guided
+//              NLM (mid_sequence_nlm_layers, k = 0; mid_sequence_nlm_layers_temporal), the bilateral and the joint bilateral over
+//              neighbouring frames (mid_sequence_bilateral_temporal, mid_sequence_bilateral_joint) -- after check_sequence, the one
+//              statement of the argument checks they share
 //   download : hipMemcpyAsync device out slot t % 4 -> host   (RGBA32F and RGBA16F outputs, and RGBA8 outputs in pageable memory)
 //              RGBA8 outputs in page-locked memory have NO download stage: the kernel's epilogue stores the packed pixels
 //              straight into the caller's buffer (4 B per pixel = 17-19 GB/s at the kernel's frame rate, a third of the link);
@@ -99,32 +100,33 @@ void mid::pipe_cache_release(mid_ctx *ctx)
     c.last = mid_pipe_last{};
 }
 
-// What the compute stage of one pipeline call runs: temporal NLM of output t over ring slots t-k..t+k, or the bilateral of
-// ring slot t alone (k = 0) with, if it has any, the guide layers uploaded beside frame t into the layer ring, or layer-guided NLM
-// of ring slot t alone (k = 0) with those layers, or layer-guided NLM of output t over ring slots t-k..t+k and their layers.
+// One compute stage, as the schedule sees it: whose call it is, what is uploaded beside each frame, which rule admits kernel-stored
+// outputs, the name of the launch range -- nothing about the filter.  The filter is the `launch` callable given to run_pipeline
+// beside the stage: each entry point supplies a lambda around its own *_out function.
 struct Stage {
     const char *who;                          // the entry point, for ranges and messages
     int width, height, format;                // the input frames
-    const mid_nlm_params *nlm;                // temporal NLM, or
-    const mid_bilateral_params *bil;          // bilateral (plain, or layer-guided when host_layers is set), or
-    const mid_nlm_params *nlm_layers;         // layer-guided NLM
-    const void *const *host_layers;           // n_layers host layers per frame, frame-major; NULL: plain bilateral / no layers
+    size_t layer_bytes;                       // one guide layer (RGBA8, or what a bilateral format word names)
+    const void *const *host_layers;           // n_layers host layers per frame, frame-major; NULL: nothing is uploaded beside the frames
     int n_layers;
-    bool temporal = false;                    // nlm_layers / bil over the frames t-k..t+k (mid_sequence_nlm_layers_temporal, mid_sequence_bilateral_temporal), any k
-    const float *joint_sigma = nullptr;       // bil, temporal: the joint bilateral with these n_layers sigmas (mid_sequence_bilateral_joint)
+    bool proven;                              // outputs are kernel-stored only inside ONE page-locked mapping (every stage but temporal NLM)
+    const char *marker;                       // the launch range, "nlm %d": profiles and the marker tests read these names
 };
 
 // Outputs [first, first+count) of an n-frame host sequence; frames outside that range are only
 // uploaded as far as the temporal window needs them (the halo of a frame block).  The caller has checked every argument.
-static int run_pipeline(mid_ctx *ctx, const Stage &st, const void *const *host_frames,
+// launch(tbl, n_win, lt, k, t0, bn, out, out_fmt, stream) queues the outputs of one batch: tbl holds the n_win device frames of
+// the batch's window (ring slots lo..need), lt their device layers, frame-major (lt[j * n_layers + l]: layer l of tbl[j]), the
+// outputs are window frames t0 .. t0+bn-1 and go to out[0..bn) in out_fmt.  A k = 0 stage reads its one slot from the same tables.
+template <typename Launch>
+static int run_pipeline(mid_ctx *ctx, const Stage &st, const Launch &launch, const void *const *host_frames,
                         int n, int k, int first, int count, void *const *host_out, int out_fmt,
                         int overlap, float *timings_ms)
 {
     const int f_lo = first - k < 0 ? 0 : first - k;                                  // first frame ever uploaded
     const int f_hi = first + count - 1 + k > n - 1 ? n - 1 : first + count - 1 + k;  // last one
     const size_t npix = (size_t)st.width * st.height;
-    // (guide layers: RGBA8, or with the bilateral what its format word names -- st.bil->format keeps both fields for the kernels)
-    const size_t in_bytes = npix * fmt_bytes(st.format), layer_bytes = npix * fmt_bytes(st.bil ? fmt_guide(st.bil->format) : MID_FMT_RGBA8);
+    const size_t in_bytes = npix * fmt_bytes(st.format), layer_bytes = st.layer_bytes;
     const int n_layers = st.host_layers ? st.n_layers : 0;
     const size_t dl_bytes = npix * fmt_bytes(out_fmt);            // one output frame, as it is written and downloaded
     const int n_up = f_hi - f_lo + 1;
@@ -160,7 +162,7 @@ static int run_pipeline(mid_ctx *ctx, const Stage &st, const void *const *host_f
     // The bilateral and layer-guided NLM take the proven rule for BOTH packed formats: their outputs are stored by the kernel only
     // when every one lies inside one page-locked allocation or registration; otherwise they are downloaded, and an output that is
     // not inside one mapping goes through the bounce buffers (`bounced`) even where both of its ends are page-locked.
-    const bool proven = st.bil || st.nlm_layers;
+    const bool proven = st.proven;
     bool out_pinned = true;
     std::vector<char> bounced(count, 0);
     if (proven) {
@@ -311,47 +313,17 @@ static int run_pipeline(mid_ctx *ctx, const Stage &st, const void *const *host_f
             if (direct) MID_HIP(hipHostGetDevicePointer((void **)&o[i], host_out[b0 - first + i], 0));
             else o[i] = (mid_pixel *)dout.p[(bi % DEPTH) * B + i];
         }
-        if (st.nlm) {
-            Range nlm_range("nlm %d", b0);
+        // the window's layers, frame-major like tbl: output b0 + i reads ring slots b0+i-k .. b0+i+k and the layers uploaded with them
+        static_assert(B == 1, "one output per launch: its window is what nlm_layers_temporal_fits admitted");
+        static_assert(kMaxLayers <= MID_NLM_LAYERS_TEMPORAL_MAX_POINTERS, "the k = 0 stages pass up to kMaxLayers layers unchecked by that rule");
+        const uint32_t *lt[MID_NLM_LAYERS_TEMPORAL_MAX_POINTERS];
+        MID_REQUIRE((need - lo + 1) * n_layers <= MID_NLM_LAYERS_TEMPORAL_MAX_POINTERS, "%s: the window's layers exceed one launch", st.who);
+        for (int f = lo; f <= need; ++f)
+            for (int l = 0; l < n_layers; ++l) lt[(f - lo) * n_layers + l] = (const uint32_t *)layer_slot(f, l);
+        {
+            Range launch_range(st.marker, b0);
             MID_HIP(hipEventRecord(c0.ev[bi], cs));
-            // RGBA8 outputs: GetImageFromGPU's u8 conversion (src/main.cpp:97-103) in the kernel's epilogue -- a quarter of the
-            // bytes to write and to download; RGBA16F outputs: round to nearest even there -- half of them
-            if (int rc = nlm_temporal_out(ctx, st.nlm, tbl, need - lo + 1, k, b0 - lo, bn, (void *const *)o, out_fmt, cs, 1)) return rc;
-            MID_HIP(hipEventRecord(c1.ev[bi], cs));
-        } else if (st.nlm_layers) {
-            Range nlm_range("nlm_layers %d", b0);
-            MID_HIP(hipEventRecord(c0.ev[bi], cs));
-            if (st.temporal) {                    // output b0 + i reads ring slots b0+i-k .. b0+i+k and the layers uploaded with them
-                static_assert(B == 1, "one output per launch: its window is what nlm_layers_temporal_fits admitted");
-                const uint32_t *lt[MID_NLM_LAYERS_TEMPORAL_MAX_POINTERS];      // the window's layers, frame-major like tbl
-                for (int f = lo; f <= need; ++f)
-                    for (int l = 0; l < n_layers; ++l) lt[(f - lo) * n_layers + l] = (const uint32_t *)layer_slot(f, l);
-                if (int rc = nlm_layers_temporal_out(ctx, st.nlm_layers, tbl, lt, n_layers, need - lo + 1, k, b0 - lo, bn,
-                                                     (void *const *)o, out_fmt, cs)) return rc;
-            } else for (int i = 0; i < bn; ++i) { // (k = 0: output b0 + i reads ring slot b0 + i and its layers only)
-                const uint32_t *lt[kMaxLayers];
-                for (int l = 0; l < n_layers; ++l) lt[l] = (const uint32_t *)layer_slot(b0 + i, l);
-                if (int rc = nlm_layers_out(ctx, st.nlm_layers, slot(b0 + i), lt, n_layers, o[i], out_fmt, cs)) return rc;
-            }
-            MID_HIP(hipEventRecord(c1.ev[bi], cs));
-        } else {
-            Range bil_range("bilateral %d", b0);
-            MID_HIP(hipEventRecord(c0.ev[bi], cs));
-            if (st.temporal) {                    // output b0 + i reads ring slots b0+i-k .. b0+i+k and the layers uploaded with them
-                static_assert(B == 1, "one output per launch: its window is what bilateral_temporal_check admitted");
-                const uint32_t *lt[MID_NLM_LAYERS_TEMPORAL_MAX_POINTERS];      // the window's layers, frame-major like tbl
-                for (int f = lo; f <= need; ++f)
-                    for (int l = 0; l < n_layers; ++l) lt[(f - lo) * n_layers + l] = (const uint32_t *)layer_slot(f, l);
-                if (st.joint_sigma) {
-                    if (int rc = bilateral_joint_out(ctx, st.bil, st.joint_sigma, tbl, lt, n_layers, need - lo + 1, k, b0 - lo, bn,
-                                                     (void *const *)o, out_fmt, cs)) return rc;
-                } else if (int rc = bilateral_temporal_out(ctx, st.bil, tbl, st.host_layers ? lt : nullptr, n_layers, need - lo + 1, k, b0 - lo, bn,
-                                                           (void *const *)o, out_fmt, cs)) return rc;
-            } else for (int i = 0; i < bn; ++i) { // (k = 0: output b0 + i reads ring slot b0 + i and its layers only)
-                const uint32_t *lt[kMaxLayers];
-                for (int l = 0; l < n_layers; ++l) lt[l] = (const uint32_t *)layer_slot(b0 + i, l);
-                if (int rc = bilateral_out(ctx, st.bil, slot(b0 + i), st.host_layers ? lt : nullptr, n_layers, o[i], out_fmt, cs)) return rc;
-            }
+            if (int rc = launch(tbl, need - lo + 1, lt, k, b0 - lo, bn, (void *const *)o, out_fmt, cs)) return rc;
             MID_HIP(hipEventRecord(c1.ev[bi], cs));
         }
 
@@ -402,162 +374,38 @@ static int run_pipeline(mid_ctx *ctx, const Stage &st, const void *const *host_f
     return MID_OK;
 }
 
-static int sequence_impl(mid_ctx *ctx, const mid_nlm_params *p, const void *const *host_frames,
-                         int n, int k, int first, int count, void *const *host_out, int out_fmt,
-                         int overlap, float *timings_ms)
+// How one entry point words and bounds the shared checks: its name in the messages, the word it has for its frame count ("n",
+// "n_frames"), whether it takes (k, first, count) -- the k = 0 entry points word a bad frame count their own way -- and whether an
+// output may be one of the call's inputs.
+struct SeqRules {
+    const char *who, *n_word;
+    bool windowed, refuse_alias;
+};
+
+// The argument checks every sequence entry point shares, made before anything is queued: the tables, the frame count and the
+// output range [first, first + count) with its window k, every frame and layer of the uploaded range [first - k, first + count - 1
+// + k] and every output non-NULL, a known output format, and (refuse_alias) no output among exactly those frames and layers nor given
+// twice -- an output that is also an input would be overwritten by a direct store while uploads that run ahead (or the kernel of
+// another stream) still read it.  The k = 0 entry points are the case (k, first, count) = (0, 0, n).  n_layers is read only with a
+// layer table and has been checked by the caller (0..16).
+static int check_sequence(const SeqRules &r, const void *const *host_frames, int n, const void *const *host_layers, int n_layers,
+                          int k, int first, int count, void *const *host_out, int out_fmt)
 {
-    Bind b(ctx, nullptr);
-    if (b.rc) return b.rc;
-    if (int rc = refuse_if_recording(ctx->compute, "mid_sequence_nlm (four streams, host-side waits)")) return rc;
-    MID_REQUIRE(p && host_frames && host_out, "sequence_nlm: NULL argument");
-    MID_REQUIRE(n >= 1 && k >= 0 && 2 * k + 2 <= kMaxFrames, "sequence_nlm: bad n=%d k=%d", n, k);
-    MID_REQUIRE(first >= 0 && count >= 1 && first + count <= n, "sequence_nlm: bad range first=%d count=%d n=%d", first, count, n);
-    MID_REQUIRE(p->width > 0 && p->height > 0, "sequence_nlm: bad size");
-    MID_REQUIRE(fmt_known(p->format), "sequence_nlm: unknown format %d", p->format);
+    const char *who = r.who;
+    MID_REQUIRE(host_frames && host_out, "%s: NULL argument", who);
+    if (!r.windowed) MID_REQUIRE(n >= 1, "%s: n_frames %d < 1", who, n);
+    MID_REQUIRE(n >= 1 && k >= 0 && 2 * (long)k + 2 <= kMaxFrames, "%s: bad %s=%d k=%d", who, r.n_word, n, k);
+    MID_REQUIRE(first >= 0 && count >= 1 && (long)first + count <= n, "%s: bad range first=%d count=%d %s=%d", who, first, count, r.n_word, n);
+    MID_REQUIRE(fmt_known(out_fmt), "%s: unknown output format %d", who, out_fmt);
+    if (!host_layers) n_layers = 0;
     const int f_lo = first - k < 0 ? 0 : first - k;
     const int f_hi = first + count - 1 + k > n - 1 ? n - 1 : first + count - 1 + k;
-    for (int i = f_lo; i <= f_hi; ++i) MID_REQUIRE(host_frames[i], "sequence_nlm: frame %d is NULL", i);
-    for (int i = 0; i < count; ++i) MID_REQUIRE(host_out[i], "sequence_nlm: output %d is NULL", i);
-    const Stage st{"sequence_nlm", p->width, p->height, p->format, p, nullptr, nullptr, nullptr, 0};
-    return run_pipeline(ctx, st, host_frames, n, k, first, count, host_out, out_fmt, overlap, timings_ms);
-}
-
-// Frames are independent (k = 0), so a frame block is a sub-array: no _range variant.  Every check comes before anything is
-// queued; an output that is also an input frame or layer would be overwritten by a direct store while uploads that run ahead
-// (or the kernel of another stream) still read it.
-extern "C" int mid_sequence_bilateral(mid_ctx *ctx, const mid_bilateral_params *p, const void *const *host_frames, int n_frames,
-                                      const void *const *host_layers, int n_layers, void *const *host_out, int out_format,
-                                      int overlap, float *timings_ms)
-{
-    Bind b(ctx, nullptr);
-    if (b.rc) return b.rc;
-    if (int rc = refuse_if_recording(ctx->compute, "mid_sequence_bilateral (four streams, host-side waits)")) return rc;
-    MID_REQUIRE(p && host_frames && host_out, "sequence_bilateral: NULL argument");
-    MID_REQUIRE(n_frames >= 1, "sequence_bilateral: n_frames %d < 1", n_frames);
-    MID_REQUIRE(p->width > 0 && p->height > 0, "sequence_bilateral: bad size %dx%d", p->width, p->height);
-    MID_REQUIRE((long)p->width * p->height < (1l << 30), "sequence_bilateral: image too large");
-    MID_REQUIRE(p->spatialSigma > 0.f && p->colorSigma > 0.f, "sequence_bilateral: sigmas must be > 0");
-    MID_REQUIRE(p->radius >= 1 && p->radius <= 24, "sequence_bilateral: radius %d outside 1..24", p->radius);
-    MID_REQUIRE((p->format & ~0xffff) == 0 && fmt_known(fmt_frames(p->format)), "sequence_bilateral: unknown format %d", p->format);
-    if ((p->format >> 8) != 0) {
-        MID_REQUIRE(host_layers != nullptr, "sequence_bilateral: format 0x%x names a guide-layer format, and this call has no guide layers", p->format);
-        MID_REQUIRE(fmt_guide(p->format) >= 0, "sequence_bilateral: unknown guide-layer format code %d in format 0x%x", p->format >> 8, p->format);
-    }
-    MID_REQUIRE(p->layout == MID_LAYOUT_TEXTURE || p->layout == MID_LAYOUT_LINEAR, "sequence_bilateral: unknown layout %d", p->layout);
-    MID_REQUIRE(fmt_known(out_format), "sequence_bilateral: unknown output format %d", out_format);
-    MID_REQUIRE(n_layers >= 0 && n_layers <= kMaxLayers, "sequence_bilateral: n_layers %d outside 0..16", n_layers);
-    MID_REQUIRE(!host_layers || p->layout == MID_LAYOUT_TEXTURE, "sequence_bilateral: layers exist for the texture layout only");
-    for (int i = 0; i < n_frames; ++i) MID_REQUIRE(host_frames[i], "sequence_bilateral: frame %d is NULL", i);
-    const int n_in = host_layers ? n_frames * n_layers : 0;
-    for (int i = 0; i < n_in; ++i)
-        MID_REQUIRE(host_layers[i], "sequence_bilateral: layer %d of frame %d is NULL", i % n_layers, i / n_layers);
-    for (int i = 0; i < n_frames; ++i) MID_REQUIRE(host_out[i], "sequence_bilateral: output %d is NULL", i);
-    std::vector<const void *> inputs;
-    try {
-        inputs.assign(host_frames, host_frames + n_frames);
-        if (n_in) inputs.insert(inputs.end(), host_layers, host_layers + n_in);
-    } catch (...) {
-        return set_error(MID_ERR_INVALID, "sequence_bilateral: no host memory for the alias check");
-    }
-    if (int rc = check_no_alias("sequence_bilateral", "an input frame or layer of this call", inputs.data(), (int)inputs.size(),
-                                (const void *const *)host_out, n_frames)) return rc;
-    const Stage st{"sequence_bilateral", p->width, p->height, fmt_frames(p->format), nullptr, p, nullptr, host_layers, n_layers};
-    return run_pipeline(ctx, st, host_frames, n_frames, 0, 0, n_frames, host_out, out_format, overlap, timings_ms);
-}
-
-// Layer-guided NLM of every frame: mid_sequence_bilateral's schedule and checks with nlm_layers_out as the compute stage.
-extern "C" int mid_sequence_nlm_layers(mid_ctx *ctx, const mid_nlm_params *p, const void *const *host_frames, int n_frames,
-                                       const void *const *host_layers, int n_layers, void *const *host_out, int out_format,
-                                       int overlap, float *timings_ms)
-{
-    Bind b(ctx, nullptr);
-    if (b.rc) return b.rc;
-    if (int rc = refuse_if_recording(ctx->compute, "mid_sequence_nlm_layers (four streams, host-side waits)")) return rc;
-    MID_REQUIRE(p && host_frames && host_out, "sequence_nlm_layers: NULL argument");
-    MID_REQUIRE(n_frames >= 1, "sequence_nlm_layers: n_frames %d < 1", n_frames);
-    if (int rc = nlm_check_params(p)) return rc;
-    MID_REQUIRE(fmt_known(out_format), "sequence_nlm_layers: unknown output format %d", out_format);
-    MID_REQUIRE(n_layers >= 0 && n_layers <= kMaxLayers, "sequence_nlm_layers: n_layers %d outside 0..16", n_layers);
-    MID_REQUIRE(host_layers || n_layers == 0, "sequence_nlm_layers: host_layers is NULL");
-    for (int i = 0; i < n_frames; ++i) MID_REQUIRE(host_frames[i], "sequence_nlm_layers: frame %d is NULL", i);
-    const int n_in = host_layers ? n_frames * n_layers : 0;
-    for (int i = 0; i < n_in; ++i)
-        MID_REQUIRE(host_layers[i], "sequence_nlm_layers: layer %d of frame %d is NULL", i % n_layers, i / n_layers);
-    for (int i = 0; i < n_frames; ++i) MID_REQUIRE(host_out[i], "sequence_nlm_layers: output %d is NULL", i);
-    std::vector<const void *> inputs;
-    try {
-        inputs.assign(host_frames, host_frames + n_frames);
-        if (n_in) inputs.insert(inputs.end(), host_layers, host_layers + n_in);
-    } catch (...) {
-        return set_error(MID_ERR_INVALID, "sequence_nlm_layers: no host memory for the alias check");
-    }
-    if (int rc = check_no_alias("sequence_nlm_layers", "an input frame or layer of this call", inputs.data(), (int)inputs.size(),
-                                (const void *const *)host_out, n_frames)) return rc;
-    const Stage st{"sequence_nlm_layers", p->width, p->height, p->format, nullptr, nullptr, p, n_layers ? host_layers : nullptr, n_layers};
-    return run_pipeline(ctx, st, host_frames, n_frames, 0, 0, n_frames, host_out, out_format, overlap, timings_ms);
-}
-
-// Layer-guided NLM over neighbouring frames: sequence_impl's temporal window (ring of 2k+4 frames, outputs [first, first+count),
-// halo frames uploaded only as far as the windows need them) with mid_sequence_nlm_layers' layer ring and refusals.
-extern "C" int mid_sequence_nlm_layers_temporal(mid_ctx *ctx, const mid_nlm_params *p, const void *const *host_frames, int n_frames,
-                                                const void *const *host_layers, int n_layers, int k, int first, int count,
-                                                void *const *host_out, int out_format, int overlap, float *timings_ms)
-{
-    Bind b(ctx, nullptr);
-    if (b.rc) return b.rc;
-    if (int rc = refuse_if_recording(ctx->compute, "mid_sequence_nlm_layers_temporal (four streams, host-side waits)")) return rc;
-    MID_REQUIRE(p && host_frames && host_out, "sequence_nlm_layers_temporal: NULL argument");
-    MID_REQUIRE(n_frames >= 1 && k >= 0 && 2 * (long)k + 2 <= kMaxFrames, "sequence_nlm_layers_temporal: bad n_frames=%d k=%d", n_frames, k);
-    MID_REQUIRE(first >= 0 && count >= 1 && (long)first + count <= n_frames,
-                "sequence_nlm_layers_temporal: bad range first=%d count=%d n_frames=%d", first, count, n_frames);
-    if (int rc = nlm_check_params(p)) return rc;
-    MID_REQUIRE(fmt_known(out_format), "sequence_nlm_layers_temporal: unknown output format %d", out_format);
-    MID_REQUIRE(n_layers >= 0 && n_layers <= kMaxLayers, "sequence_nlm_layers_temporal: n_layers %d outside 0..16", n_layers);
-    MID_REQUIRE(host_layers || n_layers == 0, "sequence_nlm_layers_temporal: host_layers is NULL");
-    if (int rc = nlm_layers_temporal_fits("sequence_nlm_layers_temporal", n_layers, n_frames, k)) return rc;
-    const int f_lo = first - k < 0 ? 0 : first - k;
-    const int f_hi = first + count - 1 + k > n_frames - 1 ? n_frames - 1 : first + count - 1 + k;
-    std::vector<const void *> inputs;
-    try {
-        inputs.reserve((size_t)(f_hi - f_lo + 1) * (n_layers + 1));
-    } catch (...) {
-        return set_error(MID_ERR_INVALID, "sequence_nlm_layers_temporal: no host memory for the alias check");
-    }
     for (int f = f_lo; f <= f_hi; ++f) {
-        MID_REQUIRE(host_frames[f], "sequence_nlm_layers_temporal: frame %d is NULL", f);
-        inputs.push_back(host_frames[f]);
-        for (int l = 0; l < n_layers; ++l) {
-            MID_REQUIRE(host_layers[(size_t)f * n_layers + l], "sequence_nlm_layers_temporal: layer %d of frame %d is NULL", l, f);
-            inputs.push_back(host_layers[(size_t)f * n_layers + l]);
-        }
+        MID_REQUIRE(host_frames[f], "%s: frame %d is NULL", who, f);
+        for (int l = 0; l < n_layers; ++l) MID_REQUIRE(host_layers[(size_t)f * n_layers + l], "%s: layer %d of frame %d is NULL", who, l, f);
     }
-    for (int i = 0; i < count; ++i) MID_REQUIRE(host_out[i], "sequence_nlm_layers_temporal: output %d is NULL", i);
-    if (int rc = check_no_alias("sequence_nlm_layers_temporal", "an input frame or layer of this call", inputs.data(), (int)inputs.size(),
-                                (const void *const *)host_out, count)) return rc;
-    const Stage st{"sequence_nlm_layers_temporal", p->width, p->height, p->format, nullptr, nullptr, p, n_layers ? host_layers : nullptr,
-                   n_layers, true};
-    return run_pipeline(ctx, st, host_frames, n_frames, k, first, count, host_out, out_format, overlap, timings_ms);
-}
-
-// The bilateral over neighbouring frames: mid_sequence_nlm_layers_temporal's schedule, layer ring and refusals with
-// bilateral_temporal_out as the compute stage; host_layers == NULL is the plain form.  joint: mid_sequence_bilateral_joint, the
-// same call with bilateral_joint_out as the compute stage and its checks (layer_sigma: n_layers floats or NULL).
-static int sequence_bilateral_temporal(mid_ctx *ctx, const char *who, bool joint, const mid_bilateral_params *p, const float *layer_sigma,
-                                       const void *const *host_frames, int n_frames, const void *const *host_layers, int n_layers, int k,
-                                       int first, int count, void *const *host_out, int out_format, int overlap, float *timings_ms)
-{
-    Bind b(ctx, nullptr);
-    if (b.rc) return b.rc;
-    if (int rc = refuse_if_recording(ctx->compute, joint ? "mid_sequence_bilateral_joint (four streams, host-side waits)" : "mid_sequence_bilateral_temporal (four streams, host-side waits)")) return rc;
-    MID_REQUIRE(p && host_frames && host_out, "%s: NULL argument", who);
-    MID_REQUIRE(n_frames >= 1 && k >= 0 && 2 * (long)k + 2 <= kMaxFrames, "%s: bad n_frames=%d k=%d", who, n_frames, k);
-    MID_REQUIRE(first >= 0 && count >= 1 && (long)first + count <= n_frames,
-                "%s: bad range first=%d count=%d n_frames=%d", who, first, count, n_frames);
-    if (int rc = joint ? bilateral_joint_check(p, who, layer_sigma, host_layers != nullptr, n_layers, n_frames, k)
-                       : bilateral_temporal_check(p, who, host_layers != nullptr, n_layers, n_frames, k)) return rc;
-    MID_REQUIRE(fmt_known(out_format), "%s: unknown output format %d", who, out_format);
-    const int f_lo = first - k < 0 ? 0 : first - k;
-    const int f_hi = first + count - 1 + k > n_frames - 1 ? n_frames - 1 : first + count - 1 + k;
+    for (int i = 0; i < count; ++i) MID_REQUIRE(host_out[i], "%s: output %d is NULL", who, i);
+    if (!r.refuse_alias) return MID_OK;
     std::vector<const void *> inputs;
     try {
         inputs.reserve((size_t)(f_hi - f_lo + 1) * (n_layers + 1));
@@ -565,20 +413,125 @@ static int sequence_bilateral_temporal(mid_ctx *ctx, const char *who, bool joint
         return set_error(MID_ERR_INVALID, "%s: no host memory for the alias check", who);
     }
     for (int f = f_lo; f <= f_hi; ++f) {
-        MID_REQUIRE(host_frames[f], "%s: frame %d is NULL", who, f);
         inputs.push_back(host_frames[f]);
-        for (int l = 0; l < n_layers; ++l) {
-            MID_REQUIRE(host_layers[(size_t)f * n_layers + l], "%s: layer %d of frame %d is NULL", who, l, f);
-            inputs.push_back(host_layers[(size_t)f * n_layers + l]);
-        }
+        for (int l = 0; l < n_layers; ++l) inputs.push_back(host_layers[(size_t)f * n_layers + l]);
     }
-    for (int i = 0; i < count; ++i) MID_REQUIRE(host_out[i], "%s: output %d is NULL", who, i);
-    if (int rc = check_no_alias(who, "an input frame or layer of this call", inputs.data(), (int)inputs.size(),
-                                (const void *const *)host_out, count)) return rc;
-    float sigma[kMaxLayers];                  // the joint stage always carries its sigmas: NULL means colorSigma in every layer
-    for (int l = 0; joint && l < n_layers; ++l) sigma[l] = layer_sigma ? layer_sigma[l] : p->colorSigma;
-    const Stage st{who, p->width, p->height, fmt_frames(p->format), nullptr, p, nullptr, host_layers, n_layers, true, joint ? sigma : nullptr};
-    return run_pipeline(ctx, st, host_frames, n_frames, k, first, count, host_out, out_format, overlap, timings_ms);
+    return check_no_alias(who, "an input frame or layer of this call", inputs.data(), (int)inputs.size(), (const void *const *)host_out, count);
+}
+
+// Temporal NLM of output t over the frames t-k..t+k.  Its outputs may be frames of the sequence: every host frame is read once,
+// by its upload, before the first output that could overwrite it is launched -- so this stage alone makes no alias check.
+static int sequence_impl(mid_ctx *ctx, const mid_nlm_params *p, const void *const *host_frames,
+                         int n, int k, int first, int count, void *const *host_out, int out_fmt,
+                         int overlap, float *timings_ms)
+{
+    Bind b(ctx, nullptr);
+    if (b.rc) return b.rc;
+    if (int rc = refuse_if_recording(ctx->compute, "mid_sequence_nlm (four streams, host-side waits)")) return rc;
+    MID_REQUIRE(p, "sequence_nlm: NULL argument");
+    if (int rc = check_sequence({"sequence_nlm", "n", true, false}, host_frames, n, nullptr, 0, k, first, count, host_out, out_fmt)) return rc;
+    MID_REQUIRE(p->width > 0 && p->height > 0, "sequence_nlm: bad size");
+    MID_REQUIRE(fmt_known(p->format), "sequence_nlm: unknown format %d", p->format);
+    const Stage st{"sequence_nlm", p->width, p->height, p->format, 0, nullptr, 0, false, "nlm %d"};
+    // RGBA8 outputs: GetImageFromGPU's u8 conversion (src/main.cpp:97-103) in the kernel's epilogue -- a quarter of the
+    // bytes to write and to download; RGBA16F outputs: round to nearest even there -- half of them
+    auto launch = [&](const void *const *tbl, int n_win, const uint32_t *const *, int k, int t0, int bn, void *const *out, int out_fmt, hipStream_t s) {
+        return nlm_temporal_out(ctx, p, tbl, n_win, k, t0, bn, out, out_fmt, s, 1);
+    };
+    return run_pipeline(ctx, st, launch, host_frames, n, k, first, count, host_out, out_fmt, overlap, timings_ms);
+}
+
+// Frames are independent (k = 0), so a frame block is a sub-array: no _range variant.  A non-NULL layer table with n_layers == 0
+// is the layered form with zero layers (magenta output), as in mid_bilateral_layers.
+extern "C" int mid_sequence_bilateral(mid_ctx *ctx, const mid_bilateral_params *p, const void *const *host_frames, int n_frames,
+                                      const void *const *host_layers, int n_layers, void *const *host_out, int out_format,
+                                      int overlap, float *timings_ms)
+{
+    Bind b(ctx, nullptr);
+    if (b.rc) return b.rc;
+    if (int rc = refuse_if_recording(ctx->compute, "mid_sequence_bilateral (four streams, host-side waits)")) return rc;
+    MID_REQUIRE(p, "sequence_bilateral: NULL argument");
+    if (int rc = bilateral_check_params(p, "sequence_bilateral", host_layers != nullptr)) return rc;
+    MID_REQUIRE(n_layers >= 0 && n_layers <= kMaxLayers, "sequence_bilateral: n_layers %d outside 0..16", n_layers);
+    MID_REQUIRE(!host_layers || p->layout == MID_LAYOUT_TEXTURE, "sequence_bilateral: layers exist for the texture layout only");
+    if (int rc = check_sequence({"sequence_bilateral", "n_frames", false, true}, host_frames, n_frames, host_layers, n_layers, 0, 0, n_frames, host_out, out_format)) return rc;
+    const size_t npix = (size_t)p->width * p->height;
+    const Stage st{"sequence_bilateral", p->width, p->height, fmt_frames(p->format), npix * fmt_bytes(fmt_guide(p->format)), host_layers, n_layers, true, "bilateral %d"};
+    auto launch = [&](const void *const *tbl, int, const uint32_t *const *lt, int, int t0, int bn, void *const *out, int out_fmt, hipStream_t s) {
+        for (int i = 0; i < bn; ++i)              // (k = 0: output t0 + i reads slot t0 + i and its layers only)
+            if (int rc = bilateral_out(ctx, p, tbl[t0 + i], host_layers ? lt + (size_t)(t0 + i) * n_layers : nullptr, n_layers, out[i], out_fmt, s)) return rc;
+        return (int)MID_OK;
+    };
+    return run_pipeline(ctx, st, launch, host_frames, n_frames, 0, 0, n_frames, host_out, out_format, overlap, timings_ms);
+}
+
+// Layer-guided NLM of every frame: mid_sequence_bilateral's schedule with nlm_layers_out as the compute stage.  n_layers == 0 is
+// "no layers", with or without a table.
+extern "C" int mid_sequence_nlm_layers(mid_ctx *ctx, const mid_nlm_params *p, const void *const *host_frames, int n_frames,
+                                       const void *const *host_layers, int n_layers, void *const *host_out, int out_format,
+                                       int overlap, float *timings_ms)
+{
+    Bind b(ctx, nullptr);
+    if (b.rc) return b.rc;
+    if (int rc = refuse_if_recording(ctx->compute, "mid_sequence_nlm_layers (four streams, host-side waits)")) return rc;
+    MID_REQUIRE(p, "sequence_nlm_layers: NULL argument");
+    if (int rc = nlm_check_params(p)) return rc;
+    MID_REQUIRE(n_layers >= 0 && n_layers <= kMaxLayers, "sequence_nlm_layers: n_layers %d outside 0..16", n_layers);
+    MID_REQUIRE(host_layers || n_layers == 0, "sequence_nlm_layers: host_layers is NULL");
+    if (int rc = check_sequence({"sequence_nlm_layers", "n_frames", false, true}, host_frames, n_frames, host_layers, n_layers, 0, 0, n_frames, host_out, out_format)) return rc;
+    const Stage st{"sequence_nlm_layers", p->width, p->height, p->format, (size_t)p->width * p->height * 4, n_layers ? host_layers : nullptr, n_layers, true, "nlm_layers %d"};
+    auto launch = [&](const void *const *tbl, int, const uint32_t *const *lt, int, int t0, int bn, void *const *out, int out_fmt, hipStream_t s) {
+        for (int i = 0; i < bn; ++i)              // (k = 0, as in mid_sequence_bilateral)
+            if (int rc = nlm_layers_out(ctx, p, tbl[t0 + i], lt + (size_t)(t0 + i) * n_layers, n_layers, out[i], out_fmt, s)) return rc;
+        return (int)MID_OK;
+    };
+    return run_pipeline(ctx, st, launch, host_frames, n_frames, 0, 0, n_frames, host_out, out_format, overlap, timings_ms);
+}
+
+// Layer-guided NLM over neighbouring frames: sequence_impl's temporal window (ring of 2k+4 frames, outputs [first, first+count),
+// halo frames uploaded only as far as the windows need them) with mid_sequence_nlm_layers' layer ring.
+extern "C" int mid_sequence_nlm_layers_temporal(mid_ctx *ctx, const mid_nlm_params *p, const void *const *host_frames, int n_frames,
+                                                const void *const *host_layers, int n_layers, int k, int first, int count,
+                                                void *const *host_out, int out_format, int overlap, float *timings_ms)
+{
+    Bind b(ctx, nullptr);
+    if (b.rc) return b.rc;
+    if (int rc = refuse_if_recording(ctx->compute, "mid_sequence_nlm_layers_temporal (four streams, host-side waits)")) return rc;
+    MID_REQUIRE(p, "sequence_nlm_layers_temporal: NULL argument");
+    if (int rc = nlm_check_params(p)) return rc;
+    MID_REQUIRE(n_layers >= 0 && n_layers <= kMaxLayers, "sequence_nlm_layers_temporal: n_layers %d outside 0..16", n_layers);
+    MID_REQUIRE(host_layers || n_layers == 0, "sequence_nlm_layers_temporal: host_layers is NULL");
+    if (int rc = check_sequence({"sequence_nlm_layers_temporal", "n_frames", true, true}, host_frames, n_frames, host_layers, n_layers, k, first, count, host_out, out_format)) return rc;
+    if (int rc = nlm_layers_temporal_fits("sequence_nlm_layers_temporal", n_layers, n_frames, k)) return rc;
+    const Stage st{"sequence_nlm_layers_temporal", p->width, p->height, p->format, (size_t)p->width * p->height * 4, n_layers ? host_layers : nullptr, n_layers, true, "nlm_layers %d"};
+    auto launch = [&](const void *const *tbl, int n_win, const uint32_t *const *lt, int k, int t0, int bn, void *const *out, int out_fmt, hipStream_t s) {
+        return nlm_layers_temporal_out(ctx, p, tbl, lt, n_layers, n_win, k, t0, bn, out, out_fmt, s);
+    };
+    return run_pipeline(ctx, st, launch, host_frames, n_frames, k, first, count, host_out, out_format, overlap, timings_ms);
+}
+
+// The bilateral over neighbouring frames: mid_sequence_nlm_layers_temporal's schedule and layer ring; host_layers == NULL is the
+// plain form, a table with n_layers == 0 the layered form with zero layers.
+// joint: mid_sequence_bilateral_joint, the same call with bilateral_joint_out as the compute stage and its checks (layer_sigma:
+// n_layers floats or NULL for colorSigma in every layer).
+static int sequence_bilateral_temporal(mid_ctx *ctx, const char *who, bool joint, const mid_bilateral_params *p, const float *layer_sigma,
+                                       const void *const *host_frames, int n_frames, const void *const *host_layers, int n_layers, int k,
+                                       int first, int count, void *const *host_out, int out_format, int overlap, float *timings_ms)
+{
+    Bind b(ctx, nullptr);
+    if (b.rc) return b.rc;
+    if (int rc = refuse_if_recording(ctx->compute, joint ? "mid_sequence_bilateral_joint (four streams, host-side waits)" : "mid_sequence_bilateral_temporal (four streams, host-side waits)")) return rc;
+    MID_REQUIRE(p, "%s: NULL argument", who);
+    if (int rc = joint ? bilateral_joint_check(p, who, layer_sigma, host_layers != nullptr, n_layers, n_frames, k)
+                       : bilateral_temporal_check(p, who, host_layers != nullptr, n_layers, n_frames, k)) return rc;
+    if (int rc = check_sequence({who, "n_frames", true, true}, host_frames, n_frames, host_layers, n_layers, k, first, count, host_out, out_format)) return rc;
+    const size_t npix = (size_t)p->width * p->height;
+    const Stage st{who, p->width, p->height, fmt_frames(p->format), npix * fmt_bytes(fmt_guide(p->format)), host_layers, n_layers, true, "bilateral %d"};
+    auto launch = [&](const void *const *tbl, int n_win, const uint32_t *const *lt, int k, int t0, int bn, void *const *out, int out_fmt, hipStream_t s) {
+        if (joint) return bilateral_joint_out(ctx, p, layer_sigma, tbl, lt, n_layers, n_win, k, t0, bn, out, out_fmt, s);
+        return bilateral_temporal_out(ctx, p, tbl, host_layers ? lt : nullptr, n_layers, n_win, k, t0, bn, out, out_fmt, s);
+    };
+    return run_pipeline(ctx, st, launch, host_frames, n_frames, k, first, count, host_out, out_format, overlap, timings_ms);
 }
 
 extern "C" int mid_sequence_bilateral_temporal(mid_ctx *ctx, const mid_bilateral_params *p, const void *const *host_frames, int n_frames,
