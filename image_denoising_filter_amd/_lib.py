@@ -91,6 +91,8 @@ _SIGNATURES = {
                                               ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_pp, ctypes.c_int, _P]),
     "mid_bilateral_joint": (ctypes.c_int, [_P, ctypes.POINTER(BilateralParams), ctypes.POINTER(ctypes.c_float), c_void_pp, c_void_pp,
                                            ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_pp, ctypes.c_int, _P]),
+    "mid_nlm_joint": (ctypes.c_int, [_P, ctypes.POINTER(NlmParams), ctypes.POINTER(ctypes.c_float), c_void_pp, c_void_pp,
+                                     ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_pp, ctypes.c_int, _P]),
     "mid_normalize": (ctypes.c_int, [_P, ctypes.POINTER(NormalizeParams), _P, _P, _P]),
     "mid_unpack_u8": (ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_int, _P, _P]),
     "mid_pack_u8": (ctypes.c_int, [_P, _P, ctypes.c_size_t, _P, _P]),
@@ -120,6 +122,9 @@ _SIGNATURES = {
     "mid_sequence_bilateral_joint": (ctypes.c_int, [_P, ctypes.POINTER(BilateralParams), ctypes.POINTER(ctypes.c_float), c_void_pp, ctypes.c_int,
                                                     c_void_pp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_pp, ctypes.c_int,
                                                     ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
+    "mid_sequence_nlm_joint": (ctypes.c_int, [_P, ctypes.POINTER(NlmParams), ctypes.POINTER(ctypes.c_float), c_void_pp, ctypes.c_int,
+                                              c_void_pp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_pp, ctypes.c_int,
+                                              ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
     "mid_nlm_multiframe": (ctypes.c_int, [_P, ctypes.POINTER(NlmParams), _P, c_void_pp, ctypes.c_int, _P, ctypes.c_int,
                                           ctypes.POINTER(ctypes.c_float)]),
     "mid_pipe_last_timeline": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int),

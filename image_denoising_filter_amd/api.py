@@ -372,6 +372,28 @@ class Context:
                "mid_nlm_layers_temporal")
         return [self.download(d, (h, w, 4), out_dtype) for d in d_out]
 
+    def nlm_joint(self, frames, layers, hs=None, k=0, first=0, count=None, hparam=0.5, search=(-7, 7), patch=(-3, 3), out_dtype=None):
+        """Joint layer-guided NLM over the frames t-k..t+k for `count` output frames (mid_nlm_joint): one weight per search
+        offset from the patch distances of all guide layers.  layers: one list per frame of equally many (1..16) uint8 (h, w, 4)
+        guide layers; hs: one h per layer, or None for hparam in every layer; out_dtype: None = float32, uint8 or float16."""
+        frames = _same_frames(frames, "nlm_joint")
+        n = len(frames)
+        count = n - first if count is None else count
+        h, w = frames[0].shape[:2]
+        n_layers, flat = _flat_layers(layers, n, h, w, "nlm_joint")
+        out_dtype = _out_dtype(False, out_dtype)
+        out_fmt = {np.dtype(np.uint8): FMT_RGBA8, np.dtype(np.float16): FMT_RGBA16F, np.dtype(np.float32): FMT_RGBA32F}[out_dtype]
+        d_fr = [self.upload(f) for f in frames]
+        d_l = [self.upload(l) for l in flat]
+        d_out = [self.alloc(w * h * 4 * out_dtype.itemsize) for _ in range(max(count, 0))]
+        p = NlmParams(w, h, hparam, search[0], search[1], patch[0], patch[1], _fmt_of(frames[0]))
+        _check(lib.mid_nlm_joint(self.handle, ctypes.byref(p), _layer_sigmas(hs, n_layers, "nlm_joint", "values of h"),
+                                 (ctypes.c_void_p * n)(*[d.ptr for d in d_fr]),
+                                 (ctypes.c_void_p * max(len(d_l), 1))(*[d.ptr for d in d_l]), n_layers, n, k, first, count,
+                                 (ctypes.c_void_p * max(len(d_out), 1))(*[d.ptr for d in d_out]), out_fmt, None),
+               "mid_nlm_joint")
+        return [self.download(d, (h, w, 4), out_dtype) for d in d_out]
+
     def bilateral_pair_accum(self, target, neighbour, W, radius, sigma_s=2.0, sigma_c=0.2):
         """One plain pair dispatch: the range weight between the `target` frame's centre and the `neighbour` frame's taps, the
         colour from `neighbour`: returns W + its sums (mid_bilateral_pair_accum)."""
@@ -512,7 +534,7 @@ class Context:
                 raise ValueError(f"{n} frames x {n_layers} layers, {len(hlayers)} layer pointers given")
             layers = ((ctypes.c_void_p * max(len(hlayers), 1))(*hlayers), n_layers)
         out_fmt = [_OUT_FMT[_out_dtype(False, dt)] for dt in out_dtype]
-        pre = [_layer_sigmas(sg, layers[1], where[len("mid_"):]) for sg in sigmas]
+        pre = [_layer_sigmas(sg, layers[1], where[len("mid_"):], "values of h" if "nlm" in entry else "sigmas") for sg in sigmas]
         t = (ctypes.c_float * 3)()
         # (the output table holds at least one entry, so that count = 0 still reaches the library's refusal)
         _check(getattr(lib, entry)(self.handle, ctypes.byref(prm), *pre, (ctypes.c_void_p * n)(*hin), n, *layers, *window,
@@ -694,13 +716,36 @@ class Context:
             frames, layers, _GUIDE_DTYPES, first, count, pinned, pinned_out, out_dtype)
 
 
-def _layer_sigmas(sigmas, n_layers, who):
-    """The layer_sigma argument of the joint bilateral: None, or a C array of n_layers floats."""
+    def sequence_nlm_joint_pinned(self, hin, hout, w, h, fmt, hlayers, n_layers, hs=None, k=0, first=0, count=None, overlap=True,
+                                  hparam=0.5, search=(-7, 7), patch=(-3, 3), out_dtype=None):
+        """mid_sequence_nlm_joint on host pointers the caller already holds: nothing but the C call.  hin, hlayers, hout as for
+        sequence_nlm_layers_temporal_pinned; hs: n_layers values of h or None.
+        Returns (wall_ms of the whole call, kernel_ms, copy_ms)."""
+        count = len(hin) - first if count is None else count
+        return self._sequence_call("mid_sequence_nlm_joint", "mid_sequence_nlm_joint",
+                                   NlmParams(w, h, hparam, search[0], search[1], patch[0], patch[1], fmt), hin, hout, count,
+                                   f"{count} outputs", overlap, layers=(hlayers, n_layers), window=(k, first, count), out_dtype=(out_dtype,),
+                                   sigmas=(hs,))
+
+    def sequence_nlm_joint(self, frames, layers, hs=None, k=0, first=0, count=None, overlap=True, hparam=0.5, search=(-7, 7),
+                           patch=(-3, 3), pinned=True, pinned_out=True, out_dtype=None):
+        """Outputs [first, first+count) of an animation through the overlapped pipeline with joint layer-guided NLM over the
+        frames t-k..t+k as its compute stage (mid_sequence_nlm_joint): output t is ctx.nlm_joint(frames, layers, hs, k) of frame
+        t in out_dtype.  layers, pinned, pinned_out, out_dtype as for sequence_nlm_layers.
+        Returns (outputs, (wall_ms, kernel_ms, copy_ms))."""
+        out_dtype = _out_dtype(False, out_dtype)
+        return self._sequence_host("sequence_nlm_joint", lambda hin, hout, w, h, fmt, hlayers, n_layers, count: self.sequence_nlm_joint_pinned(
+            hin, hout, w, h, fmt, hlayers, n_layers, hs, k, first, count, overlap, hparam, search, patch, out_dtype),
+            frames, layers, (np.uint8,), first, count, pinned, pinned_out, out_dtype)
+
+
+def _layer_sigmas(sigmas, n_layers, who, noun="sigmas"):
+    """The layer_sigma argument of the joint bilateral (layer_h of joint NLM, noun="values of h"): None, or a C array of n_layers floats."""
     if sigmas is None:
         return None
     sigmas = [float(s) for s in sigmas]
     if len(sigmas) != n_layers:
-        raise ValueError(f"{who}: {len(sigmas)} sigmas for {n_layers} layers")
+        raise ValueError(f"{who}: {len(sigmas)} {noun} for {n_layers} layers")
     return (ctypes.c_float * max(n_layers, 1))(*sigmas)
 
 

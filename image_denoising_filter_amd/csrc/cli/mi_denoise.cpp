@@ -52,6 +52,7 @@ struct Options {
     float sigma_s = 2.0f, sigma_c = 0.2f;      // src/main.cpp:806,875
     std::vector<float> sigma_layers;           // the joint modes: one range sigma per layer in discovery order (empty: sigma_c for all)
     float nlm_h = 0.5f;             // src/main.cpp:870
+    std::vector<float> h_layers;    // the joint NLM modes: one h per layer in discovery order (empty: nlm_h for all)
     int search_lo = -7, search_hi = 7, patch_lo = -3, patch_hi = 3;   // shaders/nonlocal.comp:5-6, half-open
     int temporal_k = -1;            // <0: the reference's frame list; >=0: window t-k..t+k of the sorted sequence
     int cpu_radius = 10;            // windowSize, src/main.cpp:1819
@@ -59,9 +60,9 @@ struct Options {
     bool cpu_blue_bug = true;       // pow(texColor.b - texColor.b, 2), src/main.cpp:1850
     std::vector<int> cpu_threads = {1, 8};     // src/main.cpp:1979,1984
     bool run_gpu = true, run_cpu = true;
-    std::string modes = "all";      // comma list of: bilateral,layers,linear,nlm,multiframe,overlap (all of them: "all"), nlm-layers, joint
+    std::string modes = "all";      // comma list of: bilateral,layers,linear,nlm,multiframe,overlap (all of them: "all"), nlm-layers, joint, nlm-joint
     bool animation = false;         // new capability: temporal NLM of EVERY frame of the sequence
-    std::string animation_filter = "nlm";   // animation mode: nlm | bilateral | linear | layers (the bilateral of every frame) | nlm-layers | nlm-layers-temporal | bilateral-temporal | layers-temporal | joint | joint-temporal
+    std::string animation_filter = "nlm";   // animation mode: nlm | bilateral | linear | layers (the bilateral of every frame) | nlm-layers | nlm-layers-temporal | bilateral-temporal | layers-temporal | joint | joint-temporal | nlm-joint | nlm-joint-temporal
     int gpus = 1;                   // animation mode: frame blocks over this many devices
     bool share_device = false;      // animation mode: every block on --device (rehearsal of --gpus N on fewer devices)
     bool halo_rccl = false;         // animation mode: blocks resident in HBM, halo frames GPU to GPU over RCCL (mid_nlm_temporal_sharded)
@@ -77,7 +78,7 @@ struct Options {
     } while (0)
 
 // --animation-filter, parsed once: the mid_sequence_* family a value runs, what that family reads, and the words of the value.
-enum SeqFamily { SEQ_NLM, SEQ_BILATERAL, SEQ_NLM_LAYERS, SEQ_NLM_LAYERS_TEMPORAL, SEQ_BILATERAL_TEMPORAL, SEQ_BILATERAL_JOINT };
+enum SeqFamily { SEQ_NLM, SEQ_BILATERAL, SEQ_NLM_LAYERS, SEQ_NLM_LAYERS_TEMPORAL, SEQ_BILATERAL_TEMPORAL, SEQ_BILATERAL_JOINT, SEQ_NLM_JOINT };
 struct AnimationFilter {
     const char *name;
     SeqFamily family;
@@ -101,6 +102,8 @@ static const AnimationFilter kAnimationFilters[] = {
     {"layers-temporal", SEQ_BILATERAL_TEMPORAL, true, true, false, "nonlinear-bialteral-layers-multiframe-", "bilateral", "nonlinear bialteral + layers, multiframe"},
     {"joint", SEQ_BILATERAL_JOINT, true, false, false, "nonlinear-bialteral-joint-", "joint bilateral", "joint bialteral"},
     {"joint-temporal", SEQ_BILATERAL_JOINT, true, true, false, "nonlinear-bialteral-joint-multiframe-", "joint bilateral", "joint bialteral, multiframe"},
+    {"nlm-joint", SEQ_NLM_JOINT, true, false, false, "nonlinear-nlm-joint-", "joint nonlocal", "joint nonlocal"},
+    {"nlm-joint-temporal", SEQ_NLM_JOINT, true, true, false, "nonlinear-nlm-joint-multiframe-", "joint nonlocal", "joint nonlocal, multiframe"},
 };
 static const AnimationFilter *animation_filter(const std::string &name)
 {
@@ -218,14 +221,17 @@ class DenoiseApplication {
 
     // The joint modes' range sigmas, one per layer file in discovery (sorted) order: --sigma-layers, or --sigma-c for all of them.
     // Prints the banner's `layer <file> sigma <value>` lines.
-    std::vector<float> layer_sigmas(const std::vector<std::string> &names) const
+    // nlm: the joint NLM modes' h per layer instead -- --h-layers, or --nlm-h for all of them; `layer <file> h <value>` lines.
+    std::vector<float> layer_sigmas(const std::vector<std::string> &names, bool nlm = false) const
     {
-        if (!opt.sigma_layers.empty() && opt.sigma_layers.size() != names.size())
-            throw std::runtime_error("--sigma-layers gives " + std::to_string(opt.sigma_layers.size()) + " sigma(s), but " +
-                                     std::to_string(names.size()) + " layer file(s) were found: one sigma per layer, in sorted order");
-        std::vector<float> s(names.size(), opt.sigma_c);
-        if (!opt.sigma_layers.empty()) s = opt.sigma_layers;
-        for (size_t l = 0; l < names.size(); ++l) std::cout << "\tlayer " << names[l] << " sigma " << s[l] << "\n";
+        const std::vector<float> &given = nlm ? opt.h_layers : opt.sigma_layers;
+        const std::string option = nlm ? "--h-layers" : "--sigma-layers", word = nlm ? "h" : "sigma";
+        if (!given.empty() && given.size() != names.size())
+            throw std::runtime_error(option + " gives " + std::to_string(given.size()) + " " + (nlm ? "value" : "sigma") + "(s), but " +
+                                     std::to_string(names.size()) + " layer file(s) were found: one " + word + " per layer, in sorted order");
+        std::vector<float> s(names.size(), nlm ? opt.nlm_h : opt.sigma_c);
+        if (!given.empty()) s = given;
+        for (size_t l = 0; l < names.size(); ++l) std::cout << "\tlayer " << names[l] << " " << word << " " << s[l] << "\n";
         return s;
     }
 
@@ -297,7 +303,8 @@ public:
     }
 
     // RunOnGPU, src/main.cpp:1307-1730
-    // joint (with useLayers): the joint bilateral, one weight from all layers (mid_bilateral_joint), instead of the sum of one filter per layer
+    // joint (with useLayers): the joint bilateral (mid_bilateral_joint) or, with nlmFilter, joint layer-guided NLM (mid_nlm_joint): one weight from
+    // all layers instead of the sum of one filter per layer
     void RunOnGPU(bool nlmFilter, bool nonlinear, bool multiframe, bool execAndCopyOverlap, bool useLayers, bool joint = false)
     {
         const bool linear = !nonlinear;                                              // :1311
@@ -398,8 +405,9 @@ public:
                 std::vector<float> jointSigma;
                 if (joint) {
                     if (layerNames.empty() || layerNames.size() > 16)
-                        throw std::runtime_error(opt.image + ": " + std::to_string(layerNames.size()) + " layer file(s) found, --modes joint needs 1..16");
-                    jointSigma = layer_sigmas(layerNames);
+                        throw std::runtime_error(opt.image + ": " + std::to_string(layerNames.size()) + " layer file(s) found, --modes " +
+                                                 (nlmFilter ? "nlm-joint" : "joint") + " needs 1..16");
+                    jointSigma = layer_sigmas(layerNames, nlmFilter);
                 }
                 for_each_file(0, (int)layerNames.size(), [&](int i) {
                     layerImgs[i] = load(layerNames[i], nlmFilter, pin, lfmt == MID_FMT_RGBA16F);
@@ -416,7 +424,15 @@ public:
                     timed(m_transferMs, [&] { MID_CHECK(mid_memcpy_h2d(ctx, d, l.data(), l.size(), nullptr)); });
                     MID_CHECK(mid_stream_sync(ctx, nullptr));             // (the decoded layers are released with `layerImgs`)
                 }
-                if (nlmFilter) {                                                                // the same loop with nonlocal.comp
+                if (nlmFilter && joint) {                                                       // one weight from all layers (mid_nlm_joint)
+                    mid_nlm_params p{w, h, opt.nlm_h, opt.search_lo, opt.search_hi, opt.patch_lo, opt.patch_hi, fmt};
+                    const void *fr[1] = {dIn};
+                    void *ou[1] = {dOut};
+                    timed(m_execMs, [&] {
+                        MID_CHECK(mid_nlm_joint(ctx, &p, jointSigma.data(), fr, (const uint32_t *const *)dLayers.data(), (int)dLayers.size(), 1, 0, 0, 1,
+                                                ou, MID_FMT_RGBA32F, nullptr));
+                    });
+                } else if (nlmFilter) {                                                         // the same loop with nonlocal.comp
                     mid_nlm_params p{w, h, opt.nlm_h, opt.search_lo, opt.search_hi, opt.patch_lo, opt.patch_hi, fmt};
                     timed(m_execMs, [&] {
                         MID_CHECK(mid_nlm_layers(ctx, &p, dIn, (const uint32_t *const *)dLayers.data(), (int)dLayers.size(), (mid_pixel *)dOut, nullptr));
@@ -496,7 +512,7 @@ public:
         // the schedule of layers-temporal)
         const AnimationFilter &af = *animation_filter(opt.animation_filter);        // (main has refused unknown names)
         const int n = (int)frameNames.size(), k = !af.temporal ? 0 : opt.temporal_k < 0 ? 2 : opt.temporal_k;
-        const bool use_layers = af.layers, nlm_guides = af.family == SEQ_NLM_LAYERS || af.family == SEQ_NLM_LAYERS_TEMPORAL;
+        const bool use_layers = af.layers, nlm_guides = af.family == SEQ_NLM_LAYERS || af.family == SEQ_NLM_LAYERS_TEMPORAL || af.family == SEQ_NLM_JOINT;
         if (!af.windowed() && opt.halo_rccl)
             throw std::runtime_error("--halo rccl is not available with --animation-filter " + opt.animation_filter +
                                      ": its frames read no other frame, there is no halo to exchange");
@@ -522,7 +538,8 @@ public:
         for (auto &fl : frameLayers) allLayers.insert(allLayers.end(), fl.begin(), fl.end());
         if (nlm_guides) for (const std::string &ln : allLayers) if (is_hdr(ln)) (void)load(ln, true);   // refuses, saying why
         const int lfmt = layer_format(allLayers);
-        const std::vector<float> jointSigma = af.family == SEQ_BILATERAL_JOINT ? layer_sigmas(frameLayers[0]) : std::vector<float>();   // (every frame has frame 0's layers)
+        const std::vector<float> jointSigma = af.family == SEQ_BILATERAL_JOINT ? layer_sigmas(frameLayers[0])            // (every frame has frame 0's layers)
+                                              : af.family == SEQ_NLM_JOINT ? layer_sigmas(frameLayers[0], true) : std::vector<float>();
         std::cout << "\tloading " << n << " frames\n";
         // Frames are decoded STRAIGHT INTO pinned host memory (mid_image_load_pinned) and the results land in pinned
         // buffers too, so every copy of the pipeline is a true asynchronous DMA -- the reference memcpy's its decoded
@@ -655,6 +672,8 @@ public:
                 MID_CHECK(mid_sequence_nlm_layers_temporal(c, &np, frames, nf, lp, L, kk, start, count, outs, out_fmt, 1, t)); break;
             case SEQ_BILATERAL_JOINT:      // one weight from all layers
                 MID_CHECK(mid_sequence_bilateral_joint(c, &bpp, jointSigma.data(), frames, nf, lp, L, kk, start, count, outs, out_fmt, 1, t)); break;
+            case SEQ_NLM_JOINT:            // one patch weight from all layers (jointSigma: the h of each layer)
+                MID_CHECK(mid_sequence_nlm_joint(c, &np, jointSigma.data(), frames, nf, lp, L, kk, start, count, outs, out_fmt, 1, t)); break;
             case SEQ_BILATERAL_TEMPORAL:   // plain or with the layers
                 MID_CHECK(mid_sequence_bilateral_temporal(c, &bpp, frames, nf, lp, L, kk, start, count, outs, out_fmt, 1, t)); break;
             case SEQ_NLM:     // (one entry per output format; the casts only name the element type the library stores: every pointer of outs is a void *)
@@ -858,7 +877,11 @@ static void usage()
         "                            and joint (not part of all): the joint (cross) bilateral, ONE weight per tap from all of the\n"
         "                            image's layers -- the product of the spatial term and one range term per layer, each layer\n"
         "                            with its own sigma (--sigma-layers, else --sigma-c for all; --radius / --sigma-s apply),\n"
-        "                            output output-nonlinear-bialteral-joint.{png,exr}.\n"
+        "                            output output-nonlinear-bialteral-joint.{png,exr};\n"
+        "                            and nlm-joint (not part of all): joint layer-guided NLM, ONE weight per search offset from the\n"
+        "                            patch distances of all of the image's layers, each layer with its own h (--h-layers, else\n"
+        "                            --nlm-h for all; --search / --patch apply; .png layers only, as nlm-layers),\n"
+        "                            output output-nonlinear-nlm-joint.{png,exr}.\n"
         "                            Layer files: .png (RGBA8) -- or, for the bilateral modes only (layers and joint here, layers,\n"
         "                            layers-temporal, joint and joint-temporal under --animation-filter), .exr: normals, depth, HDR albedo as rendered, read as\n"
         "                            RGBA32F, or as RGBA16F with --half; all layers of a run must have one format; nlm-layers and\n"
@@ -871,6 +894,9 @@ static void usage()
         "                            is refused.  Default: --sigma-c for every layer.  Scale it to the layer's units: normals ~0.3,\n"
         "                            depth in scene units, HDR albedo ~0.5\n"
         "  --nlm-h H                 NLM filtering parameter (default 0.5)\n"
+        "  --h-layers A,B,...        the joint NLM modes: one h per layer, in the sorted order the layer files are found in (the run\n"
+        "                            prints one `layer <file> h <value>` line each); a count other than the layer count is refused.\n"
+        "                            Default: --nlm-h for every layer\n"
         "  --search LO,HI --patch LO,HI   half-open NLM ranges (default -7,7 and -3,3; 21x21/7x7 is -10,11 and -3,4)\n"
         "  --temporal-k K            multiframe: frames t-K..t+K of the sorted sequence instead of the reference's list\n"
         "  --animation               denoise EVERY sibling frame with temporal NLM (window +-K, default 2) instead of the mode list\n"
@@ -894,7 +920,12 @@ static void usage()
         "                            --sigma-layers) of every frame alone (joint ignores --temporal-k) or over the frames t-K..t+K\n"
         "                            (K = --temporal-k, default 2; the layer rules, frame blocks and halo of layers-temporal),\n"
         "                            outputs output-animation-nonlinear-bialteral-joint-* and\n"
-        "                            output-animation-nonlinear-bialteral-joint-multiframe-*\n"
+        "                            output-animation-nonlinear-bialteral-joint-multiframe-*;\n"
+        "                            or nlm-joint / nlm-joint-temporal: joint layer-guided NLM (one weight from all of a frame's\n"
+        "                            layers, --h-layers; .png layers only) of every frame alone (nlm-joint ignores --temporal-k) or\n"
+        "                            over the frames t-K..t+K (K = --temporal-k, default 2; frame blocks and halo of\n"
+        "                            nlm-layers-temporal, not with --halo rccl), outputs output-animation-nonlinear-nlm-joint-* and\n"
+        "                            output-animation-nonlinear-nlm-joint-multiframe-*\n"
         "  --gpus N                  animation mode: split the sequence into N frame blocks, one per device\n"
         "  --halo host|rccl          animation mode with --gpus N: 'host' (default) streams every block plus its K halo frames from host\n"
         "                            memory through the overlapped pipeline; 'rccl' keeps each block resident in its GPU's HBM and\n"
@@ -943,6 +974,13 @@ int main(int argc, char **argv)
             if (opt.sigma_layers.empty()) { std::cerr << "--sigma-layers needs a comma list of sigmas\n"; usage(); return EXIT_FAILURE; }
         }
         else if (a == "--nlm-h") opt.nlm_h = (float)atof(next());
+        else if (a == "--h-layers") {
+            opt.h_layers.clear();
+            const std::string s = next();
+            size_t pos = 0;
+            while (pos < s.size()) { size_t c = s.find(',', pos); if (c == std::string::npos) c = s.size(); opt.h_layers.push_back((float)atof(s.substr(pos, c - pos).c_str())); pos = c + 1; }
+            if (opt.h_layers.empty()) { std::cerr << "--h-layers needs a comma list of values\n"; usage(); return EXIT_FAILURE; }
+        }
         else if (a == "--search") { if (!pair_arg(next(), opt.search_lo, opt.search_hi)) { usage(); return EXIT_FAILURE; } }
         else if (a == "--patch") { if (!pair_arg(next(), opt.patch_lo, opt.patch_hi)) { usage(); return EXIT_FAILURE; } }
         else if (a == "--temporal-k") opt.temporal_k = atoi(next());
@@ -1000,6 +1038,7 @@ int main(int argc, char **argv)
             // (not part of `all`: the reference has no NLM with layers, and the default run writes exactly the reference's files)
             if (listed("nlm-layers")) { std::cout << "######\nRunning on GPU (nonlocal + layers)\n######\n"; app.RunOnGPU(true, true, false, false, true); print_time(); }
             if (listed("joint")) { std::cout << "######\nRunning on GPU (joint bialteral)\n######\n"; app.RunOnGPU(false, true, false, false, true, true); print_time(); }
+            if (listed("nlm-joint")) { std::cout << "######\nRunning on GPU (joint nonlocal)\n######\n"; app.RunOnGPU(true, true, false, false, true, true); print_time(); }
         }
         if (opt.run_cpu) {
             for (int threads : opt.cpu_threads) {

@@ -187,6 +187,14 @@ int nlm_layers_temporal_out(mid_ctx *ctx, const mid_nlm_params *p, const void *c
                             int n_layers, int n_frames, int k, int first, int count, void *const *out, int out_fmt, hipStream_t s);
 int nlm_layers_temporal_fits(const char *who, int n_layers, int n_frames, int k);
 
+// mid_nlm_joint without its checks (the caller has made them), one launch per output frame on `s`: nlm_joint.hip; used by the
+// frame pipeline (mid_sequence_nlm_joint), not exported.  layer_h: n_layers host floats, or NULL for p->filteringParameter in
+// every layer.  nlm_joint_check: what both entry points check after their own tables -- nlm_check_params, n_layers in 1..16, a
+// layer table, n_frames >= 1, k >= 0, the pointer limit of one launch (nlm_layers_temporal_fits), every h > 0.
+int nlm_joint_out(mid_ctx *ctx, const mid_nlm_params *p, const float *layer_h, const void *const *frames, const uint32_t *const *layers,
+                  int n_layers, int n_frames, int k, int first, int count, void *const *out, int out_fmt, hipStream_t s);
+int nlm_joint_check(const mid_nlm_params *p, const char *who, const float *layer_h, bool have_layers, int n_layers, int n_frames, int k);
+
 // The parameter checks of mid_bilateral (size, sigmas, radius, format, layout): bilateral.hip, shared with bilateral_temporal.hip.
 // guide_ok: the entry point reads guide layers of the bilateral family, so the format word may carry their format
 // (MID_FMT_WITH_GUIDE); everywhere else a non-zero guide field is refused.

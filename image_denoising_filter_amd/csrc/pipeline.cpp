@@ -11,7 +11,7 @@
 //              The schedule knows a stage only by its description (struct Stage: sizes, layers, output rule, marker name) and by
 //              one callable that queues a batch's outputs; each entry point supplies that callable around its own filter --
 //              temporal NLM (mid_sequence_nlm*), the bilateral plain or layer-guided (mid_sequence_bilateral, k = 0), layer-guided
-//              NLM (mid_sequence_nlm_layers, k = 0; mid_sequence_nlm_layers_temporal), the bilateral and the joint bilateral over
+//              NLM (mid_sequence_nlm_layers, k = 0; mid_sequence_nlm_layers_temporal; mid_sequence_nlm_joint), the bilateral and the joint bilateral over
 //              neighbouring frames (mid_sequence_bilateral_temporal, mid_sequence_bilateral_joint) -- after check_sequence, the one
 //              statement of the argument checks they share
 //   download : hipMemcpyAsync device out slot t % 4 -> host   (RGBA32F and RGBA16F outputs, and RGBA8 outputs in pageable memory)
@@ -506,6 +506,25 @@ extern "C" int mid_sequence_nlm_layers_temporal(mid_ctx *ctx, const mid_nlm_para
     const Stage st{"sequence_nlm_layers_temporal", p->width, p->height, p->format, (size_t)p->width * p->height * 4, n_layers ? host_layers : nullptr, n_layers, true, "nlm_layers %d"};
     auto launch = [&](const void *const *tbl, int n_win, const uint32_t *const *lt, int k, int t0, int bn, void *const *out, int out_fmt, hipStream_t s) {
         return nlm_layers_temporal_out(ctx, p, tbl, lt, n_layers, n_win, k, t0, bn, out, out_fmt, s);
+    };
+    return run_pipeline(ctx, st, launch, host_frames, n_frames, k, first, count, host_out, out_format, overlap, timings_ms);
+}
+
+// Joint layer-guided NLM over neighbouring frames: mid_sequence_nlm_layers_temporal's schedule and layer ring (4 B per texel) with
+// nlm_joint_out as the compute stage and its checks (layer_h: n_layers floats, or NULL for filteringParameter in every layer).
+extern "C" int mid_sequence_nlm_joint(mid_ctx *ctx, const mid_nlm_params *p, const float *layer_h, const void *const *host_frames,
+                                      int n_frames, const void *const *host_layers, int n_layers, int k, int first, int count,
+                                      void *const *host_out, int out_format, int overlap, float *timings_ms)
+{
+    Bind b(ctx, nullptr);
+    if (b.rc) return b.rc;
+    if (int rc = refuse_if_recording(ctx->compute, "mid_sequence_nlm_joint (four streams, host-side waits)")) return rc;
+    MID_REQUIRE(p, "sequence_nlm_joint: NULL argument");
+    if (int rc = nlm_joint_check(p, "sequence_nlm_joint", layer_h, host_layers != nullptr, n_layers, n_frames, k)) return rc;
+    if (int rc = check_sequence({"sequence_nlm_joint", "n_frames", true, true}, host_frames, n_frames, host_layers, n_layers, k, first, count, host_out, out_format)) return rc;
+    const Stage st{"sequence_nlm_joint", p->width, p->height, p->format, (size_t)p->width * p->height * 4, host_layers, n_layers, true, "nlm_joint %d"};
+    auto launch = [&](const void *const *tbl, int n_win, const uint32_t *const *lt, int k, int t0, int bn, void *const *out, int out_fmt, hipStream_t s) {
+        return nlm_joint_out(ctx, p, layer_h, tbl, lt, n_layers, n_win, k, t0, bn, out, out_fmt, s);
     };
     return run_pipeline(ctx, st, launch, host_frames, n_frames, k, first, count, host_out, out_format, overlap, timings_ms);
 }

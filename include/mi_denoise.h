@@ -408,6 +408,71 @@ int mid_sequence_bilateral_joint(mid_ctx *ctx, const mid_bilateral_params *p, co
                                  const void *const *host_frames, int n_frames, const void *const *host_layers, int n_layers,
                                  int k, int first, int count, void *const *host_out, int out_format, int overlap, float *timings_ms);
 
+/* ---- a4f: joint layer-guided non-local means: one patch weight from all guide layers ---------
+ * mid_nlm_layers_temporal runs one complete NLM pass per guide layer with one filteringParameter and adds them: a sample across
+ * a depth edge is kept whenever the albedo patch happens to match.  The joint filter forms ONE weight per search offset from the
+ * patch distances of all layers, each layer l with its own h_l.  Sequence of n_frames frames with n_layers RGBA8 layers each;
+ * texels c/255; out-of-image texels are 0 in frames and guides:
+ *   d_l(p,f,s) = sum_{q in patch} |G[t][l](p+q) - G[f][l](p+s+q)|^2_rgb
+ *   w(p,f,s)   = exp( - sum_l d_l(p,f,s) / h_l^2 )
+ *   out_t(p)   = sum_{f,s} w * In_f(p+s)  /  sum_f ( 0.001 + sum_s w )
+ * f = max(0,t-k) .. min(n_frames-1,t+k), ascending; s over the search window; l = 0 .. n_layers-1; all four channels are
+ * filtered; the 0.001 is added once per neighbour frame (nonlocal.comp:32-33), so one layer reproduces mid_nlm_layers_temporal.
+ * One frame: n_frames = 1, k = 0.  There is no accumulate form, for the reason a4e gives: a product of weights cannot be chained
+ * through WeightInfo.
+ * Everything else is mid_nlm_layers_temporal's: frame-major tables of device pointers, the window rule ("only the frames and
+ * layers of [first-k, first+count+k) are read"), out_format, the alignment and alias rules, the pointer limit
+ * MID_NLM_LAYERS_TEMPORAL_MAX_POINTERS, the window limits of the parameter checks of mid_nlm_accum -- a guide-format field in
+ * p->format is refused there: layers are RGBA8 -- and non-finite texels by IEEE arithmetic.
+ * layer_h: n_layers host floats, read during the call; NULL: every layer uses p->filteringParameter.  Each entry must be finite
+ * and > 0, as filteringParameter must be > 0 (which is checked as well, also when it is not used), and the two factors of the
+ * arithmetic below must be finite and > 0 in fp32: kd (h_0 between about 1e-21 and 1e16) and every r_l (h_0 / h_l between about
+ * 4e-23 and 1.8e19).
+ * Arithmetic: texels enter as their byte values, so a layer's squared differences and their patch sums are exact integers in
+ * fp32.  The scale is applied relative to layer 0: the distance of an offset is D = D_0 + sum_{l>=1} r_l D_l with
+ * r_l = (float)(h_0^2 / h_l^2) -- summed per texel before the box sums on the LDS-tiled kernels, per layer after them on the
+ * per-pixel kernel -- and w = 2^(-D * kd), kd = (float)(log2 e / (255^2 h_0^2)), one multiplication and one exp2 per offset.
+ * Precision: results are within 2e-5 * max(1, |ref|) of the formula in float64.
+ * Bit identities:
+ *   1. n_layers == 1 with layer_h = {h}, or NULL and filteringParameter = h: the bits of mid_nlm_layers_temporal with that layer
+ *      and h, for every window class, k, frame format and output format, translucent frames included (the one-layer class keeps
+ *      the layered kernel's tile shape and takes its opaque-tile vote per neighbour colour tile).
+ *   2. appending all-zero layers (any h) to a layer set leaves the bits as long as both sets run in one class of the table
+ *      below (2, 3 and 4 layers of a tuned window count as one: they share their tile shape and their arithmetic).  From one
+ *      layer to two the tile shape changes, and with it the tiles that hold an out-of-image texel or a texel whose alpha is not 1
+ *      and take the general form of the weight sums: there the two results may differ by the 5e-7 the opaque and the general
+ *      form differ by (the last bit of normWeight), also on frames whose alpha is 1 everywhere -- at the pixels of tiles that
+ *      reach over the image border.  From four layers to five the kernel changes (tiled to per pixel) and with it the order in
+ *      which the offsets are added: only the precision bound holds across that step.
+ *   3. out_format MID_FMT_RGBA8 / MID_FMT_RGBA16F gives mid_pack_u8 / mid_pack_f16 of the float result; output t of
+ *      mid_sequence_nlm_joint has the bits of mid_nlm_joint for frame t.
+ * Classes (every tiled class: eight waves per workgroup, 64 columns per wave, two waves per SIMD, no scratch):
+ *   window               n_layers  rows per wave  tile rows  guide rings  packed target strips  LDS bytes
+ *   21x21 / 7x7          1         8              64         float        0                     143136
+ *   21x21 / 7x7          2         4              32         float        0                     108864
+ *   21x21 / 7x7          3         4              32         packed       0                     128352
+ *   21x21 / 7x7          4         4              32         packed       1                     147840
+ *   14x14 / 6x6          1         8              64         float        0                     120120
+ *   14x14 / 6x6          2         4              32         float        0                     86240
+ *   14x14 / 6x6          3         4              32         packed       0                     101640
+ *   14x14 / 6x6          4         4              32         packed       1                     117040
+ * (21x21 / 7x7 = search [-10,11) patch [-3,4); 14x14 / 6x6 = search [-7,7) patch [-3,3)); every other window, n_layers > 4 and a
+ * device whose LDS does not hold the tiles: one thread per pixel.
+ * MID_ERR_INVALID before anything is queued, outputs untouched: n_layers outside 1..16 (0 is refused, as in the joint
+ * bilateral); a NULL layer table; an h that is not finite and > 0, or outside the range above; and every refusal of mid_nlm_layers_temporal. */
+int mid_nlm_joint(mid_ctx *ctx, const mid_nlm_params *p, const float *layer_h /* n_layers host floats, or NULL */,
+                  const void *const *frames /* host array of n_frames device ptrs */,
+                  const uint32_t *const *layers_rgba8 /* host array of n_frames * n_layers device ptrs */,
+                  int n_layers, int n_frames, int k, int first, int count,
+                  void *const *out /* host array of `count` device ptrs */, int out_format, void *stream);
+/* mid_sequence_nlm_layers_temporal (section a8) with mid_nlm_joint as the compute stage: host frames and host RGBA8 layers in,
+ * host frames out, output t with the bits of mid_nlm_joint for frame t.  Same ring, same layer ring (4 B per texel), same
+ * direct-store rule, same refusals (a call inside a recording among them), same timings_ms and timeline export; plus the
+ * refusals above, which leave host_out and timings_ms untouched. */
+int mid_sequence_nlm_joint(mid_ctx *ctx, const mid_nlm_params *p, const float *layer_h,
+                           const void *const *host_frames, int n_frames, const void *const *host_layers, int n_layers,
+                           int k, int first, int count, void *const *host_out, int out_format, int overlap, float *timings_ms);
+
 /* ---- a5: normalize ----------------------------------------------------------------------
  * One dispatch of shaders/normalize.comp (RecordCommandsOfExecuteAndTransfer(normKernel=true)):
  * out = weightColor / normWeight, or (1,0,1,1) where normWeight == 0; bindings {0: out; 1: W}. */

@@ -23,6 +23,8 @@ int mid::bilateral_temporal_out(mid_ctx *, const mid_bilateral_params *, const v
 int mid::bilateral_temporal_check(const mid_bilateral_params *, const char *, bool, int, int, int) { return MID_ERR_UNSUPPORTED; }   // (bilateral_temporal.hip)
 int mid::bilateral_joint_out(mid_ctx *, const mid_bilateral_params *, const float *, const void *const *, const uint32_t *const *, int, int, int, int, int, void *const *, int, hipStream_t) { return MID_ERR_UNSUPPORTED; }   // (bilateral_joint.hip)
 int mid::bilateral_joint_check(const mid_bilateral_params *, const char *, const float *, bool, int, int, int) { return MID_ERR_UNSUPPORTED; }   // (bilateral_joint.hip)
+int mid::nlm_joint_out(mid_ctx *, const mid_nlm_params *, const float *, const void *const *, const uint32_t *const *, int, int, int, int, int, void *const *, int, hipStream_t) { return MID_ERR_UNSUPPORTED; }   // (nlm_joint.hip)
+int mid::nlm_joint_check(const mid_nlm_params *, const char *, const float *, bool, int, int, int) { return MID_ERR_UNSUPPORTED; }   // (nlm_joint.hip)
 int mid::nlm_check_params(const mid_nlm_params *) { return MID_ERR_UNSUPPORTED; }   // (nlm.hip)
 int mid::bilateral_check_params(const mid_bilateral_params *, const char *, bool) { return MID_ERR_UNSUPPORTED; }   // (bilateral.hip)
 
