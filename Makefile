@@ -27,7 +27,7 @@ EXTRA_nlm_rt.hip := $(EXTRA_nlm.hip)
 EXTRA_nlm_small.hip := -mllvm -amdgpu-sched-strategy=iterative-ilp
 EXTRA_nlm_rt4.hip := $(EXTRA_nlm.hip)
 
-build/%.o: $(CSRC)/% $(CSRC)/common.hpp $(CSRC)/bilateral_shapes.hpp $(CSRC)/nlm_strip.hpp $(CSRC)/nlm_vbox_plan.hpp $(CSRC)/codec/image_io.hpp include/mi_denoise.h
+build/%.o: $(CSRC)/% $(CSRC)/common.hpp $(CSRC)/bilateral_shapes.hpp $(CSRC)/nlm_strip.hpp $(CSRC)/nlm_guide.hpp $(CSRC)/nlm_vbox_plan.hpp $(CSRC)/codec/image_io.hpp include/mi_denoise.h
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(HIPFLAGS) $(EXTRA_$(notdir $<)) -c $< -o $@
 

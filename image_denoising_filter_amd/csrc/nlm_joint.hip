@@ -25,7 +25,7 @@
 // as well.  Compiler's report for gfx950, 21x21 / 7x7 | 14x14 / 6x6: 230 | 228 VGPRs at one layer, 211 | 200 at two, 215 | 203 at
 // three, 236 | 222 at four; no kernel uses scratch.
 // Every other window, and more than four layers, runs on a per-pixel kernel with the same arithmetic.
-#include "nlm_strip.hpp"
+#include "nlm_guide.hpp"
 
 namespace mid {
 
@@ -33,7 +33,6 @@ namespace {
 
 constexpr int kJointTiledLayers = 4;    // layers the strip kernels are built for
 constexpr int kJNW = 8;                 // waves per workgroup, every shape
-constexpr int kMaxPtrs = MID_NLM_LAYERS_TEMPORAL_MAX_POINTERS;
 
 // rows per wave / neighbour rings packed, by layer count
 constexpr int joint_rows(int n_layers) { return n_layers == 1 ? 8 : 4; }
@@ -41,13 +40,10 @@ constexpr bool joint_packed(int n_layers) { return n_layers >= 3; }
 // layers (the last ones) whose TARGET strips stay packed as well: what keeps the four-layer kernel of the 7x7 patch under 256 VGPRs
 constexpr int joint_packed_targets(int n_layers) { return n_layers >= 4 ? 1 : 0; }
 
-// LDS bytes of a strip launch: the colour tile (16 B per texel, centres only) and n_layers guide tiles (4 B per texel)
-constexpr size_t joint_lds_bytes(int sw, int pw, int tile_h, int n_layers)
-{
-    return (size_t)(64 + sw - 1) * (tile_h + sw - 1) * 16 + (size_t)n_layers * (64 + sw - 1) * (tile_h + pw - 1 + sw - 1) * 4;
-}
-static_assert(joint_lds_bytes(21, 7, 64, 1) == 143136 && joint_lds_bytes(21, 7, 32, 4) == 147840, "21x21 / 7x7");
-static_assert(joint_lds_bytes(14, 6, 64, 1) == 120120 && joint_lds_bytes(14, 6, 32, 4) == 117040, "14x14 / 6x6");
+// geometry and LDS bytes of a strip launch with L layers: the colour tile and L guide tiles
+template <int SLO, int SHI, int PLO, int PHI, int L> using JointTile = GuideTile<SLO, SHI, PLO, PHI, joint_rows(L), kJNW>;
+static_assert(JointTile<-10, 11, -3, 4, 1>::lds_bytes(1) == 143136 && JointTile<-10, 11, -3, 4, 4>::lds_bytes(4) == 147840, "21x21 / 7x7");
+static_assert(JointTile<-7, 7, -3, 3, 1>::lds_bytes(1) == 120120 && JointTile<-7, 7, -3, 3, 4>::lds_bytes(4) == 117040, "14x14 / 6x6");
 
 struct NlmJointArgs {
     int w, h;
@@ -64,46 +60,6 @@ struct NlmJointArgs {
 };
 static_assert(sizeof(NlmJointArgs) <= sizeof(NlmArgs), "no larger than the temporal NLM kernels' argument block");
 
-__device__ __forceinline__ float3 bytes_rgb(uint32_t v)
-{
-    return make_float3((float)(v & 0xffu), (float)((v >> 8) & 0xffu), (float)((v >> 16) & 0xffu));
-}
-
-__device__ __forceinline__ uint32_t guide_at(const uint32_t *g, int w, int h, int x, int y)
-{
-    return ((unsigned)x < (unsigned)w && (unsigned)y < (unsigned)h) ? g[(size_t)y * w + x] : 0u;
-}
-
-// Guide tile of tw x th packed texels whose top-left texel is image (x0,y0); four loads in flight per thread and trip.
-__device__ __forceinline__ void fill_guide(uint32_t *t, int tw, int th, const uint32_t *g, int w, int h, int x0, int y0, int tid, int nthreads)
-{
-    const int n = tw * th;
-    for (int t0 = tid; t0 < n; t0 += 4 * nthreads) {
-        uint32_t v[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int i = t0 + j * nthreads;
-            const int ty = i / tw, tx = i - ty * tw;
-            v[j] = i < n ? guide_at(g, w, h, x0 + tx, y0 + ty) : 0u;
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (t0 + j * nthreads < n) t[t0 + j * nthreads] = v[j];
-    }
-}
-
-__device__ __forceinline__ const void *nb_frame(const NlmJointArgs &a, int j) { return a.p[j * (a.n_layers + 1)]; }
-__device__ __forceinline__ const uint32_t *nb_layer(const NlmJointArgs &a, int j, int l) { return (const uint32_t *)a.p[j * (a.n_layers + 1) + 1 + l]; }
-
-// Output pixel of both kernels' epilogues: normalize.comp:36-42, then packed like nlm_layers_temporal.hip's put().
-__device__ __forceinline__ void put(const NlmJointArgs &a, size_t idx, float4 tot, float totw)
-{
-    float4 o;
-    if (totw == 0.0f) o = make_float4(1.f, 0.f, 1.f, 1.f);
-    else o = make_float4(tot.x / totw, tot.y / totw, tot.z / totw, tot.w / totw);
-    store_out(a.out, idx, a.out_fmt, o);
-}
-
 // A neighbour guide texel in a wave's ring: widened to its byte values when it enters (float3), or kept packed and widened per use.
 template <bool PACKED> struct RingTexel { using type = float3; };
 template <> struct RingTexel<true> { using type = uint32_t; };
@@ -118,13 +74,9 @@ __device__ __forceinline__ float3 ring_rgb(uint32_t v) { asm volatile("" : "+v"(
 template <int SLO, int SHI, int PLO, int PHI, int R, int L, bool PACKED, int TP>
 __global__ __launch_bounds__(kJNW * 64) void nlm_joint_strip_kernel(const NlmJointArgs a)
 {
-    constexpr int NW = kJNW;
-    constexpr int PW = PHI - PLO, DR = R + PW - 1, NL = -PLO, NR = PHI - 1, VW = 64 - (PW - 1), TILE_H = NW * R;
-    constexpr int SW = SHI - SLO, LW = 64 + SW - 1;
-    constexpr int LHC = TILE_H + SW - 1;             // colour tile rows: centres only
-    constexpr int LHG = TILE_H + PW - 1 + SW - 1;    // neighbour guide tile rows: centres + patch halo
-    static_assert(PLO <= 0 && PHI >= 1 && SLO <= 0 && SHI >= 1, "ranges must contain 0");
-    static_assert(SW <= kNlmWalk, "one run of search rows per search column");
+    using T = GuideTile<SLO, SHI, PLO, PHI, R, kJNW>;
+    constexpr int NW = T::NW, PW = T::PW, DR = T::DR, NL = T::NL, NR = T::NR, VW = T::VW, TILE_H = T::TILE_H;
+    constexpr int SW = T::SW, LW = T::LW, LHC = T::LHC, LHG = T::LHG;
     static_assert(L >= 1 && L <= kJointTiledLayers, "layers of the strip kernels");
     using Ring = typename RingTexel<PACKED>::type;
 
@@ -188,9 +140,6 @@ __global__ __launch_bounds__(kJNW * 64) void nlm_joint_strip_kernel(const NlmJoi
 #pragma unroll
         for (int k = 0; k < R; ++k) { acc[k] = make_float4(0.f, 0.f, 0.f, 0.f); accw[k] = 0.001f; }   // nonlocal.comp:32-33, once per neighbour
 
-        // issue priority by phase, as in nlm_strip_kernel: raised from the vertical sums to the end of the accumulation
-        auto raise_priority = [] { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_setprio(1); __builtin_amdgcn_sched_barrier(0); };
-        auto drop_priority = [] { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_setprio(0); __builtin_amdgcn_sched_barrier(0); };
         const float kd = a.kd;
 
         // one offset: neighbour guide window row r of layer l lives in ring slot n[l][(j + r) % DR], the centre colour of output row
@@ -272,7 +221,7 @@ __global__ __launch_bounds__(kJNW * 64) void nlm_joint_strip_kernel(const NlmJoi
         for (int k = 0; k < R; ++k) {
             const int gy = yb + k;
             if (gy >= h) break;
-            put(a, (size_t)gy * w + gx, tot[k], totw[k]);
+            put_normalized(a.out, (size_t)gy * w + gx, a.out_fmt, tot[k], totw[k]);
         }
     }
 }
@@ -315,40 +264,25 @@ __global__ __launch_bounds__(256) void nlm_joint_generic_kernel(const NlmJointAr
         tot.x += acc.x; tot.y += acc.y; tot.z += acc.z; tot.w += acc.w;
         totw += accw;
     }
-    put(a, (size_t)py * a.w + px, tot, totw);
+    put_normalized(a.out, (size_t)py * a.w + px, a.out_fmt, tot, totw);
 }
 
 int launch_joint_generic(const mid_nlm_params *p, NlmJointArgs &a, hipStream_t s)
 {
-    const dim3 grid(cdiv(a.w, 16), cdiv(a.h, 16));
-    if (a.fmt == MID_FMT_RGBA8)
-        hipLaunchKernelGGL((nlm_joint_generic_kernel<MID_FMT_RGBA8>), grid, dim3(256), 0, s, a, p->search_lo, p->search_hi, p->patch_lo, p->patch_hi);
-    else if (a.fmt == MID_FMT_RGBA16F)
-        hipLaunchKernelGGL((nlm_joint_generic_kernel<MID_FMT_RGBA16F>), grid, dim3(256), 0, s, a, p->search_lo, p->search_hi, p->patch_lo, p->patch_hi);
-    else
-        hipLaunchKernelGGL((nlm_joint_generic_kernel<MID_FMT_RGBA32F>), grid, dim3(256), 0, s, a, p->search_lo, p->search_hi, p->patch_lo, p->patch_hi);
-    MID_HIP(hipGetLastError());
-    return MID_OK;
+    return launch_guide_per_pixel([](auto fmt) { return nlm_joint_generic_kernel<decltype(fmt)::value>; }, p, a, s);
 }
 
 template <int SLO, int SHI, int PLO, int PHI, int L>
 int launch_joint_strip(mid_ctx *ctx, const mid_nlm_params *p, NlmJointArgs &a, hipStream_t s)
 {
-    constexpr int R = joint_rows(L), PW = PHI - PLO, SW = SHI - SLO, VW = 64 - (PW - 1), TILE_H = kJNW * R;
-    constexpr size_t lds_bytes = joint_lds_bytes(SW, PW, TILE_H, L);
-    if ((int)lds_bytes > ctx->lds_max) {
+    using T = JointTile<SLO, SHI, PLO, PHI, L>;
+    if ((int)T::lds_bytes(L) > ctx->lds_max) {
         // the tiles do not fit this device: the per-pixel kernel, as the header says -- under a named range, so that a trace of a
         // device on which this happens shows why its launches are slow (no gfx950 class comes here: all fit 160 KB)
-        Range r("nlm_joint: tiles need %zu B of LDS, device offers %d: per-pixel kernel", lds_bytes, ctx->lds_max);
+        Range r("nlm_joint: tiles need %zu B of LDS, device offers %d: per-pixel kernel", T::lds_bytes(L), ctx->lds_max);
         return launch_joint_generic(p, a, s);
     }
-    auto kern = nlm_joint_strip_kernel<SLO, SHI, PLO, PHI, R, L, joint_packed(L), joint_packed_targets(L)>;
-    if (int rc = ensure_lds(ctx, (const void *)kern, lds_bytes)) return rc;
-    a.tiles_x = (int)cdiv(a.w, VW);
-    a.tiles_y = (int)cdiv(a.h, TILE_H);
-    hipLaunchKernelGGL(kern, dim3((unsigned)a.tiles_x * a.tiles_y), dim3(kJNW * 64), lds_bytes, s, a);
-    MID_HIP(hipGetLastError());
-    return MID_OK;
+    return launch_guide_strip<T>(ctx, "nlm_joint", nlm_joint_strip_kernel<SLO, SHI, PLO, PHI, T::R, L, joint_packed(L), joint_packed_targets(L)>, L, a, s);
 }
 
 template <int SLO, int SHI, int PLO, int PHI>
@@ -365,6 +299,8 @@ int launch_joint_window(mid_ctx *ctx, const mid_nlm_params *p, NlmJointArgs &a, 
 
 int dispatch_joint(mid_ctx *ctx, const mid_nlm_params *p, NlmJointArgs &a, hipStream_t s)
 {
+    // (the list of nlm_guide_for_window, written out: this dispatcher's window and layer classes are read off its text by
+    // tests/test_nlm_joint_args.py)
     if (p->search_lo == -10 && p->search_hi == 11 && p->patch_lo == -3 && p->patch_hi == 4)    // 21x21 / 7x7 (benchmark)
         return launch_joint_window<-10, 11, -3, 4>(ctx, p, a, s);
     if (p->search_lo == -7 && p->search_hi == 7 && p->patch_lo == -3 && p->patch_hi == 3)      // nonlocal.comp:5-6 as shipped
@@ -386,7 +322,7 @@ int nlm_joint_check(const mid_nlm_params *p, const char *who, const float *layer
     for (int l = 0; layer_h && l < n_layers; ++l) {
         MID_REQUIRE(layer_h[l] > 0.f && std::isfinite(layer_h[l]), "%s: every h must be finite and > 0 (layer_h[%d] = %g)", who, l, (double)layer_h[l]);
         const double h0 = (double)layer_h[0], hl = (double)layer_h[l];
-        const float kd = (float)(1.4426950408889634 / (h0 * h0 * 255.0 * 255.0)), rel = (float)((h0 * h0) / (hl * hl));
+        const float kd = nlm_guide_kd(h0), rel = (float)((h0 * h0) / (hl * hl));
         MID_REQUIRE(std::isfinite(kd) && kd > 0.f && std::isfinite(rel) && rel > 0.f,
                     "%s: layer_h[%d] = %g beside layer_h[0] = %g leaves fp32 (log2(e) / (255^2 h_0^2) and h_0^2 / h_l^2 must be finite and > 0)",
                     who, l, hl, h0);
@@ -401,7 +337,7 @@ int nlm_joint_out(mid_ctx *ctx, const mid_nlm_params *p, const float *layer_h, c
         NlmJointArgs a{};
         a.w = p->width; a.h = p->height; a.fmt = p->format;
         const double h0 = layer_h ? (double)layer_h[0] : (double)p->filteringParameter;
-        a.kd = (float)(1.4426950408889634 / (h0 * h0 * 255.0 * 255.0));       // nlm_layers_temporal.hip's init_args with h = h_0
+        a.kd = nlm_guide_kd(h0);                                              // nlm_layers_temporal.hip's init_args with h = h_0
         for (int l = 0; l < n_layers; ++l) {
             const double hl = layer_h ? (double)layer_h[l] : (double)p->filteringParameter;
             a.rel[l] = (float)((h0 * h0) / (hl * hl));

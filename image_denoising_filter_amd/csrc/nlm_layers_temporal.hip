@@ -23,15 +23,13 @@
 // Kernel arguments: one launch per output frame carries that output's window only -- for each neighbour its frame pointer and
 // its L layer pointers, (L + 1) per neighbour, the target's layers being those of the neighbour f == t -- at most
 // MID_NLM_LAYERS_TEMPORAL_MAX_POINTERS of them, so the block stays smaller than the by-value tables of the temporal NLM kernels.
-#include "nlm_strip.hpp"
-#include <vector>
+#include "nlm_guide.hpp"
 
 namespace mid {
 
 namespace {
 
 constexpr int kLR = 8, kLNW = 8;        // strip kernel: rows per wave, waves per workgroup (as nlm_layers.hip)
-constexpr int kMaxPtrs = MID_NLM_LAYERS_TEMPORAL_MAX_POINTERS;
 
 struct NlmLayerPairArgs {
     int w, h;
@@ -49,35 +47,6 @@ struct NlmLayerPairArgs {
 };
 static_assert(sizeof(NlmLayerPairArgs) <= sizeof(NlmArgs), "no larger than the temporal NLM kernels' argument block");
 
-__device__ __forceinline__ float3 bytes_rgb(uint32_t v)
-{
-    return make_float3((float)(v & 0xffu), (float)((v >> 8) & 0xffu), (float)((v >> 16) & 0xffu));
-}
-
-__device__ __forceinline__ uint32_t guide_at(const uint32_t *g, int w, int h, int x, int y)
-{
-    return ((unsigned)x < (unsigned)w && (unsigned)y < (unsigned)h) ? g[(size_t)y * w + x] : 0u;
-}
-
-__device__ __forceinline__ void fill_guide(uint32_t *t, int tw, int th, const uint32_t *g, int w, int h, int x0, int y0, int tid, int nthreads)
-{
-    const int n = tw * th;
-    for (int t0 = tid; t0 < n; t0 += 4 * nthreads) {
-        uint32_t v[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int i = t0 + j * nthreads;
-            const int ty = i / tw, tx = i - ty * tw;
-            v[j] = i < n ? guide_at(g, w, h, x0 + tx, y0 + ty) : 0u;
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (t0 + j * nthreads < n) t[t0 + j * nthreads] = v[j];
-    }
-}
-
-__device__ __forceinline__ const void *nb_frame(const NlmLayerPairArgs &a, int j) { return a.p[j * (a.n_layers + 1)]; }
-__device__ __forceinline__ const uint32_t *nb_layer(const NlmLayerPairArgs &a, int j, int l) { return (const uint32_t *)a.p[j * (a.n_layers + 1) + 1 + l]; }
 template <bool FUSED>
 __device__ __forceinline__ const uint32_t *target_layer(const NlmLayerPairArgs &a, int l)
 {
@@ -88,33 +57,16 @@ __device__ __forceinline__ const uint32_t *target_layer(const NlmLayerPairArgs &
 template <bool FUSED>
 __device__ __forceinline__ void put(const NlmLayerPairArgs &a, size_t idx, float4 tot, float totw)
 {
-    if (FUSED) {
-        float4 o;
-        if (totw == 0.0f) o = make_float4(1.f, 0.f, 1.f, 1.f);
-        else o = make_float4(tot.x / totw, tot.y / totw, tot.z / totw, tot.w / totw);
-        if (a.out_fmt == MID_FMT_RGBA8) ((uint32_t *)a.out)[idx] = pack_rgba8(o);
-        else if (a.out_fmt == MID_FMT_RGBA16F) ((uint2 *)a.out)[idx] = pack_rgba16f(o);
-        else ((float4 *)a.out)[idx] = o;
-    } else {
-        float4 *wp = (float4 *)(a.W + idx);
-        float4 wc = wp[0], nw = wp[1];
-        wc.x += tot.x; wc.y += tot.y; wc.z += tot.z; wc.w += tot.w;
-        nw.x += totw;
-        wp[0] = wc;
-        wp[1] = nw;
-    }
+    if (FUSED) put_normalized(a.out, idx, a.out_fmt, tot, totw);
+    else put_accumulated(a.W, idx, tot, totw);
 }
 
 template <int SLO, int SHI, int PLO, int PHI, bool FUSED>
 __global__ __launch_bounds__(kLNW * 64) void nlm_layers_pair_strip_kernel(const NlmLayerPairArgs a)
 {
-    constexpr int R = kLR, NW = kLNW;
-    constexpr int PW = PHI - PLO, DR = R + PW - 1, NL = -PLO, NR = PHI - 1, VW = 64 - (PW - 1), TILE_H = NW * R;
-    constexpr int SW = SHI - SLO, LW = 64 + SW - 1;
-    constexpr int LHC = TILE_H + SW - 1;             // colour tile rows: centres only
-    constexpr int LHG = TILE_H + PW - 1 + SW - 1;    // neighbour guide tile rows: centres + patch halo
-    static_assert(PLO <= 0 && PHI >= 1 && SLO <= 0 && SHI >= 1, "ranges must contain 0");
-    static_assert(SW <= kNlmWalk, "one run of search rows per search column");
+    using T = GuideTile<SLO, SHI, PLO, PHI, kLR, kLNW>;
+    constexpr int R = T::R, NW = T::NW, PW = T::PW, DR = T::DR, NL = T::NL, NR = T::NR, VW = T::VW, TILE_H = T::TILE_H;
+    constexpr int SW = T::SW, LW = T::LW, LHC = T::LHC, LHG = T::LHG;
 
     extern __shared__ float4 lds[];
     float4 *ctile = lds;
@@ -168,9 +120,6 @@ __global__ __launch_bounds__(kLNW * 64) void nlm_layers_pair_strip_kernel(const 
 #pragma unroll
             for (int k = 0; k < R; ++k) { acc[k] = make_float4(0.f, 0.f, 0.f, 0.f); accw[k] = 0.001f; }   // nonlocal.comp:32-33
 
-            // issue priority by phase, as in nlm_strip_kernel: raised from the vertical sums to the end of the accumulation
-            auto raise_priority = [] { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_setprio(1); __builtin_amdgcn_sched_barrier(0); };
-            auto drop_priority = [] { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_setprio(0); __builtin_amdgcn_sched_barrier(0); };
             const float kd = a.kd;
 
             // one offset: neighbour guide window row r lives in ring slot (j + r) % DR, the centre colour of output row k in slot
@@ -281,45 +230,23 @@ __global__ __launch_bounds__(256) void nlm_layers_pair_generic_kernel(const NlmL
     put<FUSED>(a, (size_t)py * a.w + px, tot, totw);
 }
 
-template <int SLO, int SHI, int PLO, int PHI, bool FUSED>
-int launch_pair_strip(mid_ctx *ctx, NlmLayerPairArgs &a, hipStream_t s)
-{
-    constexpr int PW = PHI - PLO, SW = SHI - SLO, VW = 64 - (PW - 1), TILE_H = kLNW * kLR, LW = 64 + SW - 1;
-    constexpr size_t lds_bytes = (size_t)LW * (TILE_H + SW - 1) * sizeof(float4) + (size_t)LW * (TILE_H + PW - 1 + SW - 1) * 4;
-    auto kern = nlm_layers_pair_strip_kernel<SLO, SHI, PLO, PHI, FUSED>;
-    if ((int)lds_bytes > ctx->lds_max)
-        return set_error(MID_ERR_UNSUPPORTED, "nlm_layers_temporal tile needs %zu B of LDS, device offers %d", lds_bytes, ctx->lds_max);
-    if (int rc = ensure_lds(ctx, (const void *)kern, lds_bytes)) return rc;
-    a.tiles_x = (int)cdiv(a.w, VW);
-    a.tiles_y = (int)cdiv(a.h, TILE_H);
-    hipLaunchKernelGGL(kern, dim3((unsigned)a.tiles_x * a.tiles_y), dim3(kLNW * 64), lds_bytes, s, a);
-    MID_HIP(hipGetLastError());
-    return MID_OK;
-}
-
 template <bool FUSED>
 int dispatch_pair(mid_ctx *ctx, const mid_nlm_params *p, NlmLayerPairArgs &a, hipStream_t s)
 {
-    if (p->search_lo == -10 && p->search_hi == 11 && p->patch_lo == -3 && p->patch_hi == 4)    // 21x21 / 7x7 (benchmark)
-        return launch_pair_strip<-10, 11, -3, 4, FUSED>(ctx, a, s);
-    if (p->search_lo == -7 && p->search_hi == 7 && p->patch_lo == -3 && p->patch_hi == 3)      // nonlocal.comp:5-6 as shipped
-        return launch_pair_strip<-7, 7, -3, 3, FUSED>(ctx, a, s);
-    const dim3 grid(cdiv(a.w, 16), cdiv(a.h, 16));
-    if (a.fmt == MID_FMT_RGBA8)
-        hipLaunchKernelGGL((nlm_layers_pair_generic_kernel<MID_FMT_RGBA8, FUSED>), grid, dim3(256), 0, s, a, p->search_lo, p->search_hi, p->patch_lo, p->patch_hi);
-    else if (a.fmt == MID_FMT_RGBA16F)
-        hipLaunchKernelGGL((nlm_layers_pair_generic_kernel<MID_FMT_RGBA16F, FUSED>), grid, dim3(256), 0, s, a, p->search_lo, p->search_hi, p->patch_lo, p->patch_hi);
-    else
-        hipLaunchKernelGGL((nlm_layers_pair_generic_kernel<MID_FMT_RGBA32F, FUSED>), grid, dim3(256), 0, s, a, p->search_lo, p->search_hi, p->patch_lo, p->patch_hi);
-    MID_HIP(hipGetLastError());
-    return MID_OK;
+    int rc;
+    if (nlm_guide_for_window(p, &rc, [&](auto win) {
+            using W = decltype(win);
+            return launch_guide_strip<GuideTile<W::SLO, W::SHI, W::PLO, W::PHI, kLR, kLNW>>(
+                ctx, "nlm_layers_temporal", nlm_layers_pair_strip_kernel<W::SLO, W::SHI, W::PLO, W::PHI, FUSED>, 1, a, s);
+        }))
+        return rc;
+    return launch_guide_per_pixel([](auto fmt) { return nlm_layers_pair_generic_kernel<decltype(fmt)::value, FUSED>; }, p, a, s);
 }
 
 void init_args(NlmLayerPairArgs &a, const mid_nlm_params *p)
 {
     a.w = p->width; a.h = p->height; a.fmt = p->format;
-    const double hh = (double)p->filteringParameter * (double)p->filteringParameter;
-    a.kd = (float)(1.4426950408889634 / (hh * 255.0 * 255.0));
+    a.kd = nlm_guide_kd((double)p->filteringParameter);
 }
 
 }  // namespace

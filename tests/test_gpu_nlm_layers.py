@@ -79,6 +79,24 @@ def test_fused_equals_the_accumulate_chain(ctx, cfg, translucent):
     assert np.array_equal(bits(fused), bits(chain)), cfg
 
 
+@pytest.mark.parametrize("cfg", ["ref", "naive"])
+@pytest.mark.parametrize("translucent", [False, True])
+def test_sixteen_layers_are_the_chain_and_the_checker(ctx, cfg, translucent):
+    """The most layers one call takes (a window of one frame and 16 layer pointers in the kernel's argument block), on a frame of
+    two tile rows, one of them partial, and three tile columns: the bits of 16 accumulate dispatches + normalize, and the checker."""
+    rng = np.random.default_rng(16)
+    h, w = 70, 130
+    img = noisy(rng, h, w, translucent)
+    gl = guides(rng, h, w, 16)
+    assert len({g.tobytes() for g in gl}) == 16
+    W = np.zeros((h, w, 8), np.float32)
+    for g in gl:
+        W = ctx.nlm_layers_accum(img, g, W, H, **NLM_CFGS[cfg])
+    fused = ctx.nlm_layers(img, gl, H, **NLM_CFGS[cfg])
+    assert np.array_equal(bits(fused), bits(ctx.normalize(W))), cfg
+    assert rel_err(fused, np_nlm_layers.nlm_layers(img, gl, H, **NLM_CFGS[cfg])) < TOL, cfg
+
+
 @pytest.mark.parametrize("cfg", ["ref", "bench", "generic", "naive"])
 def test_input_as_its_own_guide_is_plain_nlm(ctx, cfg):
     rng = np.random.default_rng(8)

@@ -77,12 +77,22 @@ def test_joint_bilateral_shapes_are_the_sources():
 
 
 def test_nlm_layer_shapes_are_the_sources():
+    """Both files keep their shape constants and their colour-tile fill; the tile's geometry is nlm_guide.hpp's GuideTile, which the
+    kernels read by name and beside which they state no formula of their own."""
+    g = _src("nlm_guide.hpp")
+    assert re.search(r"static constexpr int SLO = SLO_, SHI = SHI_, PLO = PLO_, PHI = PHI_, R = R_, NW = NW_;", g)
+    assert re.search(r"static constexpr int PW = PHI - PLO, [^;]*TILE_H = NW \* R;", g)
+    assert re.search(r"static constexpr int SW = SHI - SLO, LW = 64 \+ SW - 1;", g)
+    assert re.search(r"static constexpr int LHC = TILE_H \+ SW - 1;", g)
     for name, kern in (("nlm_layers.hip", "a.in"), ("nlm_layers_temporal.hip", "nb")):
         k = _src(name)
         m = re.search(r"constexpr int kLR = (\d+), kLNW = (\d+);", k)
         assert m and (int(m.group(1)), int(m.group(2))) == ov.NLM_LAYERS_SHAPE, name
-        assert re.search(r"constexpr int SW = SHI - SLO, LW = 64 \+ SW - 1;", k), name
-        assert re.search(r"constexpr int LHC = TILE_H \+ SW - 1;", k), name
+        assert '#include "nlm_guide.hpp"' in k, name
+        assert re.search(r"using T = GuideTile<SLO, SHI, PLO, PHI, kLR, kLNW>;", k), name
+        assert re.search(r"constexpr int R = T::R, NW = T::NW, PW = T::PW, DR = T::DR, NL = T::NL, NR = T::NR, VW = T::VW, TILE_H = T::TILE_H;\s*"
+                         r"constexpr int SW = T::SW, LW = T::LW, LHC = T::LHC, LHG = T::LHG;", k), name
+        assert not re.search(r"constexpr int (LW|LHC|SW|TILE_H|NW) = [^T]", k), name
         assert re.search(r"fill_tile<MID_FMT_RGBA32F, false>\(ctile, LW, LHC, " + re.escape(kern) + r", w, h, X0 \+ PLO \+ SLO, Y0 \+ SLO, tid, NW \* 64, 1\.0f, &mine\)", k), name
 
 

@@ -23,12 +23,14 @@ TOOLS = {
     "bil_rt_time": ["tools/bil_rt_time.py"],
     "layers_time": ["tools/layers_time.py"],
     "nlm_layers_rate": ["tools/nlm_layers_rate.py", "--rounds", "3", "--reps", "5"],
+    "nlm_layers_rate_untuned": ["tools/nlm_layers_rate.py", "--rounds", "3", "--reps", "5", "--untuned"],   # + the per-pixel kernels
     "bilateral_temporal_rate": ["tools/bilateral_temporal_rate.py", "--rounds", "3", "--reps", "5", "--frames", "32"],
     "nlm_layers_temporal_rate": ["tools/nlm_layers_temporal_rate.py", "--rounds", "3", "--reps", "3", "--frames", "16"],
     "bench_full": ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "3", "--full", "--no-cpu-baseline"],
 }
 # table rows of the rate tools (every token a number or 'plain'): name of the row from its first tokens, and the time columns
 ROWS = {"nlm_layers_rate": (("L",), {1: "fused", 4: "chain"}),
+        "nlm_layers_rate_untuned": (("L",), {1: "fused", 4: "chain"}),
         "bilateral_temporal_rate": (("k", "L"), {3: "fused", 6: "chain"}),
         "nlm_layers_temporal_rate": (("k", "L"), {3: "fused", 6: "chain"})}
 NUM = re.compile(r"^-?\d+(\.\d+)?$")

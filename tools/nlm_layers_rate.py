@@ -2,7 +2,8 @@
 --out).
 
 1. Kernel time per layer: mid_nlm_layers with L = 1, 2, 4, 8 guides on one 1080p RGBA32F frame, divided by L, against a one-frame
-   mid_nlm_temporal launch (k = 0) of the same frame, at both tuned windows.  Device buffers only; each figure is the event time
+   mid_nlm_temporal launch (k = 0) of the same frame, at both tuned windows (--untuned: and at search (-2, 3), patch (-1, 3), which runs on the
+   per-pixel kernels).  Device buffers only; each figure is the event time
    (mid_timer) of REPS back-to-back calls on the context's stream / REPS, median over the rounds; variants are interleaved round by
    round so that every figure sees the same lease.
 2. Fused against the chain: mid_nlm_layers against L x mid_nlm_layers_accum + mid_normalize (the clear of W not counted).
@@ -23,6 +24,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--out", default=None)
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--reps", type=int, default=10)
+ap.add_argument("--untuned", action="store_true", help="a third window for the table of 1. and 2., one that runs on the per-pixel kernel")
 args = ap.parse_args()
 lines = []
 
@@ -40,6 +42,7 @@ def ok(rc, what):
 W, H = 1920, 1080
 NPIX = W * H
 WINDOWS = {"7x7/14x14 (reference)": ((-7, 7), (-3, 3)), "7x7/21x21 (bench)": ((-10, 11), (-3, 4))}
+TABLE_WINDOWS = dict(WINDOWS, **({"4x4/5x5 (untuned: per-pixel kernel)": ((-2, 3), (-1, 3))} if args.untuned else {}))
 LS = (1, 2, 4, 8)
 ctx = mid.Context(0)
 say(f"device {ctx.name}; 1080p RGBA32F input, h = 0.5; {args.rounds} rounds x {args.reps} calls per figure")
@@ -84,7 +87,7 @@ def variants(p):
     return v
 
 
-for wname, (search, patch) in WINDOWS.items():
+for wname, (search, patch) in TABLE_WINDOWS.items():
     p = mid.NlmParams(W, H, 0.5, search[0], search[1], patch[0], patch[1], mid.FMT_RGBA32F)
     vs = variants(p)
     res = {k: [] for k in vs}
