@@ -43,6 +43,13 @@ class NlmParams(ctypes.Structure):
                 ("format", ctypes.c_int32)]
 
 
+class AtrousParams(ctypes.Structure):
+    """mid_atrous_params (section a4g)."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("first_pass", ctypes.c_int32), ("n_passes", ctypes.c_int32),
+                ("colorSigma", ctypes.c_float), ("format", ctypes.c_int32)]
+
+
 class NormalizeParams(ctypes.Structure):
     _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32)]
 
@@ -93,6 +100,12 @@ _SIGNATURES = {
                                            ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_pp, ctypes.c_int, _P]),
     "mid_nlm_joint": (ctypes.c_int, [_P, ctypes.POINTER(NlmParams), ctypes.POINTER(ctypes.c_float), c_void_pp, c_void_pp,
                                      ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_pp, ctypes.c_int, _P]),
+    "mid_atrous_scratch_bytes": (ctypes.c_size_t, [ctypes.POINTER(AtrousParams)]),
+    "mid_atrous_joint": (ctypes.c_int, [_P, ctypes.POINTER(AtrousParams), ctypes.POINTER(ctypes.c_float), _P, c_void_pp, ctypes.c_int,
+                                        _P, ctypes.c_int, _P, _P]),
+    "mid_sequence_atrous_joint": (ctypes.c_int, [_P, ctypes.POINTER(AtrousParams), ctypes.POINTER(ctypes.c_float), c_void_pp, ctypes.c_int,
+                                                 c_void_pp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_pp, ctypes.c_int,
+                                                 ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
     "mid_normalize": (ctypes.c_int, [_P, ctypes.POINTER(NormalizeParams), _P, _P, _P]),
     "mid_unpack_u8": (ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_int, _P, _P]),
     "mid_pack_u8": (ctypes.c_int, [_P, _P, ctypes.c_size_t, _P, _P]),

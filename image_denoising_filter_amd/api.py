@@ -15,7 +15,7 @@ import weakref
 
 import numpy as np
 
-from ._lib import BilateralParams, Image, NlmParams, NormalizeParams, c_void_pp, lib
+from ._lib import AtrousParams, BilateralParams, Image, NlmParams, NormalizeParams, c_void_pp, lib
 
 FMT_RGBA32F, FMT_RGBA8, FMT_RGBA16F = 0, 1, 2
 
@@ -467,6 +467,26 @@ class Context:
                "mid_bilateral_joint")
         return [self.download(d, (h, w, 4), out_dtype) for d in d_out]
 
+    def atrous_joint(self, frame, layers, sigmas, passes=5, first_pass=0, color_sigma=0.0, out_dtype=None):
+        """The edge-avoiding a-trous filter of one frame (mid_atrous_joint): `passes` passes of the 5x5 B3-spline kernel, pass i
+        at step 2^i starting with i = first_pass, every tap weighed by all guide layers at once.  layers: 1..16 (h, w, 4) guide
+        layers, uint8, float16 or float32 and all of one dtype; sigmas: one sigma per layer; color_sigma: 0 = no colour term;
+        out_dtype: None = float32, uint8 or float16."""
+        (frame,) = _same_frames([frame], "atrous_joint")
+        h, w = frame.shape[:2]
+        n_layers, flat = _flat_layers([layers], 1, h, w, "atrous_joint", _GUIDE_DTYPES)
+        out_dtype = _out_dtype(False, out_dtype)
+        p = AtrousParams(w, h, first_pass, passes, color_sigma, _guide_fmt(_fmt_of(frame), flat, "atrous_joint"))
+        d_in = self.upload(frame)
+        d_l = [self.upload(l) for l in flat]
+        d_out = self.alloc(w * h * 4 * out_dtype.itemsize)
+        nbytes = lib.mid_atrous_scratch_bytes(ctypes.byref(p))
+        d_scratch = self.alloc(nbytes) if nbytes else None
+        _check(lib.mid_atrous_joint(self.handle, ctypes.byref(p), _layer_sigmas(sigmas, n_layers, "atrous_joint"), d_in.ptr,
+                                    (ctypes.c_void_p * max(len(d_l), 1))(*[d.ptr for d in d_l]), n_layers, d_out.ptr, _OUT_FMT[out_dtype],
+                                    d_scratch.ptr if d_scratch else None, None), "mid_atrous_joint")
+        return self.download(d_out, (h, w, 4), out_dtype)
+
     def normalize(self, W):
         """normalize.comp."""
         W = np.ascontiguousarray(W, dtype=np.float32)
@@ -737,6 +757,29 @@ class Context:
         return self._sequence_host("sequence_nlm_joint", lambda hin, hout, w, h, fmt, hlayers, n_layers, count: self.sequence_nlm_joint_pinned(
             hin, hout, w, h, fmt, hlayers, n_layers, hs, k, first, count, overlap, hparam, search, patch, out_dtype),
             frames, layers, (np.uint8,), first, count, pinned, pinned_out, out_dtype)
+
+
+    def sequence_atrous_joint_pinned(self, hin, hout, w, h, fmt, hlayers, n_layers, sigmas, passes=5, first_pass=0, color_sigma=0.0,
+                                     first=0, count=None, overlap=True, out_dtype=None):
+        """mid_sequence_atrous_joint on host pointers the caller already holds: nothing but the C call.  hin: all n frames of the
+        sequence; hlayers: n * n_layers host pointers, frame-major (RGBA8, or what fmt_with_guide names in `fmt`); hout: `count`
+        output buffers; sigmas: n_layers sigmas.  Returns (wall_ms of the whole call, kernel_ms, copy_ms)."""
+        count = len(hin) - first if count is None else count
+        return self._sequence_call("mid_sequence_atrous_joint", "mid_sequence_atrous_joint",
+                                   AtrousParams(w, h, first_pass, passes, color_sigma, fmt), hin, hout, count,
+                                   f"{count} outputs", overlap, layers=(hlayers, n_layers), window=(first, count), out_dtype=(out_dtype,),
+                                   sigmas=(sigmas,))
+
+    def sequence_atrous_joint(self, frames, layers, sigmas, passes=5, first_pass=0, color_sigma=0.0, first=0, count=None, overlap=True,
+                              pinned=True, pinned_out=True, out_dtype=None):
+        """Outputs [first, first+count) of an animation through the overlapped pipeline with the a-trous filter as its compute
+        stage (mid_sequence_atrous_joint): output t is ctx.atrous_joint(frames[t], layers[t], sigmas, passes, first_pass,
+        color_sigma) in out_dtype.  pinned, pinned_out, out_dtype as for sequence_bilateral.
+        Returns (outputs, (wall_ms, kernel_ms, copy_ms))."""
+        out_dtype = _out_dtype(False, out_dtype)
+        return self._sequence_host("sequence_atrous_joint", lambda hin, hout, w, h, fmt, hlayers, n_layers, count: self.sequence_atrous_joint_pinned(
+            hin, hout, w, h, fmt, hlayers, n_layers, sigmas, passes, first_pass, color_sigma, first, count, overlap, out_dtype),
+            frames, layers, _GUIDE_DTYPES, first, count, pinned, pinned_out, out_dtype)
 
 
 def _layer_sigmas(sigmas, n_layers, who, noun="sigmas"):

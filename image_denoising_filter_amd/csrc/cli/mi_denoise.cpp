@@ -53,6 +53,8 @@ struct Options {
     std::vector<float> sigma_layers;           // the joint modes: one range sigma per layer in discovery order (empty: sigma_c for all)
     float nlm_h = 0.5f;             // src/main.cpp:870
     std::vector<float> h_layers;    // the joint NLM modes: one h per layer in discovery order (empty: nlm_h for all)
+    int passes = 5;                 // the a-trous modes: passes of the 5x5 kernel, pass i at step 2^i (1..8)
+    float atrous_sigma_color = 0.f; // the a-trous modes: sigma of the colour term at pass 0, halved every pass (0: off)
     int search_lo = -7, search_hi = 7, patch_lo = -3, patch_hi = 3;   // shaders/nonlocal.comp:5-6, half-open
     int temporal_k = -1;            // <0: the reference's frame list; >=0: window t-k..t+k of the sorted sequence
     int cpu_radius = 10;            // windowSize, src/main.cpp:1819
@@ -60,7 +62,7 @@ struct Options {
     bool cpu_blue_bug = true;       // pow(texColor.b - texColor.b, 2), src/main.cpp:1850
     std::vector<int> cpu_threads = {1, 8};     // src/main.cpp:1979,1984
     bool run_gpu = true, run_cpu = true;
-    std::string modes = "all";      // comma list of: bilateral,layers,linear,nlm,multiframe,overlap (all of them: "all"), nlm-layers, joint, nlm-joint
+    std::string modes = "all";      // comma list of: bilateral,layers,linear,nlm,multiframe,overlap (all of them: "all"), nlm-layers, joint, nlm-joint, atrous
     bool animation = false;         // new capability: temporal NLM of EVERY frame of the sequence
     std::string animation_filter = "nlm";   // animation mode: nlm | bilateral | linear | layers (the bilateral of every frame) | nlm-layers | nlm-layers-temporal | bilateral-temporal | layers-temporal | joint | joint-temporal | nlm-joint | nlm-joint-temporal
     int gpus = 1;                   // animation mode: frame blocks over this many devices
@@ -78,7 +80,7 @@ struct Options {
     } while (0)
 
 // --animation-filter, parsed once: the mid_sequence_* family a value runs, what that family reads, and the words of the value.
-enum SeqFamily { SEQ_NLM, SEQ_BILATERAL, SEQ_NLM_LAYERS, SEQ_NLM_LAYERS_TEMPORAL, SEQ_BILATERAL_TEMPORAL, SEQ_BILATERAL_JOINT, SEQ_NLM_JOINT };
+enum SeqFamily { SEQ_NLM, SEQ_BILATERAL, SEQ_NLM_LAYERS, SEQ_NLM_LAYERS_TEMPORAL, SEQ_BILATERAL_TEMPORAL, SEQ_BILATERAL_JOINT, SEQ_NLM_JOINT, SEQ_ATROUS };
 struct AnimationFilter {
     const char *name;
     SeqFamily family;
@@ -89,7 +91,7 @@ struct AnimationFilter {
     const char *words;      // of the summary line, before r= / the layers / k=
     const char *banner;     // "Running on GPU (animation, <banner>)"
     bool bilateral() const { return family == SEQ_BILATERAL || family == SEQ_BILATERAL_TEMPORAL || family == SEQ_BILATERAL_JOINT; }
-    bool windowed() const { return family != SEQ_BILATERAL && family != SEQ_NLM_LAYERS; }     // blocks with k halo frames on either side
+    bool windowed() const { return family != SEQ_BILATERAL && family != SEQ_NLM_LAYERS && family != SEQ_ATROUS; }     // blocks with k halo frames on either side
 };
 static const AnimationFilter kAnimationFilters[] = {
     {"nlm", SEQ_NLM, false, true, false, "", "", "temporal nonlocal"},
@@ -104,6 +106,7 @@ static const AnimationFilter kAnimationFilters[] = {
     {"joint-temporal", SEQ_BILATERAL_JOINT, true, true, false, "nonlinear-bialteral-joint-multiframe-", "joint bilateral", "joint bialteral, multiframe"},
     {"nlm-joint", SEQ_NLM_JOINT, true, false, false, "nonlinear-nlm-joint-", "joint nonlocal", "joint nonlocal"},
     {"nlm-joint-temporal", SEQ_NLM_JOINT, true, true, false, "nonlinear-nlm-joint-multiframe-", "joint nonlocal", "joint nonlocal, multiframe"},
+    {"atrous", SEQ_ATROUS, true, false, false, "nonlinear-atrous-", "a-trous", "a-trous + layers"},
 };
 static const AnimationFilter *animation_filter(const std::string &name)
 {
@@ -305,7 +308,8 @@ public:
     // RunOnGPU, src/main.cpp:1307-1730
     // joint (with useLayers): the joint bilateral (mid_bilateral_joint) or, with nlmFilter, joint layer-guided NLM (mid_nlm_joint): one weight from
     // all layers instead of the sum of one filter per layer
-    void RunOnGPU(bool nlmFilter, bool nonlinear, bool multiframe, bool execAndCopyOverlap, bool useLayers, bool joint = false)
+    // atrous (with useLayers and joint): the edge-avoiding a-trous filter (mid_atrous_joint) with the joint mode's layers and sigmas
+    void RunOnGPU(bool nlmFilter, bool nonlinear, bool multiframe, bool execAndCopyOverlap, bool useLayers, bool joint = false, bool atrous = false)
     {
         const bool linear = !nonlinear;                                              // :1311
         TraceRange mode_range(std::string("RunOnGPU ") + (linear ? "linear" : "nonlinear") + (nlmFilter ? " nlm" : " bialteral") +
@@ -406,7 +410,7 @@ public:
                 if (joint) {
                     if (layerNames.empty() || layerNames.size() > 16)
                         throw std::runtime_error(opt.image + ": " + std::to_string(layerNames.size()) + " layer file(s) found, --modes " +
-                                                 (nlmFilter ? "nlm-joint" : "joint") + " needs 1..16");
+                                                 (atrous ? "atrous" : nlmFilter ? "nlm-joint" : "joint") + " needs 1..16");
                     jointSigma = layer_sigmas(layerNames, nlmFilter);
                 }
                 for_each_file(0, (int)layerNames.size(), [&](int i) {
@@ -437,6 +441,16 @@ public:
                     timed(m_execMs, [&] {
                         MID_CHECK(mid_nlm_layers(ctx, &p, dIn, (const uint32_t *const *)dLayers.data(), (int)dLayers.size(), (mid_pixel *)dOut, nullptr));
                     });
+                } else if (atrous) {                                                            // N passes of the 5x5 kernel with holes (mid_atrous_joint)
+                    mid_atrous_params p{w, h, 0, opt.passes, opt.atrous_sigma_color, lfmt == MID_FMT_RGBA8 ? fmt : MID_FMT_WITH_GUIDE(fmt, lfmt)};
+                    void *levels = nullptr;
+                    if (mid_atrous_scratch_bytes(&p)) MID_CHECK(mid_alloc(ctx, mid_atrous_scratch_bytes(&p), &levels));
+                    timed(m_execMs, [&] {
+                        MID_CHECK(mid_atrous_joint(ctx, &p, jointSigma.data(), dIn, (const uint32_t *const *)dLayers.data(), (int)dLayers.size(), dOut,
+                                                   MID_FMT_RGBA32F, levels, nullptr));
+                    });
+                    MID_CHECK(mid_stream_sync(ctx, nullptr));
+                    if (levels) mid_free(ctx, levels);
                 } else if (joint) {
                     mid_bilateral_params p{w, h, opt.sigma_s, opt.sigma_c, opt.radius, MID_LAYOUT_TEXTURE,
                                            lfmt == MID_FMT_RGBA8 ? fmt : MID_FMT_WITH_GUIDE(fmt, lfmt)};
@@ -472,6 +486,7 @@ public:
         outputFileName += multiframe ? "-multiframe" : "";
         outputFileName += execAndCopyOverlap ? "-overlap" : "";
         outputFileName += joint ? "-joint" : useLayers ? "-layers" : "";
+        if (atrous) outputFileName = "output-nonlinear-atrous";
         if (half) {   // --half: the fp32 result rounded to RGBA16F on the device (mid_pack_f16), written as HALF EXR
             std::vector<uint16_t> px(npix * 4);
             void *dF = nullptr, *dH = nullptr;
@@ -538,7 +553,7 @@ public:
         for (auto &fl : frameLayers) allLayers.insert(allLayers.end(), fl.begin(), fl.end());
         if (nlm_guides) for (const std::string &ln : allLayers) if (is_hdr(ln)) (void)load(ln, true);   // refuses, saying why
         const int lfmt = layer_format(allLayers);
-        const std::vector<float> jointSigma = af.family == SEQ_BILATERAL_JOINT ? layer_sigmas(frameLayers[0])            // (every frame has frame 0's layers)
+        const std::vector<float> jointSigma = af.family == SEQ_BILATERAL_JOINT || af.family == SEQ_ATROUS ? layer_sigmas(frameLayers[0])            // (every frame has frame 0's layers)
                                               : af.family == SEQ_NLM_JOINT ? layer_sigmas(frameLayers[0], true) : std::vector<float>();
         std::cout << "\tloading " << n << " frames\n";
         // Frames are decoded STRAIGHT INTO pinned host memory (mid_image_load_pinned) and the results land in pinned
@@ -672,6 +687,10 @@ public:
                 MID_CHECK(mid_sequence_nlm_layers_temporal(c, &np, frames, nf, lp, L, kk, start, count, outs, out_fmt, 1, t)); break;
             case SEQ_BILATERAL_JOINT:      // one weight from all layers
                 MID_CHECK(mid_sequence_bilateral_joint(c, &bpp, jointSigma.data(), frames, nf, lp, L, kk, start, count, outs, out_fmt, 1, t)); break;
+            case SEQ_ATROUS: {             // N passes of the 5x5 kernel with holes, every frame alone (a block is a range of the sequence)
+                const mid_atrous_params ap{bpp.width, bpp.height, 0, opt.passes, opt.atrous_sigma_color, bpp.format};
+                MID_CHECK(mid_sequence_atrous_joint(c, &ap, jointSigma.data(), frames, nf, lp, L, start, count, outs, out_fmt, 1, t)); break;
+            }
             case SEQ_NLM_JOINT:            // one patch weight from all layers (jointSigma: the h of each layer)
                 MID_CHECK(mid_sequence_nlm_joint(c, &np, jointSigma.data(), frames, nf, lp, L, kk, start, count, outs, out_fmt, 1, t)); break;
             case SEQ_BILATERAL_TEMPORAL:   // plain or with the layers
@@ -802,6 +821,7 @@ public:
         std::string words = af.words;
         if (af.bilateral()) words += " r=" + std::to_string(opt.radius);
         if (use_layers && af.family != SEQ_BILATERAL) words += " + " + std::to_string(L) + " layers";
+        if (af.family == SEQ_ATROUS) words += ", " + std::to_string(opt.passes) + " passes";
         if (af.windowed()) words += (words.empty() ? "k=" : ", k=") + std::to_string(k);
         std::cout << "\t" << n << " frames, " << words
                   << ", " << G << " device(s): " << sec << " sec, "
@@ -881,7 +901,12 @@ static void usage()
         "                            and nlm-joint (not part of all): joint layer-guided NLM, ONE weight per search offset from the\n"
         "                            patch distances of all of the image's layers, each layer with its own h (--h-layers, else\n"
         "                            --nlm-h for all; --search / --patch apply; .png layers only, as nlm-layers),\n"
-        "                            output output-nonlinear-nlm-joint.{png,exr}.\n"
+        "                            output output-nonlinear-nlm-joint.{png,exr};\n"
+        "                            and atrous (not part of all): the edge-avoiding a-trous filter, --passes passes of a 5x5 B3-spline\n"
+        "                            kernel, pass i sampling with holes at step 2^i (five passes reach +-62 pixels), every tap weighed\n"
+        "                            by all of the image's layers at once as in joint (--sigma-layers, else --sigma-c for all; the\n"
+        "                            layer rules of joint, .png or .exr) and, with --atrous-sigma-color, by the colour itself,\n"
+        "                            output output-nonlinear-atrous.{png,exr}.\n"
         "                            Layer files: .png (RGBA8) -- or, for the bilateral modes only (layers and joint here, layers,\n"
         "                            layers-temporal, joint and joint-temporal under --animation-filter), .exr: normals, depth, HDR albedo as rendered, read as\n"
         "                            RGBA32F, or as RGBA16F with --half; all layers of a run must have one format; nlm-layers and\n"
@@ -897,6 +922,9 @@ static void usage()
         "  --h-layers A,B,...        the joint NLM modes: one h per layer, in the sorted order the layer files are found in (the run\n"
         "                            prints one `layer <file> h <value>` line each); a count other than the layer count is refused.\n"
         "                            Default: --nlm-h for every layer\n"
+        "  --passes N                the a-trous modes: passes of the 5x5 kernel, 1..8 (default 5; pass i has step 2^i)\n"
+        "  --atrous-sigma-color X    the a-trous modes: sigma of the colour term at pass 0, halved with every pass (default 0: no\n"
+        "                            colour term, the layers alone stop the filter at edges)\n"
         "  --search LO,HI --patch LO,HI   half-open NLM ranges (default -7,7 and -3,3; 21x21/7x7 is -10,11 and -3,4)\n"
         "  --temporal-k K            multiframe: frames t-K..t+K of the sorted sequence instead of the reference's list\n"
         "  --animation               denoise EVERY sibling frame with temporal NLM (window +-K, default 2) instead of the mode list\n"
@@ -925,7 +953,10 @@ static void usage()
         "                            layers, --h-layers; .png layers only) of every frame alone (nlm-joint ignores --temporal-k) or\n"
         "                            over the frames t-K..t+K (K = --temporal-k, default 2; frame blocks and halo of\n"
         "                            nlm-layers-temporal, not with --halo rccl), outputs output-animation-nonlinear-nlm-joint-* and\n"
-        "                            output-animation-nonlinear-nlm-joint-multiframe-*\n"
+        "                            output-animation-nonlinear-nlm-joint-multiframe-*;\n"
+        "                            or atrous: the a-trous filter of every frame alone (--passes, --sigma-layers,\n"
+        "                            --atrous-sigma-color; the layer rules of joint; it ignores --temporal-k, frame blocks have no\n"
+        "                            halo, not with --halo rccl), outputs output-animation-nonlinear-atrous-*\n"
         "  --gpus N                  animation mode: split the sequence into N frame blocks, one per device\n"
         "  --halo host|rccl          animation mode with --gpus N: 'host' (default) streams every block plus its K halo frames from host\n"
         "                            memory through the overlapped pipeline; 'rccl' keeps each block resident in its GPU's HBM and\n"
@@ -981,6 +1012,11 @@ int main(int argc, char **argv)
             while (pos < s.size()) { size_t c = s.find(',', pos); if (c == std::string::npos) c = s.size(); opt.h_layers.push_back((float)atof(s.substr(pos, c - pos).c_str())); pos = c + 1; }
             if (opt.h_layers.empty()) { std::cerr << "--h-layers needs a comma list of values\n"; usage(); return EXIT_FAILURE; }
         }
+        else if (a == "--passes") {
+            opt.passes = atoi(next());
+            if (opt.passes < 1 || opt.passes > 8) { std::cerr << "--passes " << opt.passes << " is outside 1..8\n"; return EXIT_FAILURE; }
+        }
+        else if (a == "--atrous-sigma-color") opt.atrous_sigma_color = (float)atof(next());
         else if (a == "--search") { if (!pair_arg(next(), opt.search_lo, opt.search_hi)) { usage(); return EXIT_FAILURE; } }
         else if (a == "--patch") { if (!pair_arg(next(), opt.patch_lo, opt.patch_hi)) { usage(); return EXIT_FAILURE; } }
         else if (a == "--temporal-k") opt.temporal_k = atoi(next());
@@ -1039,6 +1075,7 @@ int main(int argc, char **argv)
             if (listed("nlm-layers")) { std::cout << "######\nRunning on GPU (nonlocal + layers)\n######\n"; app.RunOnGPU(true, true, false, false, true); print_time(); }
             if (listed("joint")) { std::cout << "######\nRunning on GPU (joint bialteral)\n######\n"; app.RunOnGPU(false, true, false, false, true, true); print_time(); }
             if (listed("nlm-joint")) { std::cout << "######\nRunning on GPU (joint nonlocal)\n######\n"; app.RunOnGPU(true, true, false, false, true, true); print_time(); }
+            if (listed("atrous")) { std::cout << "######\nRunning on GPU (a-trous + layers)\n######\n"; app.RunOnGPU(false, true, false, false, true, true, true); print_time(); }
         }
         if (opt.run_cpu) {
             for (int threads : opt.cpu_threads) {

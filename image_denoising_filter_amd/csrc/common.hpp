@@ -20,6 +20,7 @@ struct mid_pipe_cache {
     std::mutex mu;                      // one pipeline call per context at a time: the calls share the context's four streams
     mid_pipe_set ring, out;             // mid_sequence_nlm* / mid_sequence_bilateral: uploaded frames (2k + 4), output slots (4)
     mid_pipe_set layers;                // mid_sequence_bilateral with guide layers: n_layers per ring slot
+    mid_pipe_set atrous;                // mid_sequence_atrous_joint: the RGBA32F levels between passes, two per kernel stream
     mid_pipe_set target, slots, weights, result;   // mid_nlm_multiframe
     std::vector<hipEvent_t> ev;
     mid_pipe_last last;                 // mid_pipe_last_timeline reads the events of the last call back
@@ -221,6 +222,15 @@ int bilateral_joint_out(mid_ctx *ctx, const mid_bilateral_params *p, const float
                         int out_fmt, hipStream_t s);
 int bilateral_joint_check(const mid_bilateral_params *p, const char *who, const float *layer_sigma, bool have_layers, int n_layers,
                           int n_frames, int k);
+
+// mid_atrous_joint without its checks (the caller has made them), one launch per pass on `s`: atrous.hip; used by the frame
+// pipeline (mid_sequence_atrous_joint), not exported.  scratch0 / scratch1: the RGBA32F levels between passes (the first needed
+// from two passes on, the second from three).  atrous_check: what both entry points check before their own tables -- size,
+// pass range, colorSigma, the format word, n_layers in 1..16, a layer table, every sigma finite and > 0 (NULL is refused).
+int atrous_joint_out(mid_ctx *ctx, const mid_atrous_params *p, const float *layer_sigma, const void *in, const uint32_t *const *layers,
+                     int n_layers, void *out, int out_fmt, void *scratch0, void *scratch1, hipStream_t s);
+int atrous_check(const mid_atrous_params *p, const char *who, const float *layer_sigma, bool have_layers, int n_layers);
+size_t atrous_scratch_frames(int n_passes);
 
 // ROCTx ranges (csrc/markers.cpp): no-ops unless the process already holds a ROCTx (rocprofv3 --marker-trace preloads one).
 bool markers_active();

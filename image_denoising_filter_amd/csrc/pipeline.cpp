@@ -90,7 +90,7 @@ struct DrainOnExit {
 void mid::pipe_cache_release(mid_ctx *ctx)
 {
     mid_pipe_cache &c = ctx->pipe;
-    for (mid_pipe_set *s : {&c.ring, &c.out, &c.layers, &c.target, &c.slots, &c.weights, &c.result}) {
+    for (mid_pipe_set *s : {&c.ring, &c.out, &c.layers, &c.atrous, &c.target, &c.slots, &c.weights, &c.result}) {
         for (void *q : s->p) (void)hipFree(q);
         s->p.clear();
         s->bytes = 0;
@@ -111,6 +111,8 @@ struct Stage {
     int n_layers;
     bool proven;                              // outputs are kernel-stored only inside ONE page-locked mapping (every stage but temporal NLM)
     const char *marker;                       // the launch range, "nlm %d": profiles and the marker tests read these names
+    size_t level_bytes = 0;                   // a stage that keeps levels between its passes (a-trous): bytes of one, and how many
+    int n_levels = 0;                         // per kernel stream -- reserved in the context's cache (pipe.atrous) for both streams
 };
 
 // Outputs [first, first+count) of an n-frame host sequence; frames outside that range are only
@@ -187,6 +189,7 @@ static int run_pipeline(mid_ctx *ctx, const Stage &st, const Launch &launch, con
     if (int rc = reserve(dring, ring, in_bytes)) return rc;
     if (n_layers) { if (int rc = reserve(dlayers, (size_t)ring * n_layers, layer_bytes)) return rc; }
     if (!direct) { if (int rc = reserve(dout, DEPTH * B, dl_bytes)) return rc; }
+    if (st.n_levels) { if (int rc = reserve(ctx->pipe.atrous, (size_t)(overlap ? 2 : 1) * st.n_levels, st.level_bytes)) return rc; }
     if (int rc = reserve_events(ctx->pipe, 2 * (size_t)n_up + 4 * (size_t)nb)) return rc;
     ctx->pipe.last = mid_pipe_last{};
     struct Events { hipEvent_t *ev; } up0{ctx->pipe.ev.data()}, up1{up0.ev + n_up}, c0{up1.ev + n_up}, c1{c0.ev + nb}, d0{c1.ev + nb}, d1{d0.ev + nb};
@@ -567,6 +570,34 @@ extern "C" int mid_sequence_bilateral_joint(mid_ctx *ctx, const mid_bilateral_pa
 {
     return sequence_bilateral_temporal(ctx, "sequence_bilateral_joint", true, p, layer_sigma, host_frames, n_frames, host_layers, n_layers, k,
                                        first, count, host_out, out_format, overlap, timings_ms);
+}
+
+// The a-trous filter of every frame: mid_sequence_bilateral_joint's schedule at k = 0 (frames are independent, outputs [first,
+// first + count) of the sequence) with atrous_joint_out as the compute stage.  The levels between the passes come from the
+// context's cache: one set of up to two RGBA32F frames per kernel stream, so that consecutive outputs, which alternate between
+// the two streams, never share a level.
+extern "C" int mid_sequence_atrous_joint(mid_ctx *ctx, const mid_atrous_params *p, const float *layer_sigma,
+                                         const void *const *host_frames, int n_frames, const void *const *host_layers, int n_layers,
+                                         int first, int count, void *const *host_out, int out_format, int overlap, float *timings_ms)
+{
+    Bind b(ctx, nullptr);
+    if (b.rc) return b.rc;
+    const char *who = "sequence_atrous_joint";
+    if (int rc = refuse_if_recording(ctx->compute, "mid_sequence_atrous_joint (four streams, host-side waits)")) return rc;
+    if (int rc = atrous_check(p, who, layer_sigma, host_layers != nullptr, n_layers)) return rc;
+    if (int rc = check_sequence({who, "n_frames", true, true}, host_frames, n_frames, host_layers, n_layers, 0, first, count, host_out, out_format)) return rc;
+    const size_t npix = (size_t)p->width * p->height;
+    const int n_levels = (int)atrous_scratch_frames(p->n_passes);
+    Stage st{who, p->width, p->height, fmt_frames(p->format), npix * fmt_bytes(fmt_guide(p->format)), host_layers, n_layers, true, "atrous %d"};
+    st.level_bytes = npix * 16; st.n_levels = n_levels;
+    auto launch = [&](const void *const *tbl, int, const uint32_t *const *lt, int, int t0, int bn, void *const *out, int out_fmt, hipStream_t s) {
+        void *const *lv = ctx->pipe.atrous.p.data() + (s == ctx->compute2 ? n_levels : 0);
+        for (int i = 0; i < bn; ++i)              // (k = 0: output t0 + i reads slot t0 + i and its layers only)
+            if (int rc = atrous_joint_out(ctx, p, layer_sigma, tbl[t0 + i], lt + (size_t)(t0 + i) * n_layers, n_layers, out[i], out_fmt,
+                                          n_levels >= 1 ? lv[0] : nullptr, n_levels >= 2 ? lv[1] : nullptr, s)) return rc;
+        return (int)MID_OK;
+    };
+    return run_pipeline(ctx, st, launch, host_frames, n_frames, 0, first, count, host_out, out_format, overlap, timings_ms);
 }
 
 // Device timeline of the context's last mid_sequence_nlm*, mid_sequence_bilateral or mid_sequence_nlm_layers[_temporal] call, read back from the events the call left in the context's

@@ -473,6 +473,102 @@ int mid_sequence_nlm_joint(mid_ctx *ctx, const mid_nlm_params *p, const float *l
                            const void *const *host_frames, int n_frames, const void *const *host_layers, int n_layers,
                            int k, int first, int count, void *const *host_out, int out_format, int overlap, float *timings_ms);
 
+/* ---- a4g: the edge-avoiding a-trous filter guided by render layers -----------------------------
+ * The bilateral family ends at radius 24 and costs (2 radius + 1)^2 taps.  The edge-avoiding a-trous wavelet filter (Dammertz et
+ * al. 2010; the spatial stage of SVGF) reaches much further with the same guide layers: N passes of a 5x5 B3-spline kernel, pass
+ * i sampling with holes at step s = 2^i.  Five passes reach +-62 pixels for 125 taps per pixel, eight reach +-510.
+ * C_0 is the frame widened to fp32 (RGBA8 texels as c/255, as everywhere); G_l, l = 0 .. n_layers-1, are the frame's guide
+ * layers; k1 = (1, 4, 6, 4, 1)/16 and K(o) = k1[i+2] k1[j+2] for o = (i, j), |i|, |j| <= 2.  Pass i, for q = p + s o:
+ *   w(p,o)     = K(o) * prod_l exp(-0.5 |G_l(p) - G_l(q)|^2_rgb / sigma_l^2)
+ *                     * [colorSigma > 0:  exp(-0.5 |C_i(p) - C_i(q)|^2_rgb / (colorSigma * 2^-i)^2)]
+ *   C_{i+1}(p) = sum_o w C_i(q) / sum_o w          over the taps whose q lies inside the image
+ * Taps outside the image are SKIPPED, not read as vec4(0) -- unlike the reference-derived filters, on purpose: at step 16 a zero
+ * texel would darken a 32-pixel border.  The centre tap always counts, so the denominator is never 0 for finite inputs (there is
+ * no magenta sentinel here).  All four colour channels are filtered; the colour term reads r, g, b.  Guide texels mean what
+ * sections a3 / a4e say: IEEE values, alpha ignored, no clamping, non-finite texels by IEEE arithmetic (a NaN guide texel, or
+ * Inf against Inf, poisons the pixels whose taps meet it; a skipped tap poisons nothing).
+ * One frame per call; there is no temporal form.  p->first_pass is the ABSOLUTE index of the call's first pass (its step is
+ * 2^first_pass), so a filter can be continued: passes [0, N) in one call are, bit for bit, N calls of one pass each with
+ * first_pass = i through RGBA32F buffers.
+ * Data path: the levels between passes are RGBA32F frames in `scratch` -- mid_atrous_scratch_bytes(p): 0 bytes for one pass
+ * (NULL is accepted), one float frame for two passes, two for three and more; 16-byte aligned -- and the last pass stores
+ * out_format, mid_pack_u8 / mid_pack_f16 of the float result.  p->format: the frame's MID_FMT_* and, through MID_FMT_WITH_GUIDE,
+ * the guide format, as in a4e.  layer_sigma: n_layers host floats, read during the call; NULL is refused (there is no sigma to
+ * fall back on: colorSigma belongs to the colour term, and 0 switches that off).
+ * Arithmetic: layer l is scaled by sc_l = (float)(sqrt(0.5 log2 e) / (double)sigma_l) and a guide value g enters as the fp32
+ * product g * sc_l; the colour differences are scaled by scc_i = (float)(sqrt(0.5 log2 e) / (colorSigma * 2^-i)).  The exponent
+ * of a tap is one chain of FMAs that starts at 0: arg = fma(-d, d, arg) with d = G_l(p) sc_l - G_l(q) sc_l for layer 0's x, y,
+ * z, then layer 1's, ..., then d = (C(p) - C(q)) scc_i for r, g, b; one 2^x follows and K(o) multiplies its result (K(o) is
+ * exact in fp32).  The sums run over the taps in the order j = -2 .. 2 (rows), inside it i = -2 .. 2, each as
+ * acc = fma(C(q), w, acc) and accw += w, and the pixel is acc / accw, an IEEE division per channel.  Every class computes
+ * exactly this, so a pixel does not depend on the class that computed it.
+ * Precision: within 1e-5 * max(1, |ref|) of the formula in float64, end to end over up to 8 passes, while |g| <= 16 sigma_l.
+ * Bit identities:
+ *   - the chain identity above;
+ *   - an RGBA8 / RGBA16F frame gives the bits of the RGBA32F call on the widened frame, a half guide the bits of the float guide
+ *     it widens to, a float guide c/255 (fp32 quotient) the bits of the RGBA8 guide c; RGBA8 / RGBA16F outputs are mid_pack_u8 /
+ *     mid_pack_f16 of the float result;
+ *   - appending all-zero layers (any sigmas) leaves the bits, and one live layer in any slot among zero layers gives the bits
+ *     of that layer alone.
+ * Classes (lanes run along x in all three; no scratch memory; eight waves per workgroup in the LDS classes):
+ *   step     n_layers  kernel  tile     LDS tile   LDS bytes  workgroups per CU
+ *   1        1         tiled   64 x 16  68 x 20    38080      4
+ *   1        2         tiled   64 x 16  68 x 20    54400      3
+ *   1        3         tiled   64 x 16  68 x 20    70720      2
+ *   1        4         comb    64 x 8   68 x 12    52224      3
+ *   2        1         tiled   64 x 16  72 x 24    48384      3
+ *   2        2         tiled   64 x 16  72 x 24    69120      2
+ *   2        3         comb    64 x 16  72 x 20    74880      2
+ *   2        4         comb    64 x 8   72 x 12    55296      2
+ *   4        1         comb    64 x 16  80 x 20    44800      3
+ *   4        2         comb    64 x 16  80 x 20    64000      2
+ *   4        3         comb    64 x 8   80 x 12    49920      3
+ *   4        4         comb    64 x 8   80 x 12    61440      2
+ *   8        1         comb    64 x 16  96 x 20    53760      3
+ *   8        2         comb    64 x 16  96 x 20    76800      2
+ *   8        3         comb    64 x 8   96 x 12    59904      2
+ *   8        4         comb    64 x 8   96 x 12    73728      2
+ *   16       1         comb    64 x 16  128 x 20   71680      2
+ *   16       2         comb    64 x 8   128 x 12   61440      2
+ *   16       3         comb    64 x 8   128 x 12   79872      2
+ *   16       4         comb    64 x 8   128 x 12   98304      1
+ *   32       1         comb    64 x 8   192 x 12   64512      2
+ *   32       2         comb    64 x 8   192 x 12   92160      1
+ *   32       3         comb    64 x 8   192 x 12   119808     1
+ *   32       4         comb    64 x 8   192 x 12   147456     1
+ *   1..32    5..16     global  64 x 4   -          0          -
+ *   64, 128  1..16     global  64 x 4   -          0          -
+ * tiled: a workgroup filters 64 x 16 pixels from LDS tiles of (64 + 4 step) x (16 + 4 step) texels -- the colour tile as float4,
+ * three planes of floats per layer, already scaled, the guide format decoded when the tile is filled -- at steps 1 and 2 while two
+ * such workgroups fit the 160 KB of a CU.  comb: the same tiles for rows of ONE residue class y = y0 (mod step), which form an
+ * independent problem: the vertical halo is 4 rows at every step and only the horizontal halo (2 step columns on either side)
+ * grows; 16 rows per workgroup while two workgroups fit a CU, else 8; every step up to 32 that is not tiled.  global: one pixel
+ * per lane, the taps read from global memory.  The class follows from (step, n_layers) and the device's LDS size alone, never
+ * from n_passes or first_pass.
+ * MID_ERR_INVALID before anything is queued, outputs and scratch untouched: a NULL pointer (scratch only where bytes are needed);
+ * n_layers outside 1..16; a sigma that is not finite and > 0; colorSigma < 0 or not finite; first_pass < 0, n_passes < 1 or
+ * first_pass + n_passes > 8; an unknown frame, guide or output format; the alignment rules of a4e (scratch: 16 bytes); `out` or
+ * `scratch` overlapping `in`, a layer or each other; width or height < 1, or 2^30 pixels and more. */
+typedef struct mid_atrous_params {
+    int32_t width, height;
+    int32_t first_pass;   /* absolute index of the first pass, 0..7 */
+    int32_t n_passes;     /* >= 1, first_pass + n_passes <= 8 */
+    float   colorSigma;   /* 0: no colour term; otherwise > 0 and finite */
+    int32_t format;       /* MID_FMT_* of the frame, guide format through MID_FMT_WITH_GUIDE as in a4e */
+} mid_atrous_params;
+size_t mid_atrous_scratch_bytes(const mid_atrous_params *p);
+int mid_atrous_joint(mid_ctx *ctx, const mid_atrous_params *p, const float *layer_sigma /* n_layers host floats */, const void *in,
+                     const uint32_t *const *layers /* host array of n_layers device ptrs; cast RGBA16F / RGBA32F layers with MID_FMT_WITH_GUIDE */,
+                     int n_layers, void *out, int out_format, void *scratch, void *stream);
+/* mid_sequence_bilateral_joint at k = 0 (section a8) with mid_atrous_joint as the compute stage: host frames and host layers in,
+ * host frames out, output t with the bits of mid_atrous_joint for frame t.  Same ring, same layer ring (4 / 8 / 16 B per texel),
+ * same direct-store rule, same refusals (a call inside a recording among them), same timings_ms and timeline export; plus the
+ * refusals above, which leave host_out and timings_ms untouched.  The levels between passes live in the context's cache, one
+ * set per kernel stream of the schedule, and are released with the rest (mid_ctx_release_cached). */
+int mid_sequence_atrous_joint(mid_ctx *ctx, const mid_atrous_params *p, const float *layer_sigma,
+                              const void *const *host_frames, int n_frames, const void *const *host_layers, int n_layers,
+                              int first, int count, void *const *host_out, int out_format, int overlap, float *timings_ms);
+
 /* ---- a5: normalize ----------------------------------------------------------------------
  * One dispatch of shaders/normalize.comp (RecordCommandsOfExecuteAndTransfer(normKernel=true)):
  * out = weightColor / normWeight, or (1,0,1,1) where normWeight == 0; bindings {0: out; 1: W}. */

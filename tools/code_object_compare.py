@@ -56,10 +56,12 @@ def main():
     ap.add_argument("--change", required=True)
     ap.add_argument("--out")
     ap.add_argument("--gone", default="", help="comma-separated .hip files whose kernels may disappear with the file")
+    ap.add_argument("--new", default="", help="comma-separated .hip files that may appear with their kernels")
     args = ap.parse_args()
     (old, old_lib), (new, new_lib) = units(args.parent), units(args.change)
     new_by_name = dict(new)
     gone_ok = set(filter(None, args.gone.split(",")))
+    new_ok = set(filter(None, args.new.split(",")))
     lines = ["gfx950 code objects of libmi_denoise.so, one per translation unit in link order (_codeobj.gfx950_code_objects): parent -> change",
              f"{'file':26s} {'parent bytes':>12s} {'sha256[:16]':16s} {'change bytes':>12s} {'sha256[:16]':16s}  kernels: compared / identical (function bytes, descriptor outside its entry offset)"]
     bad = []
@@ -83,14 +85,15 @@ def main():
     for name, co in new:
         if name not in dict(old):
             lines.append(f"{name:26s} {'-':>12s} {'-':16s} {len(co):12d} {sha(co):16s}  new, {len(kernels(co))} kernels")
-            bad.append(f"{name} is new")
+            if name not in new_ok:
+                bad.append(f"{name} is new")
     for w in _codeobj.BENCH_KERNELS:
         a, b = (_codeobj.fingerprint(lib, w)["kernel_code_sha256"][:16] for lib in (old_lib, new_lib))
         lines.append(f"bench.py --workload {w}: timed kernel's code + descriptor sha256 {a} -> {b} {'identical' if a == b else 'DIFFERENT'}")
         if a != b:
             bad.append(f"fingerprint {w}")
     lines.append(f"library: {os.path.getsize(old_lib)} -> {os.path.getsize(new_lib)} bytes")
-    lines.append(f"kernels that differ, appear or disappear outside the removed files: {len(bad)}" + "".join("\n    " + b for b in bad))
+    lines.append(f"kernels that differ, appear or disappear outside the removed and the new files: {len(bad)}" + "".join("\n    " + b for b in bad))
     text = "\n".join(lines) + "\n"
     if args.out:
         open(args.out, "w").write(text)
