@@ -141,6 +141,8 @@ extern "C" void mid_ctx_destroy(mid_ctx *ctx)
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     for (hipStream_t s : {ctx->compute, ctx->compute2, ctx->upload, ctx->download}) (void)hipStreamSynchronize(s);
+    if (ctx->edge.s) { (void)hipStreamSynchronize(ctx->edge.s); (void)hipStreamDestroy(ctx->edge.s); }     // nlm_edge.hip
+    for (hipEvent_t e : {ctx->edge.fork, ctx->edge.join}) if (e) (void)hipEventDestroy(e);
     pipe_cache_release(ctx);
     bounce_release(ctx);
     for (hipStream_t s : {ctx->compute, ctx->compute2, ctx->upload, ctx->download}) (void)hipStreamDestroy(s);

@@ -37,6 +37,17 @@ struct mid_bounce {
     size_t chunk = 0;
 };
 
+// The stream a long NLM launch runs its packed right-edge launch on, beside the main launch (csrc/nlm_edge.hip): the device's LOWEST
+// priority, as the sharded call's boundary streams and for their reason (sharded.cpp) -- a pool of hardware queues of the library's own,
+// and workgroups that are dispatched where no workgroup of the main launch waits.  Created by the first launch that packs, freed with
+// the context.  fork / join order it behind and before the caller's stream; mu is held from the fork's record to the join's wait.
+struct mid_edge {
+    std::mutex mu;
+    hipStream_t s = nullptr;
+    hipEvent_t fork = nullptr, join = nullptr;
+    bool failed = false;                // the stream or an event could not be created: launches stay whole from then on
+};
+
 struct mid_ctx {
     int device;
     // The four streams are created together, in this order, by mid_ctx_create (capi.cpp explains why and at which priorities).
@@ -52,8 +63,9 @@ struct mid_ctx {
     // device, so it is tracked per context; contexts may be used from different threads)
     std::mutex mu;
     std::unordered_set<const void *> lds_configured;
+    mid_edge edge;
     mid_pipe_cache pipe;
-    mid_bounce bounce_up, bounce_down;   // pageable host memory never reaches hipMemcpyAsync: see csrc/hostcopy.cpp
+    mid_bounce bounce_up, bounce_down;  // pageable host memory never reaches hipMemcpyAsync: see csrc/hostcopy.cpp
 };
 
 namespace mid {

@@ -104,11 +104,16 @@ static int dispatch_ranges(mid_ctx *ctx, const mid_nlm_params *p, NlmArgs &a, hi
     }
     if (p->search_lo == -10 && p->search_hi == 11 && p->patch_lo == -3 && p->patch_hi == 4) {   // 21x21 / 7x7 (benchmark)
         if (multi) return launch_strip<-10, 11, -3, 4, 8, 4, FMT, FUSED, FUSED>(ctx, a, s);
-        return launch_strip<-10, 11, -3, 4, 8, 4, FMT, FUSED, false>(ctx, a, s);
+        // (a long k = 0 launch: where the frame's last tile column holds a few columns only, the packed edge launch covers it, nlm_edge.hip)
+        return nlm_dispatch_edge(ctx, p, a, s, FMT, FUSED, [](mid_ctx *c, NlmArgs &b, hipStream_t t, int less_cols) {
+            return launch_strip<-10, 11, -3, 4, 8, 4, FMT, FUSED, false>(c, b, t, 0, ~0u, less_cols);
+        });
     }
     if (p->search_lo == -7 && p->search_hi == 7 && p->patch_lo == -3 && p->patch_hi == 3) {     // nonlocal.comp:5-6 as shipped
         if (multi) return launch_strip<-7, 7, -3, 3, 8, 4, FMT, FUSED, FUSED>(ctx, a, s);
-        return launch_strip<-7, 7, -3, 3, 8, 4, FMT, FUSED, false>(ctx, a, s);
+        return nlm_dispatch_edge(ctx, p, a, s, FMT, FUSED, [](mid_ctx *c, NlmArgs &b, hipStream_t t, int less_cols) {
+            return launch_strip<-7, 7, -3, 3, 8, 4, FMT, FUSED, false>(c, b, t, 0, ~0u, less_cols);
+        });
     }
     // Any other search window: the same strip kernel with the search range -- and the texel format -- as run-time arguments
     // (LDS pitch no longer a folded constant: a few % slower), instantiated in nlm_rt.hip (patches up to 9x9) and nlm_rt4.hip

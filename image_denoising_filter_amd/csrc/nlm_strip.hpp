@@ -1,7 +1,7 @@
 // nlm_strip.hpp -- the NLM strip kernel (see nlm.hip for the algorithm) and its launcher, shared by the translation units that
 // instantiate it: nlm.hip (the two tuned windows, the per-pixel fallback, the C-ABI), nlm_rt.hip (any search window, patches up to 9x9,
 // strips of eight rows) and nlm_rt4.hip (patches of 10x10 .. 16x16, strips of four rows).  Three files so that the instantiations
-// compile in parallel.  What was measured and rejected on the way here (pair symmetry, prefetching loops, multi-pass tiles, packed
+// compile in parallel.  (And nlm_small.hip: the tuned windows' copies for small launches; nlm_edge.hip: their packed right-edge shape.)  What was measured and rejected on the way here (pair symmetry, prefetching loops, multi-pass tiles, packed
 // fp32, other priorities ...) is indexed in tools/experiments/README.md; none of it is in this file.
 #pragma once
 #include "common.hpp"
@@ -15,6 +15,14 @@ namespace mid {
 
 constexpr int kFmtRuntime = -1;  // FMT of the run-time-window instantiations: the texel format is the kernel argument NlmArgs::fmt
 constexpr int kNlmWalk = 21;     // search rows walked innermost in runs of this many (measured against 3 and 7: profiles/r03_walk_ab.txt)
+// The packed shape of the ragged right-edge tile column (TAG = kNlmEdgeTag, see nlm_strip_kernel; instantiated in nlm_edge.hip): four
+// groups of 16 lanes a wave, each on its own tile of the column; a group's tile columns 0 .. kNlmEdgeCols - 1 are real, and a tile row
+// is kNlmEdgePitch texels.  nlm_edge_valid: the columns of the last tile column that lie in the image -- packed when
+// nlm_edge_packs(valid, patch width, tile columns).
+constexpr int kNlmEdgeTag = 2, kNlmEdgeGroups = 4, kNlmEdgeLanes = 16, kNlmEdgeCols = 12, kNlmEdgePitch = 32;
+constexpr int nlm_edge_valid(int w, int patch_w) { return w - (w - 1) / (64 - (patch_w - 1)) * (64 - (patch_w - 1)); }
+constexpr bool nlm_edge_packs(int valid, int patch_w, int tiles_x) { return tiles_x >= 2 && valid + patch_w - 1 <= kNlmEdgeCols; }
+constexpr int nlm_edge_tile_rows(int tile_h, int patch_w, int search_w) { return kNlmEdgeGroups * tile_h + patch_w - 1 + search_w - 1; }
 
 struct NlmArgs {
     int w, h;
@@ -107,8 +115,21 @@ constexpr int nlm_min_waves(bool rts, bool multi, int pw)
 // each taking half of an 8-row strip (R = 4; even waves the upper, odd waves the lower four rows) with the strip's own vertical sums
 // (the plan of nlm_vbox_plan.hpp for its four output rows): identical output bits, 0.6 of a strip's instructions per wave, and two waves per SIMD on a CU that holds this
 // workgroup alone -- where a 4-wave workgroup alone leaves every wave a SIMD to itself at half issue rate.
-// TAG: no effect on the code -- it only names a second copy of an instantiation, so that the copies in nlm_small.hip (compiled with another
-// scheduling strategy, see there) and in nlm.hip are different symbols.
+// TAG: 0 and 1 have no effect on the code -- they only name two copies of an instantiation, so that the copies in nlm_small.hip (compiled
+// with another scheduling strategy, see there) and in nlm.hip are different symbols.
+// TAG = kNlmEdgeTag: the PACKED shape for the ragged right-edge tile column of a long launch (nlm_edge.hip).  A wave yields VW columns, and
+// where the last tile column holds only a few of the image's (1920 = 33 x 58 + 6) its workgroups walk every offset for a tenth of a tile.
+// Packed, a wave's 64 lanes are four groups of 16: group g = lane >> 4 works on tile row 4q + g of the edge column, lane sub = lane & 15
+// of a group owns column X0 + PLO + sub, and wave wv takes strip wv of all four tiles -- one workgroup for four vertically consecutive edge
+// tiles.  The LDS holds one tall tile of kNlmEdgePitch columns and 4 * TILE_H + PW - 1 + SW - 1 rows (78,848 B at the benchmark's window:
+// still two workgroups a CU); group g reads from row g * TILE_H down.  Outputs are stored from lanes sub in [-PLO, -PLO + valid); such a
+// lane's horizontal sum reaches lanes sub - NL .. sub + NR of its own group, all below kNlmEdgeCols, and what the whole-wave DPP shifts
+// carry across a group boundary lands in lanes that store nothing.  Lanes from kNlmEdgeCols on read a clamped tile column, so that no
+// read leaves the tile; groups whose tile row does not exist and rows at or beyond h store nothing.  There is no opaque vote -- an edge
+// tile always holds out-of-image texels -- so the shape carries the general form only, the form these pixels get in the whole shape.  A pixel
+// keeps its row within the strip and its column's neighbours, and each lane does what it does in the whole shape on the same operands in
+// the same order: identical output bits (as HALF).  Everything the shape changes sits under `EDGE`, a constant: the other instantiations
+// compile to the instructions they had.
 template <int SLO, int SHI, int PLO, int PHI, int R, int NW, int FMT, bool FUSED, bool MULTI, bool HALF = false, int TAG = 0>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(nlm_min_waves(SLO == 0 && SHI == 0, MULTI, PHI - PLO), 2)))
 void nlm_strip_kernel(const NlmArgs a)
@@ -123,6 +144,11 @@ void nlm_strip_kernel(const NlmArgs a)
     const int SW = RTS ? a.shi - a.slo : SHI - SLO;
     const int LW = 64 + SW - 1;
     const int LH = TILE_H + PW - 1 + SW - 1;
+    constexpr bool EDGE = TAG == kNlmEdgeTag;
+    const int PITCH = EDGE ? kNlmEdgePitch : LW;         // texels from one tile row to the next
+    static_assert(!EDGE || (!RTS && !MULTI && !HALF && R == 8 && NW == 4), "EDGE: the tuned windows' whole shape, one neighbour frame");
+    static_assert(!EDGE || (kNlmEdgeCols + (RTS ? 0 : SHI - SLO) - 1 <= kNlmEdgePitch && NL + NR < kNlmEdgeCols && kNlmEdgeCols <= kNlmEdgeLanes),
+                  "EDGE: a group's real columns and their search range fit a tile row");
     static_assert(PLO <= 0 && PHI >= 1 && (RTS || SHI - SLO >= 1), "ranges must contain 0");
     static_assert(!HALF || (R == 4 && NW == 8), "HALF: eight waves of four rows");
     static_assert(FMT != kFmtRuntime || RTS, "only the run-time-window instantiations take the format as an argument");
@@ -130,17 +156,21 @@ void nlm_strip_kernel(const NlmArgs a)
     extern __shared__ float4 lds[];
 
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const unsigned tiles = (unsigned)(a.tiles_x * a.tiles_y);
+    // EDGE: a workgroup per kNlmEdgeGroups tile rows of the last tile column, frame by frame; ty is its first tile row
+    const unsigned tiles = EDGE ? ((unsigned)a.tiles_y + kNlmEdgeGroups - 1u) / kNlmEdgeGroups : (unsigned)(a.tiles_x * a.tiles_y);
     const unsigned bid = blockIdx.x + a.wg_first;
     const int fz = (int)(bid / tiles);
-    const unsigned trem = xcd_remap_in_frame(bid - (unsigned)fz * tiles, tiles, (unsigned)fz);
-    const int ty = (int)(trem / (unsigned)a.tiles_x), tx = (int)(trem - (unsigned)ty * a.tiles_x);
+    const unsigned trem = EDGE ? bid - (unsigned)fz * tiles : xcd_remap_in_frame(bid - (unsigned)fz * tiles, tiles, (unsigned)fz);
+    const int ty = EDGE ? (int)trem * kNlmEdgeGroups : (int)(trem / (unsigned)a.tiles_x);
+    const int tx = EDGE ? a.tiles_x - 1 : (int)(trem - (unsigned)ty * a.tiles_x);
+    const int grp = EDGE ? lane / kNlmEdgeLanes : 0;                 // EDGE: this lane's tile among the workgroup's four ...
+    const int col = EDGE ? lane % kNlmEdgeLanes : lane;              // ... and its column in that tile
 
     const int w = a.w, h = a.h;
     const int X0 = tx * VW, Y0 = ty * TILE_H;
-    const int gx = X0 + PLO + lane;          // column owned by this lane
-    const int yb = Y0 + wv * R;              // first output row of this wave
-    const bool wave_active = yb < h;
+    const int gx = X0 + PLO + col;           // column owned by this lane
+    const int yb = Y0 + grp * TILE_H + wv * R;   // first output row of this wave (EDGE: of this lane's group)
+    const bool wave_active = Y0 + wv * R < h;
 
     const int t_out = a.first + fz;          // FUSED: output frame
     const void *target = FUSED ? a.frames.p[t_out] : a.target;
@@ -186,6 +216,8 @@ void nlm_strip_kernel(const NlmArgs a)
             if (a.fmt == MID_FMT_RGBA8) fill_tile<MID_FMT_RGBA8, false>(lds, LW, LH, nb, w, h, X0 + PLO + slo, Y0 + PLO + slo, tid, NW * 64, a.sk, opaque);
             else if (a.fmt == MID_FMT_RGBA16F) fill_tile<MID_FMT_RGBA16F, false>(lds, LW, LH, nb, w, h, X0 + PLO + slo, Y0 + PLO + slo, tid, NW * 64, a.sk, opaque);
             else fill_tile<MID_FMT_RGBA32F, false>(lds, LW, LH, nb, w, h, X0 + PLO + slo, Y0 + PLO + slo, tid, NW * 64, a.sk, opaque);
+        } else if constexpr (EDGE) {      // the tall tile of the four groups
+            fill_tile<FMT, false>(lds, kNlmEdgePitch, nlm_edge_tile_rows(TILE_H, PW, SHI - SLO), nb, w, h, X0 + PLO + slo, Y0 + PLO + slo, tid, NW * 64, a.sk, opaque);
         } else {
             fill_tile<FMT, false>(lds, LW, LH, nb, w, h, X0 + PLO + slo, Y0 + PLO + slo, tid, NW * 64, a.sk, opaque);
         }
@@ -211,7 +243,7 @@ void nlm_strip_kernel(const NlmArgs a)
         // chosen per workgroup and neighbour frame from the tile's CONTENT, and every launch shape of a window -- batched, single,
         // HALF tail, accumulate-only, temporal -- carries both forms, so a pixel's bits do not depend on the launch.  (In the opaque
         // form the 0.001 is added after the weights instead of before them: the last bit of normWeight, nothing else.)
-        constexpr bool kOpaqueForm = !RTS;
+        constexpr bool kOpaqueForm = !RTS && !EDGE;
         bool opaque = false;
         if constexpr (kOpaqueForm) {
             bool mine = true;
@@ -329,10 +361,10 @@ void nlm_strip_kernel(const NlmArgs a)
         auto run = [&](auto LT, auto A1, const bool FULL, const float4 *colp, int steps) __attribute__((always_inline)) {
             float4 n[DR];
 #pragma unroll
-            for (int m = 0; m < DR; ++m) n[m] = colp[m * LW];
+            for (int m = 0; m < DR; ++m) n[m] = colp[m * PITCH];
 #pragma unroll
             for (int j = 0; j < WALK; ++j) {
-                if (FULL || j < steps) step(LT, A1, j, n, colp + (DR + j) * LW, FULL ? j + 1 < WALK : j + 1 < steps);
+                if (FULL || j < steps) step(LT, A1, j, n, colp + (DR + j) * PITCH, FULL ? j + 1 < WALK : j + 1 < steps);
             }
             // rows still in the window that never were centre rows: keep their alpha formally live (see above)
             const float last_w = decltype(A1)::value ? acc[R - 1].w : accw[R - 1];
@@ -342,7 +374,9 @@ void nlm_strip_kernel(const NlmArgs a)
         auto walk = [&](auto A1) {
             for (int sy0 = 0; sy0 < SW; sy0 += WALK) {
                 const int steps = sy0 + WALK < SW ? WALK : SW - sy0;
-                const float4 *rowp = lds + (wv * R + sy0) * LW + lane;
+                // (EDGE: the group's tile starts grp * TILE_H rows down; a lane past the real columns reads the last column whose search range ends inside the row)
+                const float4 *rowp = EDGE ? lds + (grp * TILE_H + wv * R + sy0) * PITCH + (col < kNlmEdgePitch - SW ? col : kNlmEdgePitch - SW)
+                                          : lds + (wv * R + sy0) * LW + lane;
                 if (HALF && lower_half) {
                     if (steps == WALK) { for (int sx = 0; sx < SW; ++sx) run(std::bool_constant<HALF>{}, A1, true, rowp + sx, steps); }
                     else { for (int sx = 0; sx < SW; ++sx) run(std::bool_constant<HALF>{}, A1, false, rowp + sx, steps); }
@@ -373,11 +407,11 @@ void nlm_strip_kernel(const NlmArgs a)
         if (!MULTI) break;
     }
 
-    if (wave_active && lane >= NL && lane <= 63 - NR && gx < w) {
+    if (wave_active && col >= NL && col <= (EDGE ? kNlmEdgeLanes - 1 : 63) - NR && gx < w) {
 #pragma unroll
         for (int k = 0; k < R; ++k) {
             const int gy = yb + k;
-            if (gy >= h) break;
+            if (gy >= h) break;     // (EDGE: per lane -- also every row of a group whose tile row does not exist)
             const size_t idx = (size_t)gy * w + gx;
             if (FUSED) {
                 float4 o;
@@ -399,8 +433,9 @@ void nlm_strip_kernel(const NlmArgs a)
 }
 
 template <int SLO, int SHI, int PLO, int PHI, int R, int NW, int FMT, bool FUSED, bool MULTI, bool HALF = false, int TAG = 0>
-static int launch_strip(mid_ctx *ctx, NlmArgs &a, hipStream_t s, unsigned wg_first = 0, unsigned wg_count = ~0u)
+static int launch_strip(mid_ctx *ctx, NlmArgs &a, hipStream_t s, unsigned wg_first = 0, unsigned wg_count = ~0u, int less_cols = 0)
 {
+    // less_cols: tile columns at the right edge that ANOTHER launch covers (1: the packed edge launch of nlm_edge.hip runs beside this one)
     constexpr bool RTS = (SLO == 0 && SHI == 0);
     constexpr int PW = PHI - PLO;
     constexpr int VW = 64 - (PW - 1), TILE_H = NW * R;
@@ -412,7 +447,7 @@ static int launch_strip(mid_ctx *ctx, NlmArgs &a, hipStream_t s, unsigned wg_fir
         return set_error(MID_ERR_UNSUPPORTED, "nlm tile needs %zu B of LDS, device offers %d", lds_bytes, ctx->lds_max);
     // run-time-range instantiations are launched with different tile sizes: raise their limit to the device maximum once
     if (int rc = ensure_lds(ctx, (const void *)kern, RTS ? (size_t)ctx->lds_max : lds_bytes)) return rc;
-    a.tiles_x = (int)cdiv(a.w, VW);
+    a.tiles_x = (int)cdiv(a.w, VW) - less_cols;
     a.tiles_y = (int)cdiv(a.h, TILE_H);
     const unsigned nwg = (unsigned)a.tiles_x * a.tiles_y * (FUSED ? a.count : 1);
     // (a launch may cover a sub-range of the tiles x frames grid: the tail of a small launch goes to the HALF shape)
@@ -440,5 +475,10 @@ int nlm_dispatch_rt4(mid_ctx *ctx, const mid_nlm_params *p, NlmArgs &a, hipStrea
 // own copies of the tuned kernels (TAG = 1) and the HALF shape for the last round.  *handled = false: not a tuned window / not a small launch.
 constexpr unsigned kNlmSmallRounds = 7;
 int nlm_dispatch_small(mid_ctx *ctx, const mid_nlm_params *p, NlmArgs &a, hipStream_t s, int fmt, bool fused, bool *handled);
+// A long k = 0 launch of a tuned window: defined in nlm_edge.hip.  main_launch(ctx, a, s, less_cols) is the caller's launch_strip of the
+// whole shape; it is called once -- with less_cols = 1 beside the packed edge launch where the frame's last tile column packs
+// (nlm_edge_packs), with 0 and nothing beside it otherwise.
+typedef int (*nlm_main_launch)(mid_ctx *ctx, NlmArgs &a, hipStream_t s, int less_cols);
+int nlm_dispatch_edge(mid_ctx *ctx, const mid_nlm_params *p, NlmArgs &a, hipStream_t s, int fmt, bool fused, nlm_main_launch main_launch);
 
 }  // namespace mid

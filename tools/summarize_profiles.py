@@ -109,18 +109,33 @@ else:
 
 # ---- traffic of the dominant kernel (the 8-frame bench launches = the largest grid) ----------
 dom = [k for k in pmc if "nlm_strip_kernel" in k[0]]
+# (the bench launch's own kernel where the collection holds it: since the packed edge launch its grid is no longer the largest
+# of the strip kernels -- the kernel mix's temporal launch covers every tile column)
+dom = [k for k in dom if k[0].endswith("nlm_strip_kernel<-10, 11, -3, 4, 8, 4, 0, true, false, false, 0>") and "FETCH_SIZE" in pmc[k]] or dom
 if dom:
     k = max(dom, key=lambda kk: int(kk[1]))
     d = pmc[k]
+    # (since the packed edge launch, csrc/nlm_edge.hip: a bench launch is the main kernel over 33 of a frame's 34 tile columns + the packed
+    # kernel, TAG = 2, over the last one; the figures below are the sums of both, the packed kernel's share is stated on its own)
+    edge = [kk for kk in pmc if kk[0].endswith(", 2>") and "nlm_strip_kernel<-10, 11, -3, 4, 8, 4, 0, true, false" in kk[0]
+            and "FETCH_SIZE" in pmc[kk] and "WRITE_SIZE" in pmc[kk]]
     if "FETCH_SIZE" in d and "WRITE_SIZE" in d:
         fetch_kb = sum(d["FETCH_SIZE"]) / len(d["FETCH_SIZE"])
         write_kb = sum(d["WRITE_SIZE"]) / len(d["WRITE_SIZE"])
-        t = {"kernel": k[0], "grid": k[1], "FETCH_SIZE_KB_raw": fetch_kb, "WRITE_SIZE_KB": write_kb,
+        tiles_per_frame = 34 * 34
+        packed = {}
+        if edge:
+            e = pmc[max(edge, key=lambda kk: int(kk[1]))]
+            e_fetch, e_write = sum(e["FETCH_SIZE"]) / len(e["FETCH_SIZE"]), sum(e["WRITE_SIZE"]) / len(e["WRITE_SIZE"])
+            packed = {"packed_edge_kernel": {"kernel": edge[0][0], "grid": max(int(kk[1]) for kk in edge), "FETCH_SIZE_KB_raw": e_fetch, "WRITE_SIZE_KB": e_write}}
+            fetch_kb, write_kb = fetch_kb + e_fetch, write_kb + e_write
+            tiles_per_frame = 33 * 34
+        t = {"kernel": k[0], "grid": k[1], "FETCH_SIZE_KB_raw": fetch_kb, "WRITE_SIZE_KB": write_kb, **packed,
              "read_bytes_corrected": fetch_kb * 1024 * 2, "write_bytes": write_kb * 1024,
              "traffic_bytes_per_launch": fetch_kb * 1024 * 2 + write_kb * 1024,
              "correction": "gfx950: FETCH_SIZE counts 64 B per 128-B request for wide coalesced reads -> x2 "
                            "(MI355X_MICROARCH.md, HBM); WRITE_SIZE exact for 16-B/lane streaming stores",
-             "algorithmic_bytes_per_launch": int(k[1]) // 256 // (34 * 34) * 1920 * 1080 * 32,
+             "algorithmic_bytes_per_launch": int(k[1]) // 256 // tiles_per_frame * 1920 * 1080 * 32,
              "date": __import__("time").strftime("%Y-%m-%d", __import__("time").gmtime()),
              **({"kernel_symbol": FP["kernel_symbol"], "kernel_code_sha256": FP["kernel_code_sha256"]} if FP else {}),
              "command": "rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE (one pass each) -- python3 bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-extras"}
