@@ -106,6 +106,12 @@ _SIGNATURES = {
     "mid_sequence_atrous_joint": (ctypes.c_int, [_P, ctypes.POINTER(AtrousParams), ctypes.POINTER(ctypes.c_float), c_void_pp, ctypes.c_int,
                                                  c_void_pp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_pp, ctypes.c_int,
                                                  ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
+    "mid_atrous_joint_temporal": (ctypes.c_int, [_P, ctypes.POINTER(AtrousParams), ctypes.POINTER(ctypes.c_float), c_void_pp, c_void_pp,
+                                                 ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_pp, ctypes.c_int,
+                                                 _P, _P]),
+    "mid_sequence_atrous_joint_temporal": (ctypes.c_int, [_P, ctypes.POINTER(AtrousParams), ctypes.POINTER(ctypes.c_float), c_void_pp,
+                                                          ctypes.c_int, c_void_pp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                          c_void_pp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
     "mid_normalize": (ctypes.c_int, [_P, ctypes.POINTER(NormalizeParams), _P, _P, _P]),
     "mid_unpack_u8": (ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_int, _P, _P]),
     "mid_pack_u8": (ctypes.c_int, [_P, _P, ctypes.c_size_t, _P, _P]),

@@ -487,6 +487,30 @@ class Context:
                                     d_scratch.ptr if d_scratch else None, None), "mid_atrous_joint")
         return self.download(d_out, (h, w, 4), out_dtype)
 
+    def atrous_joint_temporal(self, frames, layers, sigmas, k=2, first=0, count=None, passes=5, color_sigma=0.0, out_dtype=None):
+        """The a-trous filter over the frames t-k..t+k for `count` output frames (mid_atrous_joint_temporal): pass 0 takes its
+        taps from every frame of the window, the centre from frame t; passes 1.. are atrous_joint's on that estimate with frame
+        t's layers.  layers: one list per frame of equally many (1..16) (h, w, 4) guide layers, uint8, float16 or float32 and all
+        of one dtype; sigmas: one sigma per layer; color_sigma: 0 = no colour term; out_dtype: None = float32, uint8 or float16."""
+        frames = _same_frames(frames, "atrous_joint_temporal")
+        n = len(frames)
+        count = n - first if count is None else count
+        h, w = frames[0].shape[:2]
+        n_layers, flat = _flat_layers(layers, n, h, w, "atrous_joint_temporal", _GUIDE_DTYPES)
+        out_dtype = _out_dtype(False, out_dtype)
+        p = AtrousParams(w, h, 0, passes, color_sigma, _guide_fmt(_fmt_of(frames[0]), flat, "atrous_joint_temporal"))
+        d_fr = [self.upload(f) for f in frames]
+        d_l = [self.upload(l) for l in flat]
+        d_out = [self.alloc(w * h * 4 * out_dtype.itemsize) for _ in range(max(count, 0))]
+        nbytes = lib.mid_atrous_scratch_bytes(ctypes.byref(p))
+        d_scratch = self.alloc(nbytes) if nbytes else None
+        _check(lib.mid_atrous_joint_temporal(self.handle, ctypes.byref(p), _layer_sigmas(sigmas, n_layers, "atrous_joint_temporal"),
+                                             (ctypes.c_void_p * n)(*[d.ptr for d in d_fr]),
+                                             (ctypes.c_void_p * max(len(d_l), 1))(*[d.ptr for d in d_l]), n_layers, n, k, first, count,
+                                             (ctypes.c_void_p * max(len(d_out), 1))(*[d.ptr for d in d_out]), _OUT_FMT[out_dtype],
+                                             d_scratch.ptr if d_scratch else None, None), "mid_atrous_joint_temporal")
+        return [self.download(d, (h, w, 4), out_dtype) for d in d_out]
+
     def normalize(self, W):
         """normalize.comp."""
         W = np.ascontiguousarray(W, dtype=np.float32)
@@ -779,6 +803,28 @@ class Context:
         out_dtype = _out_dtype(False, out_dtype)
         return self._sequence_host("sequence_atrous_joint", lambda hin, hout, w, h, fmt, hlayers, n_layers, count: self.sequence_atrous_joint_pinned(
             hin, hout, w, h, fmt, hlayers, n_layers, sigmas, passes, first_pass, color_sigma, first, count, overlap, out_dtype),
+            frames, layers, _GUIDE_DTYPES, first, count, pinned, pinned_out, out_dtype)
+
+    def sequence_atrous_joint_temporal_pinned(self, hin, hout, w, h, fmt, hlayers, n_layers, sigmas, k=2, first=0, count=None, passes=5,
+                                              color_sigma=0.0, overlap=True, out_dtype=None):
+        """mid_sequence_atrous_joint_temporal on host pointers the caller already holds: nothing but the C call.  hin, hlayers,
+        hout as for sequence_bilateral_joint_pinned; sigmas: n_layers sigmas.
+        Returns (wall_ms of the whole call, kernel_ms, copy_ms)."""
+        count = len(hin) - first if count is None else count
+        return self._sequence_call("mid_sequence_atrous_joint_temporal", "mid_sequence_atrous_joint_temporal",
+                                   AtrousParams(w, h, 0, passes, color_sigma, fmt), hin, hout, count,
+                                   f"{count} outputs", overlap, layers=(hlayers, n_layers), window=(k, first, count), out_dtype=(out_dtype,),
+                                   sigmas=(sigmas,))
+
+    def sequence_atrous_joint_temporal(self, frames, layers, sigmas, k=2, first=0, count=None, passes=5, color_sigma=0.0, overlap=True,
+                                       pinned=True, pinned_out=True, out_dtype=None):
+        """Outputs [first, first+count) of an animation through the overlapped pipeline with the a-trous filter over the frames
+        t-k..t+k as its compute stage (mid_sequence_atrous_joint_temporal): output t is ctx.atrous_joint_temporal(frames, layers,
+        sigmas, k, passes=passes, color_sigma=color_sigma) of frame t in out_dtype.  pinned, pinned_out, out_dtype as for
+        sequence_bilateral.  Returns (outputs, (wall_ms, kernel_ms, copy_ms))."""
+        out_dtype = _out_dtype(False, out_dtype)
+        return self._sequence_host("sequence_atrous_joint_temporal", lambda hin, hout, w, h, fmt, hlayers, n_layers, count: self.sequence_atrous_joint_temporal_pinned(
+            hin, hout, w, h, fmt, hlayers, n_layers, sigmas, k, first, count, passes, color_sigma, overlap, out_dtype),
             frames, layers, _GUIDE_DTYPES, first, count, pinned, pinned_out, out_dtype)
 
 

@@ -64,7 +64,7 @@ struct Options {
     bool run_gpu = true, run_cpu = true;
     std::string modes = "all";      // comma list of: bilateral,layers,linear,nlm,multiframe,overlap (all of them: "all"), nlm-layers, joint, nlm-joint, atrous
     bool animation = false;         // new capability: temporal NLM of EVERY frame of the sequence
-    std::string animation_filter = "nlm";   // animation mode: nlm | bilateral | linear | layers (the bilateral of every frame) | nlm-layers | nlm-layers-temporal | bilateral-temporal | layers-temporal | joint | joint-temporal | nlm-joint | nlm-joint-temporal
+    std::string animation_filter = "nlm";   // animation mode: nlm | bilateral | linear | layers (the bilateral of every frame) | nlm-layers | nlm-layers-temporal | bilateral-temporal | layers-temporal | joint | joint-temporal | nlm-joint | nlm-joint-temporal | atrous | atrous-temporal
     int gpus = 1;                   // animation mode: frame blocks over this many devices
     bool share_device = false;      // animation mode: every block on --device (rehearsal of --gpus N on fewer devices)
     bool halo_rccl = false;         // animation mode: blocks resident in HBM, halo frames GPU to GPU over RCCL (mid_nlm_temporal_sharded)
@@ -80,7 +80,7 @@ struct Options {
     } while (0)
 
 // --animation-filter, parsed once: the mid_sequence_* family a value runs, what that family reads, and the words of the value.
-enum SeqFamily { SEQ_NLM, SEQ_BILATERAL, SEQ_NLM_LAYERS, SEQ_NLM_LAYERS_TEMPORAL, SEQ_BILATERAL_TEMPORAL, SEQ_BILATERAL_JOINT, SEQ_NLM_JOINT, SEQ_ATROUS };
+enum SeqFamily { SEQ_NLM, SEQ_BILATERAL, SEQ_NLM_LAYERS, SEQ_NLM_LAYERS_TEMPORAL, SEQ_BILATERAL_TEMPORAL, SEQ_BILATERAL_JOINT, SEQ_NLM_JOINT, SEQ_ATROUS, SEQ_ATROUS_TEMPORAL };
 struct AnimationFilter {
     const char *name;
     SeqFamily family;
@@ -107,6 +107,7 @@ static const AnimationFilter kAnimationFilters[] = {
     {"nlm-joint", SEQ_NLM_JOINT, true, false, false, "nonlinear-nlm-joint-", "joint nonlocal", "joint nonlocal"},
     {"nlm-joint-temporal", SEQ_NLM_JOINT, true, true, false, "nonlinear-nlm-joint-multiframe-", "joint nonlocal", "joint nonlocal, multiframe"},
     {"atrous", SEQ_ATROUS, true, false, false, "nonlinear-atrous-", "a-trous", "a-trous + layers"},
+    {"atrous-temporal", SEQ_ATROUS_TEMPORAL, true, true, false, "nonlinear-atrous-multiframe-", "a-trous", "a-trous + layers, multiframe"},
 };
 static const AnimationFilter *animation_filter(const std::string &name)
 {
@@ -553,7 +554,7 @@ public:
         for (auto &fl : frameLayers) allLayers.insert(allLayers.end(), fl.begin(), fl.end());
         if (nlm_guides) for (const std::string &ln : allLayers) if (is_hdr(ln)) (void)load(ln, true);   // refuses, saying why
         const int lfmt = layer_format(allLayers);
-        const std::vector<float> jointSigma = af.family == SEQ_BILATERAL_JOINT || af.family == SEQ_ATROUS ? layer_sigmas(frameLayers[0])            // (every frame has frame 0's layers)
+        const std::vector<float> jointSigma = af.family == SEQ_BILATERAL_JOINT || af.family == SEQ_ATROUS || af.family == SEQ_ATROUS_TEMPORAL ? layer_sigmas(frameLayers[0])            // (every frame has frame 0's layers)
                                               : af.family == SEQ_NLM_JOINT ? layer_sigmas(frameLayers[0], true) : std::vector<float>();
         std::cout << "\tloading " << n << " frames\n";
         // Frames are decoded STRAIGHT INTO pinned host memory (mid_image_load_pinned) and the results land in pinned
@@ -691,6 +692,10 @@ public:
                 const mid_atrous_params ap{bpp.width, bpp.height, 0, opt.passes, opt.atrous_sigma_color, bpp.format};
                 MID_CHECK(mid_sequence_atrous_joint(c, &ap, jointSigma.data(), frames, nf, lp, L, start, count, outs, out_fmt, 1, t)); break;
             }
+            case SEQ_ATROUS_TEMPORAL: {    // pass 0 over the frames t-k..t+k, the later passes on frame t's estimate
+                const mid_atrous_params ap{bpp.width, bpp.height, 0, opt.passes, opt.atrous_sigma_color, bpp.format};
+                MID_CHECK(mid_sequence_atrous_joint_temporal(c, &ap, jointSigma.data(), frames, nf, lp, L, kk, start, count, outs, out_fmt, 1, t)); break;
+            }
             case SEQ_NLM_JOINT:            // one patch weight from all layers (jointSigma: the h of each layer)
                 MID_CHECK(mid_sequence_nlm_joint(c, &np, jointSigma.data(), frames, nf, lp, L, kk, start, count, outs, out_fmt, 1, t)); break;
             case SEQ_BILATERAL_TEMPORAL:   // plain or with the layers
@@ -821,7 +826,7 @@ public:
         std::string words = af.words;
         if (af.bilateral()) words += " r=" + std::to_string(opt.radius);
         if (use_layers && af.family != SEQ_BILATERAL) words += " + " + std::to_string(L) + " layers";
-        if (af.family == SEQ_ATROUS) words += ", " + std::to_string(opt.passes) + " passes";
+        if (af.family == SEQ_ATROUS || af.family == SEQ_ATROUS_TEMPORAL) words += ", " + std::to_string(opt.passes) + " passes";
         if (af.windowed()) words += (words.empty() ? "k=" : ", k=") + std::to_string(k);
         std::cout << "\t" << n << " frames, " << words
                   << ", " << G << " device(s): " << sec << " sec, "
@@ -956,7 +961,11 @@ static void usage()
         "                            output-animation-nonlinear-nlm-joint-multiframe-*;\n"
         "                            or atrous: the a-trous filter of every frame alone (--passes, --sigma-layers,\n"
         "                            --atrous-sigma-color; the layer rules of joint; it ignores --temporal-k, frame blocks have no\n"
-        "                            halo, not with --halo rccl), outputs output-animation-nonlinear-atrous-*\n"
+        "                            halo, not with --halo rccl), outputs output-animation-nonlinear-atrous-*;\n"
+        "                            or atrous-temporal: the same with pass 0 taking its taps from the frames t-K..t+K, weighed by\n"
+        "                            frame t's layers against the neighbour frame's (K = --temporal-k, default 2; the later passes\n"
+        "                            filter frame t's estimate; the layer rules of atrous, the frame blocks and halo of\n"
+        "                            joint-temporal, not with --halo rccl), outputs output-animation-nonlinear-atrous-multiframe-*\n"
         "  --gpus N                  animation mode: split the sequence into N frame blocks, one per device\n"
         "  --halo host|rccl          animation mode with --gpus N: 'host' (default) streams every block plus its K halo frames from host\n"
         "                            memory through the overlapped pipeline; 'rccl' keeps each block resident in its GPU's HBM and\n"

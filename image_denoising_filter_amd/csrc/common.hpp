@@ -244,6 +244,17 @@ int atrous_joint_out(mid_ctx *ctx, const mid_atrous_params *p, const float *laye
 int atrous_check(const mid_atrous_params *p, const char *who, const float *layer_sigma, bool have_layers, int n_layers);
 size_t atrous_scratch_frames(int n_passes);
 
+// mid_atrous_joint_temporal without its checks (the caller has made them), per output frame one launch of the temporal pass and
+// then atrous_joint_out for passes 1 .. N-1, all on `s`: atrous_temporal.hip; used by the frame pipeline
+// (mid_sequence_atrous_joint_temporal), not exported.  scratch0 / scratch1: the levels, as above, shared by the call's outputs.
+// atrous_temporal_check: what both entry points check before their own tables -- atrous_check, first_pass == 0, n_frames >= 1,
+// k >= 0 and the pointer limit of one launch (nlm_layers_temporal_fits).
+int atrous_temporal_out(mid_ctx *ctx, const mid_atrous_params *p, const float *layer_sigma, const void *const *frames,
+                        const uint32_t *const *layers, int n_layers, int n_frames, int k, int first, int count, void *const *out,
+                        int out_fmt, void *scratch0, void *scratch1, hipStream_t s);
+int atrous_temporal_check(const mid_atrous_params *p, const char *who, const float *layer_sigma, bool have_layers, int n_layers,
+                          int n_frames, int k);
+
 // ROCTx ranges (csrc/markers.cpp): no-ops unless the process already holds a ROCTx (rocprofv3 --marker-trace preloads one).
 bool markers_active();
 void range_push(const char *name);

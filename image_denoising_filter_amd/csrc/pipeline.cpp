@@ -600,6 +600,31 @@ extern "C" int mid_sequence_atrous_joint(mid_ctx *ctx, const mid_atrous_params *
     return run_pipeline(ctx, st, launch, host_frames, n_frames, 0, first, count, host_out, out_format, overlap, timings_ms);
 }
 
+// The a-trous filter over neighbouring frames: mid_sequence_atrous_joint with a window -- mid_sequence_bilateral_joint's schedule
+// and layer ring at k, the launch callable of sequence_bilateral_temporal's window tables, the levels of the call above.
+extern "C" int mid_sequence_atrous_joint_temporal(mid_ctx *ctx, const mid_atrous_params *p, const float *layer_sigma,
+                                                  const void *const *host_frames, int n_frames, const void *const *host_layers, int n_layers,
+                                                  int k, int first, int count, void *const *host_out, int out_format, int overlap,
+                                                  float *timings_ms)
+{
+    Bind b(ctx, nullptr);
+    if (b.rc) return b.rc;
+    const char *who = "sequence_atrous_joint_temporal";
+    if (int rc = refuse_if_recording(ctx->compute, "mid_sequence_atrous_joint_temporal (four streams, host-side waits)")) return rc;
+    if (int rc = atrous_temporal_check(p, who, layer_sigma, host_layers != nullptr, n_layers, n_frames, k)) return rc;
+    if (int rc = check_sequence({who, "n_frames", true, true}, host_frames, n_frames, host_layers, n_layers, k, first, count, host_out, out_format)) return rc;
+    const size_t npix = (size_t)p->width * p->height;
+    const int n_levels = (int)atrous_scratch_frames(p->n_passes);
+    Stage st{who, p->width, p->height, fmt_frames(p->format), npix * fmt_bytes(fmt_guide(p->format)), host_layers, n_layers, true, "atrous %d"};
+    st.level_bytes = npix * 16; st.n_levels = n_levels;
+    auto launch = [&](const void *const *tbl, int n_win, const uint32_t *const *lt, int k, int t0, int bn, void *const *out, int out_fmt, hipStream_t s) {
+        void *const *lv = ctx->pipe.atrous.p.data() + (s == ctx->compute2 ? n_levels : 0);
+        return atrous_temporal_out(ctx, p, layer_sigma, tbl, lt, n_layers, n_win, k, t0, bn, out, out_fmt,
+                                   n_levels >= 1 ? lv[0] : nullptr, n_levels >= 2 ? lv[1] : nullptr, s);
+    };
+    return run_pipeline(ctx, st, launch, host_frames, n_frames, k, first, count, host_out, out_format, overlap, timings_ms);
+}
+
 // Device timeline of the context's last mid_sequence_nlm*, mid_sequence_bilateral or mid_sequence_nlm_layers[_temporal] call, read back from the events the call left in the context's
 // cache (valid until the next pipeline call on this context; no profiler involved, so the call ran at its own pace).
 extern "C" int mid_pipe_last_timeline(mid_ctx *ctx, int cap, float *upload_ms, int *n_uploads, int *first_upload_frame,

@@ -487,7 +487,7 @@ int mid_sequence_nlm_joint(mid_ctx *ctx, const mid_nlm_params *p, const float *l
  * no magenta sentinel here).  All four colour channels are filtered; the colour term reads r, g, b.  Guide texels mean what
  * sections a3 / a4e say: IEEE values, alpha ignored, no clamping, non-finite texels by IEEE arithmetic (a NaN guide texel, or
  * Inf against Inf, poisons the pixels whose taps meet it; a skipped tap poisons nothing).
- * One frame per call; there is no temporal form.  p->first_pass is the ABSOLUTE index of the call's first pass (its step is
+ * One frame per call; the form over neighbouring frames is section a4h.  p->first_pass is the ABSOLUTE index of the call's first pass (its step is
  * 2^first_pass), so a filter can be continued: passes [0, N) in one call are, bit for bit, N calls of one pass each with
  * first_pass = i through RGBA32F buffers.
  * Data path: the levels between passes are RGBA32F frames in `scratch` -- mid_atrous_scratch_bytes(p): 0 bytes for one pass
@@ -568,6 +568,62 @@ int mid_atrous_joint(mid_ctx *ctx, const mid_atrous_params *p, const float *laye
 int mid_sequence_atrous_joint(mid_ctx *ctx, const mid_atrous_params *p, const float *layer_sigma,
                               const void *const *host_frames, int n_frames, const void *const *host_layers, int n_layers,
                               int first, int count, void *const *host_out, int out_format, int overlap, float *timings_ms);
+
+/* ---- a4h: the a-trous filter over neighbouring frames -------------------------------------------
+ * The temporal half of the filter of a4g, taken the way mid_bilateral_joint and mid_nlm_joint take temporal samples: no motion
+ * vectors, the frames' own guide layers reject a neighbour's samples where the scene moved.  Pass 0 (step 1) of output frame t
+ * takes its taps from every frame f of the window lo = max(0, t-k) .. hi = min(n_frames-1, t+k) (clipped at the sequence ends, as
+ * in the other temporal forms); the centre always comes from frame t.  For q = p + o, o = (i, j), |i|, |j| <= 2:
+ *   w(p,f,o)   = K(o) * prod_l exp(-0.5 |G[t][l](p) - G[f][l](q)|^2_rgb / sigma_l^2)
+ *                     * [colorSigma > 0:  exp(-0.5 |C[t](p) - C[f](q)|^2_rgb / colorSigma^2)]
+ *   C_1(p)     = sum_{f = lo..hi} sum_o w C[f](q) / sum_{f,o} w       over the taps whose q lies inside the image
+ * Passes 1 .. n_passes-1 are a4g's, unchanged, on C_1 with frame t's layers: the temporal samples enter once and the later passes
+ * filter the accumulated estimate (a temporal form of the later passes would need the levels of every neighbour).  Everything
+ * else is a4g's: taps outside the image are skipped, all four channels are filtered, guide texels are IEEE values in the guide
+ * format of MID_FMT_WITH_GUIDE, there is no magenta sentinel.
+ * Arithmetic: a4g's chain with the centre from frame t and the tap from frame f -- arg starts at 0 and runs through layer 0's
+ * x, y, z of d = G[t][l](p) sc_l - G[f][l](q) sc_l, then layer 1's, ..., then d = (C[t](p) - C[f](q)) scc_0 for r, g, b; one 2^x
+ * follows, times the exact K(o).  ONE pair of accumulators runs across the whole window: frames in ascending order lo .. hi,
+ * inside a frame j = -2 .. 2, then i = -2 .. 2, acc = fma(C[f](q), w, acc) and accw += w; one IEEE division per channel at the
+ * end.  Every class computes exactly this per pixel, and with a window of one frame it is mid_atrous_joint's chain.
+ * Precision: a4g's, within 1e-5 * max(1, |ref|) of the formula in float64 end to end.
+ * Bit identities:
+ *   - k = 0, or n_frames = 1 with any k, gives the bits of mid_atrous_joint for frame t;
+ *   - neighbours whose every weight is exactly 0 leave the bits of k = 0;
+ *   - N passes in one call are the temporal pass alone (n_passes = 1) into an RGBA32F buffer followed by mid_atrous_joint with
+ *     first_pass = 1, n_passes = N - 1 on that buffer with frame t's layers;
+ *   - the format and zero-layer identities of a4g.
+ * frames / layers: frame-major tables as in mid_bilateral_joint (layers[f * n_layers + l]); the call produces outputs
+ * [first, first + count) into out[0 .. count).  scratch: mid_atrous_scratch_bytes(p) bytes, 16-byte aligned, shared by all
+ * outputs of the call, which run in stream order.  n_passes = 1 stores out_format directly.
+ * Classes of the temporal pass (lanes run along x; no scratch memory; one neighbour's tiles are resident at a time, so the LDS
+ * bytes are those of a4g's step-1 rows; the later passes have a4g's classes):
+ *   layers 1       kernel tiled   pixels 64 x 16  LDS tile 68 x 20  bytes 38080  workgroups per CU 4 by LDS, 2 by registers
+ *   layers 2       kernel tiled   pixels 64 x 16  LDS tile 68 x 20  bytes 54400  workgroups per CU 3 by LDS, 2 by registers
+ *   layers 3       kernel tiled   pixels 64 x 16  LDS tile 68 x 20  bytes 70720  workgroups per CU 2
+ *   layers 4       kernel tiled   pixels 64 x 8   LDS tile 68 x 12  bytes 52224  workgroups per CU 3
+ *   layers 5..16   kernel global  pixels 64 x 4   no LDS
+ * tiled: per neighbour the colour tile and the scaled guide planes are refilled (two barriers), the centres C[t](p) and
+ * G[t][l](p) sc_l and the accumulators stay in registers.  global: one pixel per lane, every neighbour's taps from global memory.
+ * The class follows from n_layers and the device's LDS size alone.
+ * MID_ERR_INVALID before anything is queued, outputs and scratch untouched: every refusal of a4g; p->first_pass != 0 (the
+ * temporal pass is pass 0; a filter is continued with mid_atrous_joint); n_frames < 1; k < 0;
+ * min(2k+1, n_frames) * (n_layers + 1) > MID_NLM_LAYERS_TEMPORAL_MAX_POINTERS; a bad output range; the NULL, alignment and alias
+ * checks of the window [first - k, first + count - 1 + k] as in mid_bilateral_joint (an output that is a frame or layer of the
+ * window, or given twice); scratch overlapping a frame or layer of the window or an output. */
+int mid_atrous_joint_temporal(mid_ctx *ctx, const mid_atrous_params *p, const float *layer_sigma /* n_layers host floats */,
+                              const void *const *frames /* host array of n_frames device ptrs */,
+                              const uint32_t *const *layers /* host array of n_frames * n_layers device ptrs */,
+                              int n_layers, int n_frames, int k, int first, int count,
+                              void *const *out /* host array of `count` device ptrs */, int out_format, void *scratch, void *stream);
+/* mid_sequence_atrous_joint with a window: mid_sequence_bilateral_joint's schedule at k (section a8) with
+ * mid_atrous_joint_temporal as the compute stage -- each host frame and its layers are uploaded once, output t has the bits of
+ * mid_atrous_joint_temporal for frame t.  Same ring, same layer ring (4 / 8 / 16 B per texel), same levels per kernel stream,
+ * same direct-store rule, same refusals (a call inside a recording among them), same timings_ms and timeline export; plus the
+ * refusals above, which leave host_out and timings_ms untouched. */
+int mid_sequence_atrous_joint_temporal(mid_ctx *ctx, const mid_atrous_params *p, const float *layer_sigma,
+                                       const void *const *host_frames, int n_frames, const void *const *host_layers, int n_layers,
+                                       int k, int first, int count, void *const *host_out, int out_format, int overlap, float *timings_ms);
 
 /* ---- a5: normalize ----------------------------------------------------------------------
  * One dispatch of shaders/normalize.comp (RecordCommandsOfExecuteAndTransfer(normKernel=true)):

@@ -28,6 +28,8 @@ int mid::nlm_joint_check(const mid_nlm_params *, const char *, const float *, bo
 int mid::atrous_joint_out(mid_ctx *, const mid_atrous_params *, const float *, const void *, const uint32_t *const *, int, void *, int, void *, void *, hipStream_t) { return MID_ERR_UNSUPPORTED; }   // (atrous.hip)
 int mid::atrous_check(const mid_atrous_params *, const char *, const float *, bool, int) { return MID_ERR_UNSUPPORTED; }   // (atrous.hip)
 size_t mid::atrous_scratch_frames(int) { return 0; }   // (atrous.hip)
+int mid::atrous_temporal_out(mid_ctx *, const mid_atrous_params *, const float *, const void *const *, const uint32_t *const *, int, int, int, int, int, void *const *, int, void *, void *, hipStream_t) { return MID_ERR_UNSUPPORTED; }   // (atrous_temporal.hip)
+int mid::atrous_temporal_check(const mid_atrous_params *, const char *, const float *, bool, int, int, int) { return MID_ERR_UNSUPPORTED; }   // (atrous_temporal.hip)
 int mid::nlm_check_params(const mid_nlm_params *) { return MID_ERR_UNSUPPORTED; }   // (nlm.hip)
 int mid::bilateral_check_params(const mid_bilateral_params *, const char *, bool) { return MID_ERR_UNSUPPORTED; }   // (bilateral.hip)
 
