@@ -7,7 +7,8 @@ oracle run on crops around them, as tests/test_gpu_fullsize.py does at 1080p.  C
 both addressings (the linear one wraps rows, bialteral_linear.comp:58), the fused NLM strip kernel at the benchmark
 window, mid_nlm_accum into the 8.6 GB weight buffer + mid_normalize, and pack/unpack over the whole buffer; layer-guided NLM
 (mid_nlm_layers fused on the strip and the per-pixel kernel, mid_nlm_layers_accum + mid_normalize, mid_nlm_layers_temporal and its
-chain of mid_nlm_layers_pair_accum dispatches) with RGBA8 guides built on the device, against the float64 checkers on crops.
+chain of mid_nlm_layers_pair_accum dispatches) with RGBA8 guides built on the device, against the float64 checkers on crops;
+joint layer-guided NLM (mid_nlm_joint) with two guides on its 32-row tiles, into an output that holds NaN before the call.
 """
 import ctypes
 
@@ -16,6 +17,7 @@ import pytest
 import torch
 
 import image_denoising_filter_amd as mid
+import np_nlm_joint
 import np_nlm_layers
 import np_nlm_layers_temporal
 import oracle
@@ -255,4 +257,30 @@ def test_nlm_layers_temporal_beyond_4_gib(ctx, huge, ts):
         # every pixel was written: the dispatch of frame t with itself has the zero-offset weight 1 (the other frame's guide differs)
         assert float(Wb[..., 4].min()) >= 1.0
     del Wb, out2, outs, gl, second, frames
+    torch.cuda.empty_cache()
+
+
+def test_nlm_joint_strip_kernel_beyond_4_gib(ctx, huge, ts):
+    # two guides with unequal h on the 21x21 / 7x7 window: the class of eight waves of four rows on 32-row tiles, 513 x 283 of them.
+    # The output holds NaN before the call, so a tile the remap of the tile index leaves out shows in the scan of the whole buffer.
+    search, patch, halo, hs = (-10, 11), (-3, 4), 13, (0.5, 0.8)
+    s = ts.cuda_stream
+    gl = [_guide(ts, i, 96 + i) for i in range(2)]
+    assert gl[0].numel() > 2 ** 30
+    with torch.cuda.stream(ts):
+        out = torch.full_like(huge, float("nan"))
+    p = mid.NlmParams(W, H, 0.5, search[0], search[1], patch[0], patch[1], mid.FMT_RGBA32F)
+    assert mid.lib.mid_nlm_joint(ctx.handle, ctypes.byref(p), (ctypes.c_float * 2)(*hs), (ctypes.c_void_p * 1)(huge.data_ptr()),
+                                 (ctypes.c_void_p * 2)(*[g.data_ptr() for g in gl]), 2, 1, 0, 0, 1, (ctypes.c_void_p * 1)(out.data_ptr()),
+                                 mid.FMT_RGBA32F, s) == 0, mid.lib.mid_last_error()
+    torch.cuda.synchronize()
+    worst = 0.0
+    for y0, x0 in WINDOWS:
+        ref = np_nlm_joint.nlm_joint([_crop(huge, y0, x0, halo)], [[_crop_u8(g, y0, x0, halo) for g in gl]], hs, 0, search, patch)[0]
+        e = rel_err(_window(out, y0, x0), ref[halo:halo + SIZE, halo:halo + SIZE])
+        worst = max(worst, e)
+        assert e < TOL, (y0, x0, e)
+    print(f"16400 x 16400, joint NLM, two guides, h = {hs}, 21x21 / 7x7 (32-row strip kernel): worst rel err over the windows {worst:.2e}")
+    assert not torch.isnan(out).any(), "every tile was dealt"
+    del out, gl
     torch.cuda.empty_cache()
