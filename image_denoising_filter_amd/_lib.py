@@ -50,6 +50,18 @@ class AtrousParams(ctypes.Structure):
                 ("colorSigma", ctypes.c_float), ("format", ctypes.c_int32)]
 
 
+class AtrousMomentsParams(ctypes.Structure):
+    """mid_atrous_moments_params (section a4i)."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("format", ctypes.c_int32)]
+
+
+class AtrousVarianceParams(ctypes.Structure):
+    """mid_atrous_variance_params (section a4i)."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("first_pass", ctypes.c_int32), ("n_passes", ctypes.c_int32),
+                ("sigmaLum", ctypes.c_float), ("epsilon", ctypes.c_float), ("format", ctypes.c_int32)]
+
+
 class NormalizeParams(ctypes.Structure):
     _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32)]
 
@@ -112,6 +124,14 @@ _SIGNATURES = {
     "mid_sequence_atrous_joint_temporal": (ctypes.c_int, [_P, ctypes.POINTER(AtrousParams), ctypes.POINTER(ctypes.c_float), c_void_pp,
                                                           ctypes.c_int, c_void_pp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                           c_void_pp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
+    "mid_atrous_moments": (ctypes.c_int, [_P, ctypes.POINTER(AtrousMomentsParams), ctypes.POINTER(ctypes.c_float), c_void_pp, c_void_pp,
+                                          ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P]),
+    "mid_atrous_variance_scratch_bytes": (ctypes.c_size_t, [ctypes.POINTER(AtrousVarianceParams)]),
+    "mid_atrous_variance": (ctypes.c_int, [_P, ctypes.POINTER(AtrousVarianceParams), ctypes.POINTER(ctypes.c_float), _P, _P, c_void_pp,
+                                           ctypes.c_int, _P, ctypes.c_int, _P, _P, _P]),
+    "mid_sequence_atrous_variance": (ctypes.c_int, [_P, ctypes.POINTER(AtrousVarianceParams), ctypes.POINTER(ctypes.c_float), c_void_pp,
+                                                    ctypes.c_int, c_void_pp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                    c_void_pp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
     "mid_normalize": (ctypes.c_int, [_P, ctypes.POINTER(NormalizeParams), _P, _P, _P]),
     "mid_unpack_u8": (ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_int, _P, _P]),
     "mid_pack_u8": (ctypes.c_int, [_P, _P, ctypes.c_size_t, _P, _P]),

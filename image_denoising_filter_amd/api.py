@@ -15,7 +15,7 @@ import weakref
 
 import numpy as np
 
-from ._lib import AtrousParams, BilateralParams, Image, NlmParams, NormalizeParams, c_void_pp, lib
+from ._lib import AtrousMomentsParams, AtrousParams, AtrousVarianceParams, BilateralParams, Image, NlmParams, NormalizeParams, c_void_pp, lib
 
 FMT_RGBA32F, FMT_RGBA8, FMT_RGBA16F = 0, 1, 2
 
@@ -511,6 +511,51 @@ class Context:
                                              d_scratch.ptr if d_scratch else None, None), "mid_atrous_joint_temporal")
         return [self.download(d, (h, w, 4), out_dtype) for d in d_out]
 
+    def atrous_moments(self, frames, layers, sigmas, k=0, t=0):
+        """The luminance variance estimate of output frame t over the frames t-k..t+k (mid_atrous_moments): a 7x7 neighbourhood in
+        every frame of the window, every tap weighed by all guide layers at once.  layers: one list per frame of equally many
+        (1..16) (h, w, 4) guide layers, uint8, float16 or float32 and all of one dtype; sigmas: one sigma per layer.  Returns the
+        float32 plane (h, w)."""
+        frames = _same_frames(frames, "atrous_moments")
+        n = len(frames)
+        h, w = frames[0].shape[:2]
+        n_layers, flat = _flat_layers(layers, n, h, w, "atrous_moments", _GUIDE_DTYPES)
+        p = AtrousMomentsParams(w, h, _guide_fmt(_fmt_of(frames[0]), flat, "atrous_moments"))
+        d_fr = [self.upload(f) for f in frames]
+        d_l = [self.upload(l) for l in flat]
+        d_var = self.alloc(w * h * 4)
+        _check(lib.mid_atrous_moments(self.handle, ctypes.byref(p), _layer_sigmas(sigmas, n_layers, "atrous_moments"),
+                                      (ctypes.c_void_p * n)(*[d.ptr for d in d_fr]),
+                                      (ctypes.c_void_p * max(len(d_l), 1))(*[d.ptr for d in d_l]), n_layers, n, k, t, d_var.ptr, None),
+               "mid_atrous_moments")
+        return self.download(d_var, (h, w), np.float32)
+
+    def atrous_variance(self, frame, variance, layers, sigmas, passes=5, first_pass=0, sigma_lum=4.0, epsilon=1e-3, out_dtype=None,
+                        return_variance=False):
+        """The variance-guided a-trous filter of one frame (mid_atrous_variance): atrous_joint's passes with a luminance term whose
+        width follows the per-pixel `variance` (a float32 (h, w) plane, atrous_moments' output or a renderer's own), which is
+        filtered along with the colour.  sigma_lum: 0 = no luminance term.  return_variance: also return the variance plane of
+        the last pass, as (frame, variance)."""
+        (frame,) = _same_frames([frame], "atrous_variance")
+        h, w = frame.shape[:2]
+        variance = np.ascontiguousarray(variance, dtype=np.float32)
+        if variance.shape != (h, w):
+            raise ValueError(f"atrous_variance: the variance plane must be {(h, w)}, got {variance.shape}")
+        n_layers, flat = _flat_layers([layers], 1, h, w, "atrous_variance", _GUIDE_DTYPES)
+        out_dtype = _out_dtype(False, out_dtype)
+        p = AtrousVarianceParams(w, h, first_pass, passes, sigma_lum, epsilon, _guide_fmt(_fmt_of(frame), flat, "atrous_variance"))
+        d_in, d_vin = self.upload(frame), self.upload(variance)
+        d_l = [self.upload(l) for l in flat]
+        d_out = self.alloc(w * h * 4 * out_dtype.itemsize)
+        d_vout = self.alloc(w * h * 4) if return_variance else None
+        nbytes = lib.mid_atrous_variance_scratch_bytes(ctypes.byref(p))
+        d_scratch = self.alloc(nbytes) if nbytes else None
+        _check(lib.mid_atrous_variance(self.handle, ctypes.byref(p), _layer_sigmas(sigmas, n_layers, "atrous_variance"), d_in.ptr, d_vin.ptr,
+                                       (ctypes.c_void_p * max(len(d_l), 1))(*[d.ptr for d in d_l]), n_layers, d_out.ptr, _OUT_FMT[out_dtype],
+                                       d_vout.ptr if d_vout else None, d_scratch.ptr if d_scratch else None, None), "mid_atrous_variance")
+        out = self.download(d_out, (h, w, 4), out_dtype)
+        return (out, self.download(d_vout, (h, w), np.float32)) if return_variance else out
+
     def normalize(self, W):
         """normalize.comp."""
         W = np.ascontiguousarray(W, dtype=np.float32)
@@ -825,6 +870,28 @@ class Context:
         out_dtype = _out_dtype(False, out_dtype)
         return self._sequence_host("sequence_atrous_joint_temporal", lambda hin, hout, w, h, fmt, hlayers, n_layers, count: self.sequence_atrous_joint_temporal_pinned(
             hin, hout, w, h, fmt, hlayers, n_layers, sigmas, k, first, count, passes, color_sigma, overlap, out_dtype),
+            frames, layers, _GUIDE_DTYPES, first, count, pinned, pinned_out, out_dtype)
+
+    def sequence_atrous_variance_pinned(self, hin, hout, w, h, fmt, hlayers, n_layers, sigmas, k=2, first=0, count=None, passes=5,
+                                        sigma_lum=4.0, epsilon=1e-3, overlap=True, out_dtype=None):
+        """mid_sequence_atrous_variance on host pointers the caller already holds: nothing but the C call.  hin, hlayers, hout as
+        for sequence_bilateral_joint_pinned; sigmas: n_layers sigmas; k: the window of the moments.
+        Returns (wall_ms of the whole call, kernel_ms, copy_ms)."""
+        count = len(hin) - first if count is None else count
+        return self._sequence_call("mid_sequence_atrous_variance", "mid_sequence_atrous_variance",
+                                   AtrousVarianceParams(w, h, 0, passes, sigma_lum, epsilon, fmt), hin, hout, count,
+                                   f"{count} outputs", overlap, layers=(hlayers, n_layers), window=(k, first, count), out_dtype=(out_dtype,),
+                                   sigmas=(sigmas,))
+
+    def sequence_atrous_variance(self, frames, layers, sigmas, k=2, first=0, count=None, passes=5, sigma_lum=4.0, epsilon=1e-3,
+                                 overlap=True, pinned=True, pinned_out=True, out_dtype=None):
+        """Outputs [first, first+count) of an animation through the overlapped pipeline with the variance-guided a-trous filter
+        as its compute stage (mid_sequence_atrous_variance): output t is ctx.atrous_variance(frames[t], ctx.atrous_moments(frames,
+        layers, sigmas, k, t), layers[t], sigmas, passes, 0, sigma_lum, epsilon) in out_dtype.  pinned, pinned_out, out_dtype as
+        for sequence_bilateral.  Returns (outputs, (wall_ms, kernel_ms, copy_ms))."""
+        out_dtype = _out_dtype(False, out_dtype)
+        return self._sequence_host("sequence_atrous_variance", lambda hin, hout, w, h, fmt, hlayers, n_layers, count: self.sequence_atrous_variance_pinned(
+            hin, hout, w, h, fmt, hlayers, n_layers, sigmas, k, first, count, passes, sigma_lum, epsilon, overlap, out_dtype),
             frames, layers, _GUIDE_DTYPES, first, count, pinned, pinned_out, out_dtype)
 
 

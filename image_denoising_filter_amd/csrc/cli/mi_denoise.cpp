@@ -55,6 +55,8 @@ struct Options {
     std::vector<float> h_layers;    // the joint NLM modes: one h per layer in discovery order (empty: nlm_h for all)
     int passes = 5;                 // the a-trous modes: passes of the 5x5 kernel, pass i at step 2^i (1..8)
     float atrous_sigma_color = 0.f; // the a-trous modes: sigma of the colour term at pass 0, halved every pass (0: off)
+    float atrous_sigma_lum = 4.f;   // atrous-variance: sigma of the luminance term in standard deviations of the pixel (SVGF's 4; 0: off)
+    float atrous_epsilon = 1e-3f;   // atrous-variance: what is added to sigma_lum * sqrt(variance) (> 0)
     int search_lo = -7, search_hi = 7, patch_lo = -3, patch_hi = 3;   // shaders/nonlocal.comp:5-6, half-open
     int temporal_k = -1;            // <0: the reference's frame list; >=0: window t-k..t+k of the sorted sequence
     int cpu_radius = 10;            // windowSize, src/main.cpp:1819
@@ -62,9 +64,9 @@ struct Options {
     bool cpu_blue_bug = true;       // pow(texColor.b - texColor.b, 2), src/main.cpp:1850
     std::vector<int> cpu_threads = {1, 8};     // src/main.cpp:1979,1984
     bool run_gpu = true, run_cpu = true;
-    std::string modes = "all";      // comma list of: bilateral,layers,linear,nlm,multiframe,overlap (all of them: "all"), nlm-layers, joint, nlm-joint, atrous
+    std::string modes = "all";      // comma list of: bilateral,layers,linear,nlm,multiframe,overlap (all of them: "all"), nlm-layers, joint, nlm-joint, atrous, atrous-variance
     bool animation = false;         // new capability: temporal NLM of EVERY frame of the sequence
-    std::string animation_filter = "nlm";   // animation mode: nlm | bilateral | linear | layers (the bilateral of every frame) | nlm-layers | nlm-layers-temporal | bilateral-temporal | layers-temporal | joint | joint-temporal | nlm-joint | nlm-joint-temporal | atrous | atrous-temporal
+    std::string animation_filter = "nlm";   // animation mode: nlm | bilateral | linear | layers (the bilateral of every frame) | nlm-layers | nlm-layers-temporal | bilateral-temporal | layers-temporal | joint | joint-temporal | nlm-joint | nlm-joint-temporal | atrous | atrous-temporal | atrous-variance
     int gpus = 1;                   // animation mode: frame blocks over this many devices
     bool share_device = false;      // animation mode: every block on --device (rehearsal of --gpus N on fewer devices)
     bool halo_rccl = false;         // animation mode: blocks resident in HBM, halo frames GPU to GPU over RCCL (mid_nlm_temporal_sharded)
@@ -80,7 +82,7 @@ struct Options {
     } while (0)
 
 // --animation-filter, parsed once: the mid_sequence_* family a value runs, what that family reads, and the words of the value.
-enum SeqFamily { SEQ_NLM, SEQ_BILATERAL, SEQ_NLM_LAYERS, SEQ_NLM_LAYERS_TEMPORAL, SEQ_BILATERAL_TEMPORAL, SEQ_BILATERAL_JOINT, SEQ_NLM_JOINT, SEQ_ATROUS, SEQ_ATROUS_TEMPORAL };
+enum SeqFamily { SEQ_NLM, SEQ_BILATERAL, SEQ_NLM_LAYERS, SEQ_NLM_LAYERS_TEMPORAL, SEQ_BILATERAL_TEMPORAL, SEQ_BILATERAL_JOINT, SEQ_NLM_JOINT, SEQ_ATROUS, SEQ_ATROUS_TEMPORAL, SEQ_ATROUS_VARIANCE };
 struct AnimationFilter {
     const char *name;
     SeqFamily family;
@@ -108,6 +110,7 @@ static const AnimationFilter kAnimationFilters[] = {
     {"nlm-joint-temporal", SEQ_NLM_JOINT, true, true, false, "nonlinear-nlm-joint-multiframe-", "joint nonlocal", "joint nonlocal, multiframe"},
     {"atrous", SEQ_ATROUS, true, false, false, "nonlinear-atrous-", "a-trous", "a-trous + layers"},
     {"atrous-temporal", SEQ_ATROUS_TEMPORAL, true, true, false, "nonlinear-atrous-multiframe-", "a-trous", "a-trous + layers, multiframe"},
+    {"atrous-variance", SEQ_ATROUS_VARIANCE, true, true, false, "nonlinear-atrous-variance-", "variance-guided a-trous", "a-trous + layers, variance-guided"},
 };
 static const AnimationFilter *animation_filter(const std::string &name)
 {
@@ -309,8 +312,9 @@ public:
     // RunOnGPU, src/main.cpp:1307-1730
     // joint (with useLayers): the joint bilateral (mid_bilateral_joint) or, with nlmFilter, joint layer-guided NLM (mid_nlm_joint): one weight from
     // all layers instead of the sum of one filter per layer
-    // atrous (with useLayers and joint): the edge-avoiding a-trous filter (mid_atrous_joint) with the joint mode's layers and sigmas
-    void RunOnGPU(bool nlmFilter, bool nonlinear, bool multiframe, bool execAndCopyOverlap, bool useLayers, bool joint = false, bool atrous = false)
+    // atrous (with useLayers and joint): 1 = the edge-avoiding a-trous filter (mid_atrous_joint) with the joint mode's layers and sigmas,
+    // 2 = its variance-guided form (mid_atrous_moments of the image alone, then mid_atrous_variance)
+    void RunOnGPU(bool nlmFilter, bool nonlinear, bool multiframe, bool execAndCopyOverlap, bool useLayers, bool joint = false, int atrous = 0)
     {
         const bool linear = !nonlinear;                                              // :1311
         TraceRange mode_range(std::string("RunOnGPU ") + (linear ? "linear" : "nonlinear") + (nlmFilter ? " nlm" : " bialteral") +
@@ -411,7 +415,7 @@ public:
                 if (joint) {
                     if (layerNames.empty() || layerNames.size() > 16)
                         throw std::runtime_error(opt.image + ": " + std::to_string(layerNames.size()) + " layer file(s) found, --modes " +
-                                                 (atrous ? "atrous" : nlmFilter ? "nlm-joint" : "joint") + " needs 1..16");
+                                                 (atrous == 2 ? "atrous-variance" : atrous ? "atrous" : nlmFilter ? "nlm-joint" : "joint") + " needs 1..16");
                     jointSigma = layer_sigmas(layerNames, nlmFilter);
                 }
                 for_each_file(0, (int)layerNames.size(), [&](int i) {
@@ -442,6 +446,23 @@ public:
                     timed(m_execMs, [&] {
                         MID_CHECK(mid_nlm_layers(ctx, &p, dIn, (const uint32_t *const *)dLayers.data(), (int)dLayers.size(), (mid_pixel *)dOut, nullptr));
                     });
+                } else if (atrous == 2) {                                                       // the variance of the luminance, then the passes it guides
+                    const int fw = lfmt == MID_FMT_RGBA8 ? fmt : MID_FMT_WITH_GUIDE(fmt, lfmt);
+                    const mid_atrous_moments_params mp{w, h, fw};
+                    const mid_atrous_variance_params p{w, h, 0, opt.passes, opt.atrous_sigma_lum, opt.atrous_epsilon, fw};
+                    void *levels = nullptr, *variance = nullptr;
+                    MID_CHECK(mid_alloc(ctx, npix * sizeof(float), &variance));
+                    if (mid_atrous_variance_scratch_bytes(&p)) MID_CHECK(mid_alloc(ctx, mid_atrous_variance_scratch_bytes(&p), &levels));
+                    const void *fr[1] = {dIn};
+                    timed(m_execMs, [&] {
+                        MID_CHECK(mid_atrous_moments(ctx, &mp, jointSigma.data(), fr, (const uint32_t *const *)dLayers.data(), (int)dLayers.size(), 1, 0, 0,
+                                                     (float *)variance, nullptr));
+                        MID_CHECK(mid_atrous_variance(ctx, &p, jointSigma.data(), dIn, (const float *)variance, (const uint32_t *const *)dLayers.data(),
+                                                      (int)dLayers.size(), dOut, MID_FMT_RGBA32F, nullptr, levels, nullptr));
+                    });
+                    MID_CHECK(mid_stream_sync(ctx, nullptr));
+                    if (levels) mid_free(ctx, levels);
+                    mid_free(ctx, variance);
                 } else if (atrous) {                                                            // N passes of the 5x5 kernel with holes (mid_atrous_joint)
                     mid_atrous_params p{w, h, 0, opt.passes, opt.atrous_sigma_color, lfmt == MID_FMT_RGBA8 ? fmt : MID_FMT_WITH_GUIDE(fmt, lfmt)};
                     void *levels = nullptr;
@@ -487,7 +508,7 @@ public:
         outputFileName += multiframe ? "-multiframe" : "";
         outputFileName += execAndCopyOverlap ? "-overlap" : "";
         outputFileName += joint ? "-joint" : useLayers ? "-layers" : "";
-        if (atrous) outputFileName = "output-nonlinear-atrous";
+        if (atrous) outputFileName = atrous == 2 ? "output-nonlinear-atrous-variance" : "output-nonlinear-atrous";
         if (half) {   // --half: the fp32 result rounded to RGBA16F on the device (mid_pack_f16), written as HALF EXR
             std::vector<uint16_t> px(npix * 4);
             void *dF = nullptr, *dH = nullptr;
@@ -554,7 +575,7 @@ public:
         for (auto &fl : frameLayers) allLayers.insert(allLayers.end(), fl.begin(), fl.end());
         if (nlm_guides) for (const std::string &ln : allLayers) if (is_hdr(ln)) (void)load(ln, true);   // refuses, saying why
         const int lfmt = layer_format(allLayers);
-        const std::vector<float> jointSigma = af.family == SEQ_BILATERAL_JOINT || af.family == SEQ_ATROUS || af.family == SEQ_ATROUS_TEMPORAL ? layer_sigmas(frameLayers[0])            // (every frame has frame 0's layers)
+        const std::vector<float> jointSigma = af.family == SEQ_BILATERAL_JOINT || af.family == SEQ_ATROUS || af.family == SEQ_ATROUS_TEMPORAL || af.family == SEQ_ATROUS_VARIANCE ? layer_sigmas(frameLayers[0])            // (every frame has frame 0's layers)
                                               : af.family == SEQ_NLM_JOINT ? layer_sigmas(frameLayers[0], true) : std::vector<float>();
         std::cout << "\tloading " << n << " frames\n";
         // Frames are decoded STRAIGHT INTO pinned host memory (mid_image_load_pinned) and the results land in pinned
@@ -696,6 +717,10 @@ public:
                 const mid_atrous_params ap{bpp.width, bpp.height, 0, opt.passes, opt.atrous_sigma_color, bpp.format};
                 MID_CHECK(mid_sequence_atrous_joint_temporal(c, &ap, jointSigma.data(), frames, nf, lp, L, kk, start, count, outs, out_fmt, 1, t)); break;
             }
+            case SEQ_ATROUS_VARIANCE: {    // the moments over the frames t-k..t+k, then the variance-guided passes on frame t
+                const mid_atrous_variance_params vp{bpp.width, bpp.height, 0, opt.passes, opt.atrous_sigma_lum, opt.atrous_epsilon, bpp.format};
+                MID_CHECK(mid_sequence_atrous_variance(c, &vp, jointSigma.data(), frames, nf, lp, L, kk, start, count, outs, out_fmt, 1, t)); break;
+            }
             case SEQ_NLM_JOINT:            // one patch weight from all layers (jointSigma: the h of each layer)
                 MID_CHECK(mid_sequence_nlm_joint(c, &np, jointSigma.data(), frames, nf, lp, L, kk, start, count, outs, out_fmt, 1, t)); break;
             case SEQ_BILATERAL_TEMPORAL:   // plain or with the layers
@@ -826,7 +851,7 @@ public:
         std::string words = af.words;
         if (af.bilateral()) words += " r=" + std::to_string(opt.radius);
         if (use_layers && af.family != SEQ_BILATERAL) words += " + " + std::to_string(L) + " layers";
-        if (af.family == SEQ_ATROUS || af.family == SEQ_ATROUS_TEMPORAL) words += ", " + std::to_string(opt.passes) + " passes";
+        if (af.family == SEQ_ATROUS || af.family == SEQ_ATROUS_TEMPORAL || af.family == SEQ_ATROUS_VARIANCE) words += ", " + std::to_string(opt.passes) + " passes";
         if (af.windowed()) words += (words.empty() ? "k=" : ", k=") + std::to_string(k);
         std::cout << "\t" << n << " frames, " << words
                   << ", " << G << " device(s): " << sec << " sec, "
@@ -911,7 +936,12 @@ static void usage()
         "                            kernel, pass i sampling with holes at step 2^i (five passes reach +-62 pixels), every tap weighed\n"
         "                            by all of the image's layers at once as in joint (--sigma-layers, else --sigma-c for all; the\n"
         "                            layer rules of joint, .png or .exr) and, with --atrous-sigma-color, by the colour itself,\n"
-        "                            output output-nonlinear-atrous.{png,exr}.\n"
+        "                            output output-nonlinear-atrous.{png,exr};\n"
+        "                            and atrous-variance (not part of all): the same passes guided by the per-pixel variance of the\n"
+        "                            luminance -- estimated from a 7x7 neighbourhood weighed by the layers, it sets the width of a\n"
+        "                            luminance term per pixel (wide where the image is noisy, narrow where it has converged) and is\n"
+        "                            filtered along with the colour (--passes, --sigma-layers, --atrous-sigma-lum, --atrous-epsilon;\n"
+        "                            the layer rules of atrous), output output-nonlinear-atrous-variance.{png,exr}.\n"
         "                            Layer files: .png (RGBA8) -- or, for the bilateral modes only (layers and joint here, layers,\n"
         "                            layers-temporal, joint and joint-temporal under --animation-filter), .exr: normals, depth, HDR albedo as rendered, read as\n"
         "                            RGBA32F, or as RGBA16F with --half; all layers of a run must have one format; nlm-layers and\n"
@@ -930,6 +960,10 @@ static void usage()
         "  --passes N                the a-trous modes: passes of the 5x5 kernel, 1..8 (default 5; pass i has step 2^i)\n"
         "  --atrous-sigma-color X    the a-trous modes: sigma of the colour term at pass 0, halved with every pass (default 0: no\n"
         "                            colour term, the layers alone stop the filter at edges)\n"
+        "  --atrous-sigma-lum X      atrous-variance: the luminance term lets through differences of about X standard deviations of\n"
+        "                            the pixel's luminance (default 4; 0: no luminance term)\n"
+        "  --atrous-epsilon X        atrous-variance: added to X * sqrt(variance), so that a converged pixel (variance 0) still averages\n"
+        "                            texels that differ by rounding alone (default 1e-3, for luminances of order 1; > 0)\n"
         "  --search LO,HI --patch LO,HI   half-open NLM ranges (default -7,7 and -3,3; 21x21/7x7 is -10,11 and -3,4)\n"
         "  --temporal-k K            multiframe: frames t-K..t+K of the sorted sequence instead of the reference's list\n"
         "  --animation               denoise EVERY sibling frame with temporal NLM (window +-K, default 2) instead of the mode list\n"
@@ -965,7 +999,11 @@ static void usage()
         "                            or atrous-temporal: the same with pass 0 taking its taps from the frames t-K..t+K, weighed by\n"
         "                            frame t's layers against the neighbour frame's (K = --temporal-k, default 2; the later passes\n"
         "                            filter frame t's estimate; the layer rules of atrous, the frame blocks and halo of\n"
-        "                            joint-temporal, not with --halo rccl), outputs output-animation-nonlinear-atrous-multiframe-*\n"
+        "                            joint-temporal, not with --halo rccl), outputs output-animation-nonlinear-atrous-multiframe-*;\n"
+        "                            or atrous-variance: the variance-guided a-trous filter of every frame, its variance estimated\n"
+        "                            over the frames t-K..t+K (K = --temporal-k, default 2; --passes, --sigma-layers,\n"
+        "                            --atrous-sigma-lum, --atrous-epsilon; the layer rules of atrous, the frame blocks and halo of\n"
+        "                            joint-temporal, not with --halo rccl), outputs output-animation-nonlinear-atrous-variance-*\n"
         "  --gpus N                  animation mode: split the sequence into N frame blocks, one per device\n"
         "  --halo host|rccl          animation mode with --gpus N: 'host' (default) streams every block plus its K halo frames from host\n"
         "                            memory through the overlapped pipeline; 'rccl' keeps each block resident in its GPU's HBM and\n"
@@ -1026,6 +1064,8 @@ int main(int argc, char **argv)
             if (opt.passes < 1 || opt.passes > 8) { std::cerr << "--passes " << opt.passes << " is outside 1..8\n"; return EXIT_FAILURE; }
         }
         else if (a == "--atrous-sigma-color") opt.atrous_sigma_color = (float)atof(next());
+        else if (a == "--atrous-sigma-lum") opt.atrous_sigma_lum = (float)atof(next());
+        else if (a == "--atrous-epsilon") opt.atrous_epsilon = (float)atof(next());
         else if (a == "--search") { if (!pair_arg(next(), opt.search_lo, opt.search_hi)) { usage(); return EXIT_FAILURE; } }
         else if (a == "--patch") { if (!pair_arg(next(), opt.patch_lo, opt.patch_hi)) { usage(); return EXIT_FAILURE; } }
         else if (a == "--temporal-k") opt.temporal_k = atoi(next());
@@ -1084,7 +1124,8 @@ int main(int argc, char **argv)
             if (listed("nlm-layers")) { std::cout << "######\nRunning on GPU (nonlocal + layers)\n######\n"; app.RunOnGPU(true, true, false, false, true); print_time(); }
             if (listed("joint")) { std::cout << "######\nRunning on GPU (joint bialteral)\n######\n"; app.RunOnGPU(false, true, false, false, true, true); print_time(); }
             if (listed("nlm-joint")) { std::cout << "######\nRunning on GPU (joint nonlocal)\n######\n"; app.RunOnGPU(true, true, false, false, true, true); print_time(); }
-            if (listed("atrous")) { std::cout << "######\nRunning on GPU (a-trous + layers)\n######\n"; app.RunOnGPU(false, true, false, false, true, true, true); print_time(); }
+            if (listed("atrous")) { std::cout << "######\nRunning on GPU (a-trous + layers)\n######\n"; app.RunOnGPU(false, true, false, false, true, true, 1); print_time(); }
+            if (listed("atrous-variance")) { std::cout << "######\nRunning on GPU (a-trous + layers, variance-guided)\n######\n"; app.RunOnGPU(false, true, false, false, true, true, 2); print_time(); }
         }
         if (opt.run_cpu) {
             for (int threads : opt.cpu_threads) {

@@ -21,6 +21,7 @@ struct mid_pipe_cache {
     mid_pipe_set ring, out;             // mid_sequence_nlm* / mid_sequence_bilateral: uploaded frames (2k + 4), output slots (4)
     mid_pipe_set layers;                // mid_sequence_bilateral with guide layers: n_layers per ring slot
     mid_pipe_set atrous;                // mid_sequence_atrous_joint: the RGBA32F levels between passes, two per kernel stream
+                                        // (mid_sequence_atrous_variance: one block per kernel stream -- colour levels, variance levels, V_0)
     mid_pipe_set target, slots, weights, result;   // mid_nlm_multiframe
     std::vector<hipEvent_t> ev;
     mid_pipe_last last;                 // mid_pipe_last_timeline reads the events of the last call back
@@ -254,6 +255,19 @@ int atrous_temporal_out(mid_ctx *ctx, const mid_atrous_params *p, const float *l
                         int out_fmt, void *scratch0, void *scratch1, hipStream_t s);
 int atrous_temporal_check(const mid_atrous_params *p, const char *who, const float *layer_sigma, bool have_layers, int n_layers,
                           int n_frames, int k);
+
+// mid_atrous_moments / mid_atrous_variance without their checks (the caller has made them), one launch per output / per pass on
+// `s`: atrous_variance.hip; used by the frame pipeline (mid_sequence_atrous_variance), not exported.  level / vlevel: the RGBA32F
+// colour levels and the float variance levels between passes (the first pair needed from two passes on, the second from three);
+// var_out == nullptr: the last pass stores no variance.  The checks: what the entry points check before their own tables.
+int atrous_moments_out(mid_ctx *ctx, const mid_atrous_moments_params *p, const float *layer_sigma, const void *const *frames,
+                       const uint32_t *const *layers, int n_layers, int n_frames, int k, int t, float *var_out, hipStream_t s);
+int atrous_variance_out(mid_ctx *ctx, const mid_atrous_variance_params *p, const float *layer_sigma, const void *in, const float *var_in,
+                        const uint32_t *const *layers, int n_layers, void *out, int out_fmt, float *var_out, void *const level[2],
+                        float *const vlevel[2], hipStream_t s);
+int atrous_moments_check(const mid_atrous_moments_params *p, const char *who, const float *layer_sigma, bool have_layers, int n_layers,
+                         int n_frames, int k);
+int atrous_variance_check(const mid_atrous_variance_params *p, const char *who, const float *layer_sigma, bool have_layers, int n_layers);
 
 // ROCTx ranges (csrc/markers.cpp): no-ops unless the process already holds a ROCTx (rocprofv3 --marker-trace preloads one).
 bool markers_active();

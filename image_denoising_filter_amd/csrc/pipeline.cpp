@@ -625,6 +625,46 @@ extern "C" int mid_sequence_atrous_joint_temporal(mid_ctx *ctx, const mid_atrous
     return run_pipeline(ctx, st, launch, host_frames, n_frames, k, first, count, host_out, out_format, overlap, timings_ms);
 }
 
+// The variance-guided a-trous filter of an animation: mid_sequence_atrous_joint_temporal's schedule and layer ring at k, where k is
+// the window of the MOMENTS.  Per output: the moments over the window into a V_0 plane, then the passes on frame t alone with frame
+// t's layers.  Everything between the kernels lives in ONE block of the context's cache per kernel stream -- the colour levels,
+// the variance levels (mid_atrous_variance's scratch layout) and, behind them, the V_0 plane.
+extern "C" int mid_sequence_atrous_variance(mid_ctx *ctx, const mid_atrous_variance_params *p, const float *layer_sigma,
+                                            const void *const *host_frames, int n_frames, const void *const *host_layers, int n_layers,
+                                            int k, int first, int count, void *const *host_out, int out_format, int overlap,
+                                            float *timings_ms)
+{
+    Bind b(ctx, nullptr);
+    if (b.rc) return b.rc;
+    const char *who = "sequence_atrous_variance";
+    if (int rc = refuse_if_recording(ctx->compute, "mid_sequence_atrous_variance (four streams, host-side waits)")) return rc;
+    if (int rc = atrous_variance_check(p, who, layer_sigma, host_layers != nullptr, n_layers)) return rc;
+    MID_REQUIRE(p->first_pass == 0, "%s: first_pass %d: the moments estimate the variance of the unfiltered frame (continue a filter with mid_atrous_variance)", who, p->first_pass);
+    const mid_atrous_moments_params mp{p->width, p->height, p->format};
+    if (int rc = atrous_moments_check(&mp, who, layer_sigma, host_layers != nullptr, n_layers, n_frames, k)) return rc;
+    if (int rc = check_sequence({who, "n_frames", true, true}, host_frames, n_frames, host_layers, n_layers, k, first, count, host_out, out_format)) return rc;
+    const size_t npix = (size_t)p->width * p->height;
+    const size_t sets = atrous_scratch_frames(p->n_passes);
+    const size_t v0_at = (sets * npix * (16 + 4) + 15) & ~(size_t)15;
+    Stage st{who, p->width, p->height, fmt_frames(p->format), npix * fmt_bytes(fmt_guide(p->format)), host_layers, n_layers, true, "atrous variance %d"};
+    st.level_bytes = v0_at + npix * 4; st.n_levels = 1;
+    auto launch = [&](const void *const *tbl, int n_win, const uint32_t *const *lt, int k, int t0, int bn, void *const *out, int out_fmt, hipStream_t s) {
+        char *blk = (char *)ctx->pipe.atrous.p[s == ctx->compute2 ? 1 : 0];
+        void *level[2] = {sets >= 1 ? blk : nullptr, sets >= 2 ? blk + npix * 16 : nullptr};
+        char *vb = blk + sets * npix * 16;
+        float *vlevel[2] = {sets >= 1 ? (float *)vb : nullptr, sets >= 2 ? (float *)(vb + npix * 4) : nullptr};
+        float *v0 = (float *)(blk + v0_at);
+        for (int i = 0; i < bn; ++i) {
+            const int t = t0 + i;
+            if (int rc = atrous_moments_out(ctx, &mp, layer_sigma, tbl, lt, n_layers, n_win, k, t, v0, s)) return rc;
+            if (int rc = atrous_variance_out(ctx, p, layer_sigma, tbl[t], v0, lt + (size_t)t * n_layers, n_layers, out[i], out_fmt, nullptr,
+                                             level, vlevel, s)) return rc;
+        }
+        return (int)MID_OK;
+    };
+    return run_pipeline(ctx, st, launch, host_frames, n_frames, k, first, count, host_out, out_format, overlap, timings_ms);
+}
+
 // Device timeline of the context's last mid_sequence_nlm*, mid_sequence_bilateral or mid_sequence_nlm_layers[_temporal] call, read back from the events the call left in the context's
 // cache (valid until the next pipeline call on this context; no profiler involved, so the call ran at its own pace).
 extern "C" int mid_pipe_last_timeline(mid_ctx *ctx, int cap, float *upload_ms, int *n_uploads, int *first_upload_frame,

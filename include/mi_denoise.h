@@ -625,6 +625,133 @@ int mid_sequence_atrous_joint_temporal(mid_ctx *ctx, const mid_atrous_params *p,
                                        const void *const *host_frames, int n_frames, const void *const *host_layers, int n_layers,
                                        int k, int first, int count, void *const *host_out, int out_format, int overlap, float *timings_ms);
 
+/* ---- a4i: the variance-guided a-trous filter ----------------------------------------------------
+ * What gives SVGF its name: a per-pixel variance of the luminance steers the colour edge-stopping term of a4g's passes and is
+ * filtered along with the colour.  a4g's only colour term is one global colorSigma halved every pass: too tight where a
+ * path-traced frame is noisy, too loose where it has converged.  The term here is wide where the estimate is noisy and narrow
+ * where it is not.  Two entry points: mid_atrous_moments estimates V_0, mid_atrous_variance runs the passes.
+ * Luminance everywhere: l(C) = fma(0.0722f, b, fma(0.7152f, g, 0.2126f * r)) of the widened fp32 texel (RGBA8 texels c/255).
+ *
+ * (1) mid_atrous_moments.  For output frame t the window is f = max(0, t-k) .. min(n_frames-1, t+k), k >= 0, and in every frame
+ * of it a 7x7 neighbourhood o = (i, j), |i|, |j| <= 3, is taken; taps outside the image are skipped.  With q = p + o:
+ *   w(p,f,o) = prod_l exp(-0.5 |G[t][l](p) - G[f][l](q)|^2_rgb / sigma_l^2)                       (no spatial kernel)
+ *   d        = l(C[f](q)) - l(C[t](p))       -- shifted by the centre's luminance, so that the subtraction below does not cancel
+ *   W += w;  wd = w * d;  s1 += wd;  s2 = fma(wd, d, s2)     frames ascending, inside a frame j = -3 .. 3, then i = -3 .. 3
+ *   m = s1 / W;  v = fma(-m, m, s2 / W);  V_0(p) = v < 0 ? 0 : v                                   (a NaN stays a NaN)
+ * The layer exponent is a4g's FMA chain with the same sc_l, started at 0; w = 2^arg.  The centre tap has w = 1 and d = 0, so
+ * W >= 1.  k = 0 is SVGF's spatial estimate; k > 0 the temporal one under this library's policy: no motion vectors, the layers
+ * reject what moved.  var_out: one fp32 plane of width * height floats, 16-byte aligned.  frames / layers: frame-major tables as
+ * in mid_atrous_joint_temporal (layers[f * n_layers + l]).  p->format: the frames' MID_FMT_* and, through MID_FMT_WITH_GUIDE,
+ * the guide format.
+ * Precision: |V - V_ref| <= 1e-5 * max(1, M2_ref), M2 = s2 / W in float64: both terms of v carry the rounding of a sum of that
+ * size.  Bit identities: appended all-zero layers leave the bits; neighbour frames whose every weight is exactly 0 leave the
+ * bits of k = 0; an RGBA8 / RGBA16F frame gives the bits of the float frame it widens to.
+ * Classes (lanes run along x; no scratch memory; no register array indexed by a run-time value):
+ *   layers 1       kernel tiled   pixels 64 x 16  LDS tile 70 x 22  bytes 24640  workgroups per CU 6 by LDS, 3 by registers
+ *   layers 2       kernel tiled   pixels 64 x 16  LDS tile 70 x 22  bytes 43120  workgroups per CU 3
+ *   layers 3       kernel tiled   pixels 64 x 16  LDS tile 70 x 22  bytes 61600  workgroups per CU 2
+ *   layers 4       kernel tiled   pixels 64 x 16  LDS tile 70 x 22  bytes 80080  workgroups per CU 2
+ *   layers 5..16   kernel global  pixels 64 x 4   no LDS
+ * tiled: eight waves, two rows per wave; per neighbour frame the tile is refilled with ONE plane of luminances and 3 L planes of
+ * scaled guide values (two barriers); the centres and the sums W, s1, s2 stay in registers.  global: one pixel per lane.
+ * MID_ERR_INVALID before anything is queued, var_out untouched: a NULL pointer; n_layers outside 1..16; a sigma that is not
+ * finite and > 0; an unknown frame or guide format; the alignment rules of a4e (var_out: 16 bytes); n_frames < 1, k < 0, t
+ * outside [0, n_frames); var_out overlapping a frame or layer of the window;
+ * min(2k+1, n_frames) * (n_layers + 1) > MID_NLM_LAYERS_TEMPORAL_MAX_POINTERS; width or height < 1, or 2^30 pixels and more.
+ *
+ * (2) mid_atrous_variance.  Pass i at step s = 2^i over the colour level C_i and the variance plane V_i (V of the call's first
+ * pass is var_in); K, k1, sc_l, the tap order and the skipped taps are a4g's.  For q = p + s o:
+ *   vt(p)      = sum g(i) g(j) V_i(p + (i,j)) / sum g(i) g(j),  g = (1, 2, 1)/4, |i|, |j| <= 1 at step 1 whatever s, in-image
+ *                taps only, j then i; num = fma(g g, V, num), den += g g, one IEEE division
+ *   scv(p)     = (float)log2(e) / fma(sigmaLum, sqrtf(vt(p)), epsilon)         (IEEE sqrt and division, once per pixel)
+ *   arg        = a4g's layer chain from 0, then  arg = fma(-|l(C_i(p)) - l(C_i(q))|, scv(p), arg)
+ *   w          = K(o) * 2^arg,  0 for q outside the image;  order j = -2 .. 2, inside it i = -2 .. 2
+ *   acc = fma(C_i(q), w, acc);  accw += w;  accv = fma(w * w, V_i(q), accv)
+ *   C_{i+1}(p) = acc / accw (per channel);     V_{i+1}(p) = accv / (accw * accw)
+ * that is, the luminance weight is SVGF's exp(-|dl| / (sigmaLum sqrt(vt) + epsilon)) and the variance of a weighted mean of
+ * independent samples is propagated.  sigmaLum == 0 switches the luminance term off: vt is not read, the colour output has the
+ * bits of mid_atrous_joint with colorSigma = 0, and the variance is still propagated.  Otherwise sigmaLum > 0 and finite (SVGF
+ * uses 4) and epsilon > 0 and finite.
+ * Why epsilon is a parameter and not SVGF's 1e-8: where vt = 0 the denominator IS epsilon.  Two texels of a level that differ
+ * only by the rounding of earlier passes differ by about 1e-7 |l|; with a denominator below that resolution their weight is
+ * exp(-10) or exp(0) by the toss of a coin, and so is the result -- in fp32 and in float64 alike, with different tosses.  epsilon
+ * belongs well above the fp32 resolution of the luminances it meets: 1e-3 suits values of order 1.
+ * Arguments: `in` the frame; var_in a const float plane; layers, layer_sigma, out, out_format as in a4g; var_out a float plane
+ * for V of the last pass, or NULL: the last pass then stores no variance (a wave-uniform flag) and the colour bits are the same.
+ * scratch: mid_atrous_variance_scratch_bytes(p) = (0, 1 or 2 for n_passes 1, 2, 3 and more) * (16 + 4) * width * height bytes,
+ * 16-byte aligned, the RGBA32F colour levels first, then the float variance levels.  var_in / var_out: 16-byte aligned.
+ * Chain identity: passes [0, N) in one call are, bit for bit, N one-pass calls with first_pass = i through RGBA32F buffers and
+ * float planes; a launch knows its step and nothing of n_passes.
+ * Precision: colour within 1e-5 * max(1, |ref|) and V within 1e-5 * max(1, max V_ref) of the formula in float64, end to end, on
+ * inputs where the float64 formula itself is stable against fp32 rounding of its levels (see epsilon above).
+ * Classes (lanes run along x; no scratch memory; eight waves per workgroup in the LDS class).  comb is a4g's row comb with one
+ * plane more: float4 colour, one float of V and 3 L floats of scaled guides, 16 + 4 + 12 L bytes per texel; 16 rows per
+ * workgroup while two workgroups fit a CU, else 8.  vt(p) is loaded by each lane from global memory, nine loads over three
+ * rows: in a comb tile the rows y +- 1 belong to other residue classes.  There is no fixed-step tiled class.
+ *   layers 1   step 1    kernel comb  pixels 64 x 16  LDS tile 68 x 20   bytes 43520   workgroups per CU 3
+ *   layers 2   step 1    kernel comb  pixels 64 x 16  LDS tile 68 x 20   bytes 59840   workgroups per CU 2
+ *   layers 3   step 1    kernel comb  pixels 64 x 16  LDS tile 68 x 20   bytes 76160   workgroups per CU 2
+ *   layers 4   step 1    kernel comb  pixels 64 x 8   LDS tile 68 x 12   bytes 55488   workgroups per CU 2
+ *   layers 1   step 2    kernel comb  pixels 64 x 16  LDS tile 72 x 20   bytes 46080   workgroups per CU 3
+ *   layers 2   step 2    kernel comb  pixels 64 x 16  LDS tile 72 x 20   bytes 63360   workgroups per CU 2
+ *   layers 3   step 2    kernel comb  pixels 64 x 16  LDS tile 72 x 20   bytes 80640   workgroups per CU 2
+ *   layers 4   step 2    kernel comb  pixels 64 x 8   LDS tile 72 x 12   bytes 58752   workgroups per CU 2
+ *   layers 1   step 4    kernel comb  pixels 64 x 16  LDS tile 80 x 20   bytes 51200   workgroups per CU 3
+ *   layers 2   step 4    kernel comb  pixels 64 x 16  LDS tile 80 x 20   bytes 70400   workgroups per CU 2
+ *   layers 3   step 4    kernel comb  pixels 64 x 8   LDS tile 80 x 12   bytes 53760   workgroups per CU 3
+ *   layers 4   step 4    kernel comb  pixels 64 x 8   LDS tile 80 x 12   bytes 65280   workgroups per CU 2
+ *   layers 1   step 8    kernel comb  pixels 64 x 16  LDS tile 96 x 20   bytes 61440   workgroups per CU 2
+ *   layers 2   step 8    kernel comb  pixels 64 x 8   LDS tile 96 x 12   bytes 50688   workgroups per CU 3
+ *   layers 3   step 8    kernel comb  pixels 64 x 8   LDS tile 96 x 12   bytes 64512   workgroups per CU 2
+ *   layers 4   step 8    kernel comb  pixels 64 x 8   LDS tile 96 x 12   bytes 78336   workgroups per CU 2
+ *   layers 1   step 16   kernel comb  pixels 64 x 16  LDS tile 128 x 20  bytes 81920   workgroups per CU 2
+ *   layers 2   step 16   kernel comb  pixels 64 x 8   LDS tile 128 x 12  bytes 67584   workgroups per CU 2
+ *   layers 3   step 16   kernel comb  pixels 64 x 8   LDS tile 128 x 12  bytes 86016   workgroups per CU 1
+ *   layers 4   step 16   kernel comb  pixels 64 x 8   LDS tile 128 x 12  bytes 104448  workgroups per CU 1
+ *   layers 1   step 32   kernel comb  pixels 64 x 8   LDS tile 192 x 12  bytes 73728   workgroups per CU 2
+ *   layers 2   step 32   kernel comb  pixels 64 x 8   LDS tile 192 x 12  bytes 101376  workgroups per CU 1
+ *   layers 3   step 32   kernel comb  pixels 64 x 8   LDS tile 192 x 12  bytes 129024  workgroups per CU 1
+ *   layers 4   step 32   kernel comb  pixels 64 x 8   LDS tile 192 x 12  bytes 156672  workgroups per CU 1
+ *   layers 5..16  step 1..32     kernel global  pixels 64 x 4  no LDS
+ *   layers 1..16  step 64, 128   kernel global  pixels 64 x 4  no LDS
+ * The class follows from (step, n_layers) and the device's LDS size alone; nothing is refused for LDS reasons: what does not
+ * fit takes global taps.  Against a4g's table only (step 8, 2 layers) falls from 16 rows to 8 because of the extra plane.
+ * MID_ERR_INVALID before anything is queued, out, var_out and scratch untouched: every refusal of a4g that applies (there is no
+ * colorSigma); sigmaLum < 0 or not finite; with sigmaLum > 0, epsilon <= 0 or not finite; NULL var_in; var_in or var_out not
+ * 16-byte aligned; `out`, var_out or `scratch` overlapping `in`, var_in, a layer or each other. */
+typedef struct mid_atrous_moments_params {
+    int32_t width, height;
+    int32_t format;       /* MID_FMT_* of the frames, guide format through MID_FMT_WITH_GUIDE as in a4e */
+} mid_atrous_moments_params;
+int mid_atrous_moments(mid_ctx *ctx, const mid_atrous_moments_params *p, const float *layer_sigma /* n_layers host floats */,
+                       const void *const *frames /* host array of n_frames device ptrs */,
+                       const uint32_t *const *layers /* host array of n_frames * n_layers device ptrs */,
+                       int n_layers, int n_frames, int k, int t, float *var_out, void *stream);
+typedef struct mid_atrous_variance_params {
+    int32_t width, height;
+    int32_t first_pass;   /* absolute index of the first pass, 0..7 */
+    int32_t n_passes;     /* >= 1, first_pass + n_passes <= 8 */
+    float   sigmaLum;     /* 0: no luminance term; otherwise > 0 and finite */
+    float   epsilon;      /* > 0 and finite where sigmaLum > 0 */
+    int32_t format;       /* MID_FMT_* of the frame, guide format through MID_FMT_WITH_GUIDE as in a4e */
+} mid_atrous_variance_params;
+size_t mid_atrous_variance_scratch_bytes(const mid_atrous_variance_params *p);
+int mid_atrous_variance(mid_ctx *ctx, const mid_atrous_variance_params *p, const float *layer_sigma /* n_layers host floats */,
+                        const void *in, const float *var_in,
+                        const uint32_t *const *layers /* host array of n_layers device ptrs; cast RGBA16F / RGBA32F layers with MID_FMT_WITH_GUIDE */,
+                        int n_layers, void *out, int out_format, float *var_out, void *scratch, void *stream);
+/* An animation through the frame pipeline (section a8) with the variance-guided filter as its compute stage:
+ * mid_sequence_atrous_joint_temporal's schedule, where k is the window of the MOMENTS.  Per output frame t: mid_atrous_moments over
+ * the window into a V_0 plane, then mid_atrous_variance (var_out = NULL) on frame t alone with frame t's layers; output t has the
+ * bits of those two calls.  p->first_pass must be 0.  Each host frame and its layers are uploaded once.  The colour levels, the
+ * variance levels and the V_0 plane live in the context's cache, one set per kernel stream, and are released with the rest
+ * (mid_ctx_release_cached).  Same ring, same layer ring, same direct-store rule, same refusals (a call inside a recording among
+ * them), same timings_ms and timeline export as the other stages; plus the refusals of both calls, which leave host_out and
+ * timings_ms untouched. */
+int mid_sequence_atrous_variance(mid_ctx *ctx, const mid_atrous_variance_params *p, const float *layer_sigma,
+                                 const void *const *host_frames, int n_frames, const void *const *host_layers, int n_layers,
+                                 int k, int first, int count, void *const *host_out, int out_format, int overlap, float *timings_ms);
+
 /* ---- a5: normalize ----------------------------------------------------------------------
  * One dispatch of shaders/normalize.comp (RecordCommandsOfExecuteAndTransfer(normKernel=true)):
  * out = weightColor / normWeight, or (1,0,1,1) where normWeight == 0; bindings {0: out; 1: W}. */

@@ -1,0 +1,156 @@
+"""GPU suite: the luminance moments of the variance-guided a-trous filter, mid_atrous_moments (include/mi_denoise.h, section a4i),
+in both classes of csrc/atrous_variance.hip: the 64 x 16 LDS tiles for 1..4 layers, global taps for 5 and 16.
+
+Frames (h, w): (1, 1); (5, 7), smaller than the 7 x 7 neighbourhood; (17, 65): a tile seam at x = 64 and at y = 16, one column and
+one row beyond it; (37, 131): three tile columns, the last 3 wide, and three tile rows.
+
+What is asserted: the float64 checker (np_atrous_variance.moments) within |dV| <= 1e-5 max(1, M2_ref) per pixel -- both terms of
+v = M2 - m^2 carry the rounding of a sum of the size of M2; the bit identities of the header; every refusal with var_out untouched.
+"""
+import ctypes
+
+import numpy as np
+import pytest
+
+import atrous_variance_inputs as avi
+import image_denoising_filter_amd as mid
+import np_atrous_variance as chk
+
+pytestmark = pytest.mark.gpu
+
+SHAPES = [(1, 1), (5, 7), (17, 65), (37, 131)]
+LAYERS = (1, 2, 3, 4, 5, 16)
+DT = (np.float32, np.float16, np.uint8)
+N = 4
+TOL = 1e-5
+WORST = {}
+
+
+def same(a, b):
+    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+
+
+def inputs(shape, L, fdt, gdt):
+    return [avi.frame_of(shape, f, fdt) for f in range(N)], [avi.layers_of(shape, L, gdt, f) for f in range(N)]
+
+
+@pytest.mark.parametrize("L", LAYERS)
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_against_float64(ctx, shape, L):
+    sg = avi.sigmas_of(L)
+    for k in (0, 1, 2):
+        n = k + LAYERS.index(L) + SHAPES.index(shape)
+        fdt, gdt = DT[n % 3], DT[(n // 3 + k) % 3]
+        fr, ly = inputs(shape, L, fdt, gdt)
+        for t in range(N):
+            got = ctx.atrous_moments(fr, ly, sg, k=k, t=t)
+            ref, m2 = chk.moments(fr, ly, sg, k=k, t=t)
+            err = float(np.max(np.abs(got.astype(np.float64) - ref) / np.maximum(1.0, m2)))
+            key = f"{'LDS tiles' if L <= 4 else 'global taps'}, L={L}"
+            WORST[key] = max(WORST.get(key, 0.0), err)
+            print(f"{shape} L={L} k={k} t={t} frames={np.dtype(fdt).name} guides={np.dtype(gdt).name}: {err:.3e} (max V {ref.max():.3g})")
+            assert got.dtype == np.float32 and got.shape == shape and np.isfinite(got).all() and got.min() >= 0
+            assert err <= TOL, (shape, L, k, t, err)
+
+
+@pytest.mark.parametrize("gdt", DT, ids=lambda d: np.dtype(d).name)
+def test_appended_zero_layers_change_no_bit(ctx, gdt):
+    shape = (17, 65)
+    zero = np.zeros(shape + (4,), gdt)
+    odd = [0.01, 3.0, 0.3, 7.0] * 4
+    for base_L in (1, 5):
+        fr, ly = inputs(shape, base_L, np.float32, gdt)
+        sg = avi.sigmas_of(base_L)
+        want = ctx.atrous_moments(fr, ly, sg, k=1, t=1)
+        for extra in ((1, 2, 3, 4, 15) if base_L == 1 else (11,)):     # 2, 3, 4 layers: tiles; 5 and 16: global taps -- one arithmetic
+            more = [l + [zero] * extra for l in ly]
+            assert same(ctx.atrous_moments(fr, more, sg + odd[:extra], k=1, t=1), want), (base_L, extra)
+
+
+@pytest.mark.parametrize("L", [2, 5])
+def test_neighbours_without_weight_leave_the_bits_of_k_0(ctx, L):
+    shape = (17, 65)
+    fr, ly = inputs(shape, L, np.float32, np.float32)
+    sg = avi.sigmas_of(L)
+    for t in (0, 2):
+        far = [[g + np.float32(100.0) for g in ly[f]] if f != t else ly[f] for f in range(N)]     # 200 sigma and more away: 2^arg is exactly 0
+        want = ctx.atrous_moments(fr, ly, sg, k=0, t=t)
+        assert same(ctx.atrous_moments(fr, far, sg, k=2, t=t), want), (L, t)
+        assert not same(ctx.atrous_moments(fr, ly, sg, k=2, t=t), want)
+
+
+@pytest.mark.parametrize("L", [3, 5])
+def test_frame_formats_give_the_bits_of_the_widened_frame(ctx, L):
+    shape = (37, 131)
+    sg = avi.sigmas_of(L)
+    _, ly = inputs(shape, L, np.float32, np.float32)
+    f16 = [avi.frame_of(shape, f, np.float16) for f in range(N)]
+    u8 = [avi.frame_of(shape, f, np.uint8) for f in range(N)]
+    wide = [(u.astype(np.float32) / np.float32(255)).astype(np.float32) for u in u8]       # the correctly rounded fp32 quotient c / 255
+    for k, t in ((0, 0), (1, 2)):
+        assert same(ctx.atrous_moments(f16, ly, sg, k=k, t=t), ctx.atrous_moments([f.astype(np.float32) for f in f16], ly, sg, k=k, t=t))
+        assert same(ctx.atrous_moments(u8, ly, sg, k=k, t=t), ctx.atrous_moments(wide, ly, sg, k=k, t=t))
+
+
+def test_a_nan_stays_a_nan(ctx):
+    shape = (17, 65)
+    fr, ly = inputs(shape, 2, np.float32, np.float32)
+    bad = [f.copy() for f in fr]
+    bad[1][8, 30, 1] = np.nan
+    got = ctx.atrous_moments(bad, ly, avi.sigmas_of(2), k=0, t=1)
+    ref, _ = chk.moments(bad, ly, avi.sigmas_of(2), k=0, t=1)
+    assert np.array_equal(np.isnan(got), np.isnan(ref)) and np.isnan(got).sum() == 49
+
+
+def test_every_refusal_leaves_the_output_alone(ctx):
+    h, w = 12, 20
+    F32, F16 = mid.FMT_RGBA32F, mid.FMT_RGBA16F
+    WG = mid.api.fmt_with_guide
+    d_fr = [ctx.upload(np.ones((h, w, 4), np.float32)) for _ in range(3)]
+    d_l = [ctx.upload(np.full((h, w, 4), 0.5, np.float32)) for _ in range(6)]
+    sent = np.full((h, w), 7.0, np.float32)
+    d_var = ctx.upload(sent)
+    base = dict(w=w, h=h, fmt=WG(F32, F32), sig=[0.5, 0.5], frames=[d.ptr for d in d_fr], layers=[d.ptr for d in d_l], nl=2, n=3, k=1, t=1,
+                var=d_var.ptr, null_p=False, null_fr=False, null_tbl=False)
+
+    def call(**kw):
+        a = dict(base, **kw)
+        p = mid.AtrousMomentsParams(a["w"], a["h"], a["fmt"])
+        sig = None if a["sig"] is None else (ctypes.c_float * 16)(*a["sig"])
+        fr = None if a["null_fr"] else (ctypes.c_void_p * 64)(*a["frames"])
+        tbl = None if a["null_tbl"] else (ctypes.c_void_p * 1024)(*a["layers"])
+        return mid.lib.mid_atrous_moments(ctx.handle, None if a["null_p"] else ctypes.byref(p), sig, fr, tbl, a["nl"], a["n"], a["k"], a["t"],
+                                          a["var"], None)
+
+    nan, inf = float("nan"), float("inf")
+    fp, lp = base["frames"], base["layers"]
+    refused = {
+        "NULL params": dict(null_p=True), "NULL sigmas": dict(sig=None), "NULL frame table": dict(null_fr=True), "NULL var_out": dict(var=None),
+        "NULL layer table": dict(null_tbl=True), "NULL frame of the window": dict(frames=[fp[0], fp[1], None]),
+        "NULL layer of the window": dict(layers=lp[:5] + [None]),
+        "no layers": dict(nl=0), "17 layers": dict(nl=17, layers=[lp[0]] * 51, sig=[0.5] * 16),
+        "sigma 0": dict(sig=[0.5, 0.0]), "sigma < 0": dict(sig=[-1.0, 0.5]), "sigma NaN": dict(sig=[0.5, nan]), "sigma Inf": dict(sig=[inf, 0.5]),
+        "unknown frame format": dict(fmt=3), "unknown guide code": dict(fmt=F32 | (9 << 8)), "bits above 15": dict(fmt=F32 | (1 << 16)),
+        "RGBA16F frame off by 4": dict(fmt=WG(F16, F32), frames=[fp[0] + 4, fp[1], fp[2]]), "RGBA32F guide off by 8": dict(layers=[lp[0] + 8] + lp[1:]),
+        "var_out off by 4": dict(var=d_var.ptr + 4),
+        "t < 0": dict(t=-1), "t beyond the sequence": dict(t=3), "no frames": dict(n=0, t=0), "k < 0": dict(k=-1),
+        "var_out is a frame": dict(var=fp[2]), "var_out inside a frame": dict(var=fp[0] + 32), "var_out is a layer": dict(var=lp[3]),
+        "too many pointers": dict(n=64, k=31, t=31, nl=2, frames=[fp[0]] * 64, layers=[lp[0]] * 128),
+        "width 0": dict(w=0), "height 0": dict(h=0), "negative size": dict(w=-4), "2^30 pixels": dict(w=32768, h=32768),
+    }
+    for name, kw in refused.items():
+        rc = call(**kw)
+        assert rc == 1, f"{name}: returned {rc}, {mid.lib.mid_last_error()}"
+        assert mid.lib.mid_last_error(), name
+    ctx.sync()
+    assert same(ctx.download(d_var, sent.shape, np.float32), sent)
+    # a frame outside the window may be NULL or the output itself: only the window is read
+    assert call(k=0, t=0, frames=[fp[0], None, d_var.ptr]) == 0
+    assert call() == 0
+    ctx.sync()
+    assert same(ctx.download(d_var, sent.shape, np.float32), np.zeros((h, w), np.float32))
+
+
+def test_report_worst_errors():
+    for k in sorted(WORST):
+        print(f"worst error of the moments against float64, {k}: {WORST[k]:.3e}")

@@ -30,6 +30,10 @@ int mid::atrous_check(const mid_atrous_params *, const char *, const float *, bo
 size_t mid::atrous_scratch_frames(int) { return 0; }   // (atrous.hip)
 int mid::atrous_temporal_out(mid_ctx *, const mid_atrous_params *, const float *, const void *const *, const uint32_t *const *, int, int, int, int, int, void *const *, int, void *, void *, hipStream_t) { return MID_ERR_UNSUPPORTED; }   // (atrous_temporal.hip)
 int mid::atrous_temporal_check(const mid_atrous_params *, const char *, const float *, bool, int, int, int) { return MID_ERR_UNSUPPORTED; }   // (atrous_temporal.hip)
+int mid::atrous_moments_out(mid_ctx *, const mid_atrous_moments_params *, const float *, const void *const *, const uint32_t *const *, int, int, int, int, float *, hipStream_t) { return MID_ERR_UNSUPPORTED; }   // (atrous_variance.hip)
+int mid::atrous_variance_out(mid_ctx *, const mid_atrous_variance_params *, const float *, const void *, const float *, const uint32_t *const *, int, void *, int, float *, void *const *, float *const *, hipStream_t) { return MID_ERR_UNSUPPORTED; }   // (atrous_variance.hip)
+int mid::atrous_moments_check(const mid_atrous_moments_params *, const char *, const float *, bool, int, int, int) { return MID_ERR_UNSUPPORTED; }   // (atrous_variance.hip)
+int mid::atrous_variance_check(const mid_atrous_variance_params *, const char *, const float *, bool, int) { return MID_ERR_UNSUPPORTED; }   // (atrous_variance.hip)
 int mid::nlm_check_params(const mid_nlm_params *) { return MID_ERR_UNSUPPORTED; }   // (nlm.hip)
 int mid::bilateral_check_params(const mid_bilateral_params *, const char *, bool) { return MID_ERR_UNSUPPORTED; }   // (bilateral.hip)
 
