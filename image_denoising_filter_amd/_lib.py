@@ -62,6 +62,13 @@ class AtrousVarianceParams(ctypes.Structure):
                 ("sigmaLum", ctypes.c_float), ("epsilon", ctypes.c_float), ("format", ctypes.c_int32)]
 
 
+class TemporalAccumParams(ctypes.Structure):
+    """mid_temporal_accum_params (section a4j)."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("alpha", ctypes.c_float), ("alphaMoments", ctypes.c_float),
+                ("historyMax", ctypes.c_float), ("historyFull", ctypes.c_float), ("format", ctypes.c_int32)]
+
+
 class NormalizeParams(ctypes.Structure):
     _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32)]
 
@@ -132,6 +139,12 @@ _SIGNATURES = {
     "mid_sequence_atrous_variance": (ctypes.c_int, [_P, ctypes.POINTER(AtrousVarianceParams), ctypes.POINTER(ctypes.c_float), c_void_pp,
                                                     ctypes.c_int, c_void_pp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                     c_void_pp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
+    "mid_temporal_accumulate": (ctypes.c_int, [_P, ctypes.POINTER(TemporalAccumParams), ctypes.POINTER(ctypes.c_float), _P, c_void_pp, c_void_pp,
+                                               ctypes.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mid_sequence_atrous_recursive": (ctypes.c_int, [_P, ctypes.POINTER(TemporalAccumParams), ctypes.POINTER(AtrousVarianceParams),
+                                                     ctypes.POINTER(ctypes.c_float), c_void_pp, ctypes.c_int, c_void_pp, ctypes.c_int, c_void_pp,
+                                                     ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_pp, ctypes.c_int, ctypes.c_int,
+                                                     ctypes.POINTER(ctypes.c_float)]),
     "mid_normalize": (ctypes.c_int, [_P, ctypes.POINTER(NormalizeParams), _P, _P, _P]),
     "mid_unpack_u8": (ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_int, _P, _P]),
     "mid_pack_u8": (ctypes.c_int, [_P, _P, ctypes.c_size_t, _P, _P]),

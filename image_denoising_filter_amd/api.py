@@ -15,7 +15,7 @@ import weakref
 
 import numpy as np
 
-from ._lib import AtrousMomentsParams, AtrousParams, AtrousVarianceParams, BilateralParams, Image, NlmParams, NormalizeParams, c_void_pp, lib
+from ._lib import AtrousMomentsParams, AtrousParams, AtrousVarianceParams, BilateralParams, Image, NlmParams, NormalizeParams, TemporalAccumParams, c_void_pp, lib
 
 FMT_RGBA32F, FMT_RGBA8, FMT_RGBA16F = 0, 1, 2
 
@@ -556,6 +556,40 @@ class Context:
         out = self.download(d_out, (h, w, 4), out_dtype)
         return (out, self.download(d_vout, (h, w), np.float32)) if return_variance else out
 
+    def temporal_accumulate(self, frame, layers, prev_layers, sigmas, hist=None, motion=None, var_spatial=None, alpha=0.2,
+                            alpha_moments=0.2, history_max=32, history_full=4):
+        """One step of the recursive temporal accumulation (mid_temporal_accumulate): the history `hist` = (colour, state), two
+        float32 (h, w, 4) planes of the previous step (state = (m1, m2, N, 0)), or None for no history, is reprojected by `motion`
+        (float32 (h, w, 2), pixels: p was at p + motion(p); None = zero motion), weighed by the guide layers (`layers` of this frame
+        against `prev_layers` of the previous one: 0..16 (h, w, 4) layers each, uint8, float16 or float32 and all of one dtype;
+        prev_layers None = `layers`) and blended with `frame`.  var_spatial: a float32 (h, w) plane (atrous_moments at k = 0) or
+        None.  Returns (colour, state, variance): float32 (h, w, 4), (h, w, 4) and (h, w)."""
+        who = "temporal_accumulate"
+        (frame,) = _same_frames([frame], who)
+        h, w = frame.shape[:2]
+        layers = list(layers)
+        prev_layers = layers if prev_layers is None else list(prev_layers)
+        n_layers, flat = _flat_layers([layers, prev_layers], 2, h, w, who, _GUIDE_DTYPES)
+        hc, hs = (None, None) if hist is None else hist
+        planes = []
+        for name, a, shape in (("hist[0]", hc, (h, w, 4)), ("hist[1]", hs, (h, w, 4)), ("motion", motion, (h, w, 2)), ("var_spatial", var_spatial, (h, w))):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float32)
+                if a.shape != shape:
+                    raise ValueError(f"{who}: {name} must be {shape}, got {a.shape}")
+                a = self.upload(a)
+            planes.append(a)                                   # (the buffers live until the call has been downloaded)
+        p_hc, p_hs, p_mv, p_vs = (d.ptr if d is not None else None for d in planes)
+        p = TemporalAccumParams(w, h, alpha, alpha_moments, history_max, history_full, _guide_fmt(_fmt_of(frame), flat, who))
+        d_in = self.upload(frame)
+        d_l = [self.upload(l) for l in flat]
+        d_col, d_st, d_var = self.alloc(w * h * 16), self.alloc(w * h * 16), self.alloc(w * h * 4)
+        _check(lib.mid_temporal_accumulate(self.handle, ctypes.byref(p), _layer_sigmas(sigmas, n_layers, who), d_in.ptr,
+                                           (ctypes.c_void_p * max(n_layers, 1))(*[d.ptr for d in d_l[:n_layers]]),
+                                           (ctypes.c_void_p * max(n_layers, 1))(*[d.ptr for d in d_l[n_layers:]]), n_layers, p_mv, p_hc, p_hs, p_vs,
+                                           d_col.ptr, d_st.ptr, d_var.ptr, None), "mid_temporal_accumulate")
+        return self.download(d_col, (h, w, 4), np.float32), self.download(d_st, (h, w, 4), np.float32), self.download(d_var, (h, w), np.float32)
+
     def normalize(self, W):
         """normalize.comp."""
         W = np.ascontiguousarray(W, dtype=np.float32)
@@ -893,6 +927,57 @@ class Context:
         return self._sequence_host("sequence_atrous_variance", lambda hin, hout, w, h, fmt, hlayers, n_layers, count: self.sequence_atrous_variance_pinned(
             hin, hout, w, h, fmt, hlayers, n_layers, sigmas, k, first, count, passes, sigma_lum, epsilon, overlap, out_dtype),
             frames, layers, _GUIDE_DTYPES, first, count, pinned, pinned_out, out_dtype)
+
+    def sequence_atrous_recursive_pinned(self, hin, hout, w, h, fmt, hlayers, n_layers, sigmas, hmotion=None, feedback=1, warmup=16, first=0,
+                                         count=None, passes=5, sigma_lum=4.0, epsilon=1e-3, alpha=0.2, alpha_moments=0.2, history_max=32,
+                                         history_full=4, overlap=True, out_dtype=None):
+        """mid_sequence_atrous_recursive on host pointers the caller already holds: nothing but the C call.  hin, hlayers, hout as
+        for sequence_atrous_variance_pinned; hmotion: one pointer per frame to a float32 (h, w, 2) plane, or None: zero motion.
+        Returns (wall_ms of the whole call, kernel_ms, copy_ms)."""
+        n = len(hin)
+        count = n - first if count is None else count
+        if len(hout) < count:
+            raise ValueError(f"{count} outputs, {len(hout)} output buffers given")
+        if len(hlayers) != n * n_layers:
+            raise ValueError(f"{n} frames x {n_layers} layers, {len(hlayers)} layer pointers given")
+        if hmotion is not None and len(hmotion) != n:
+            raise ValueError(f"{n} frames, {len(hmotion)} motion planes given")
+        ap = TemporalAccumParams(w, h, alpha, alpha_moments, history_max, history_full, fmt)
+        vp = AtrousVarianceParams(w, h, 0, passes, sigma_lum, epsilon, fmt)
+        t = (ctypes.c_float * 3)()
+        _check(lib.mid_sequence_atrous_recursive(self.handle, ctypes.byref(ap), ctypes.byref(vp), _layer_sigmas(sigmas, n_layers, "sequence_atrous_recursive"),
+                                                 (ctypes.c_void_p * n)(*hin), n, (ctypes.c_void_p * max(len(hlayers), 1))(*hlayers), n_layers,
+                                                 None if hmotion is None else (ctypes.c_void_p * n)(*hmotion), feedback, warmup, first, count,
+                                                 (ctypes.c_void_p * max(count, 1))(*hout[:max(count, 0)]), _OUT_FMT[_out_dtype(False, out_dtype)],
+                                                 1 if overlap else 0, t), "mid_sequence_atrous_recursive")
+        return tuple(t)
+
+    def sequence_atrous_recursive(self, frames, layers, sigmas, motion=None, feedback=1, warmup=16, first=0, count=None, passes=5, sigma_lum=4.0,
+                                  epsilon=1e-3, alpha=0.2, alpha_moments=0.2, history_max=32, history_full=4, overlap=True, pinned=True,
+                                  pinned_out=True, out_dtype=None):
+        """Outputs [first, first+count) of an animation through the pipeline with the recursive temporal accumulation as its compute
+        stage (mid_sequence_atrous_recursive).  From frame s = max(0, first - warmup) on, per frame t: Vs = atrous_moments([frame], k=0),
+        (colour, state, var) = temporal_accumulate(frame t, layers t, layers t-1, history, motion[t], Vs), output = atrous_variance(colour,
+        var, layers t, passes); the next history is (colour, state) with feedback=0 and (the level after pass 0, state) with
+        feedback=1.  motion: one float32 (h, w, 2) plane per frame, or None.  A run with first > 0 equals the whole run bit for bit
+        only when warmup reaches frame 0.  pinned, pinned_out, out_dtype as for sequence_bilateral.
+        Returns (outputs, (wall_ms, kernel_ms, copy_ms))."""
+        out_dtype = _out_dtype(False, out_dtype)
+        hmv = None
+        if motion is not None:
+            hmv = [np.ascontiguousarray(m, dtype=np.float32) for m in motion]
+            shape = np.asarray(frames[0]).shape[:2] + (2,)
+            if len(hmv) != len(frames) or any(m.shape != shape for m in hmv):
+                raise ValueError(f"sequence_atrous_recursive: motion must be one {shape} plane per frame")
+        pmv = PinnedFrames(self, hmv) if hmv is not None and pinned else None
+        try:
+            ptrs = None if hmv is None else (pmv.ptrs if pmv is not None else [m.ctypes.data for m in hmv])
+            return self._sequence_host("sequence_atrous_recursive", lambda hin, hout, w, h, fmt, hlayers, n_layers, count: self.sequence_atrous_recursive_pinned(
+                hin, hout, w, h, fmt, hlayers, n_layers, sigmas, ptrs, feedback, warmup, first, count, passes, sigma_lum, epsilon, alpha, alpha_moments,
+                history_max, history_full, overlap, out_dtype), frames, layers, _GUIDE_DTYPES, first, count, pinned, pinned_out, out_dtype)
+        finally:
+            if pmv is not None:
+                pmv.free()
 
 
 def _layer_sigmas(sigmas, n_layers, who, noun="sigmas"):

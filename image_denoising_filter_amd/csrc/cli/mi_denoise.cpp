@@ -57,6 +57,10 @@ struct Options {
     float atrous_sigma_color = 0.f; // the a-trous modes: sigma of the colour term at pass 0, halved every pass (0: off)
     float atrous_sigma_lum = 4.f;   // atrous-variance: sigma of the luminance term in standard deviations of the pixel (SVGF's 4; 0: off)
     float atrous_epsilon = 1e-3f;   // atrous-variance: what is added to sigma_lum * sqrt(variance) (> 0)
+    float alpha = 0.2f, alpha_moments = 0.2f, history_max = 32.f;   // atrous-recursive: mid_temporal_accum_params (historyFull stays SVGF's 4)
+    int feedback = 1, warmup = 16;  // atrous-recursive: the next colour history (0: accumulated colour, 1: level after pass 0); warm-up frames of a block
+    std::string motion_layer;       // atrous-recursive: substring of the .exr render element that holds the motion (R, G in pixels); empty: zero motion
+    float motion_sx = 1.f, motion_sy = 1.f;   // --motion-scale
     int search_lo = -7, search_hi = 7, patch_lo = -3, patch_hi = 3;   // shaders/nonlocal.comp:5-6, half-open
     int temporal_k = -1;            // <0: the reference's frame list; >=0: window t-k..t+k of the sorted sequence
     int cpu_radius = 10;            // windowSize, src/main.cpp:1819
@@ -82,7 +86,7 @@ struct Options {
     } while (0)
 
 // --animation-filter, parsed once: the mid_sequence_* family a value runs, what that family reads, and the words of the value.
-enum SeqFamily { SEQ_NLM, SEQ_BILATERAL, SEQ_NLM_LAYERS, SEQ_NLM_LAYERS_TEMPORAL, SEQ_BILATERAL_TEMPORAL, SEQ_BILATERAL_JOINT, SEQ_NLM_JOINT, SEQ_ATROUS, SEQ_ATROUS_TEMPORAL, SEQ_ATROUS_VARIANCE };
+enum SeqFamily { SEQ_NLM, SEQ_BILATERAL, SEQ_NLM_LAYERS, SEQ_NLM_LAYERS_TEMPORAL, SEQ_BILATERAL_TEMPORAL, SEQ_BILATERAL_JOINT, SEQ_NLM_JOINT, SEQ_ATROUS, SEQ_ATROUS_TEMPORAL, SEQ_ATROUS_VARIANCE, SEQ_ATROUS_RECURSIVE };
 struct AnimationFilter {
     const char *name;
     SeqFamily family;
@@ -111,6 +115,7 @@ static const AnimationFilter kAnimationFilters[] = {
     {"atrous", SEQ_ATROUS, true, false, false, "nonlinear-atrous-", "a-trous", "a-trous + layers"},
     {"atrous-temporal", SEQ_ATROUS_TEMPORAL, true, true, false, "nonlinear-atrous-multiframe-", "a-trous", "a-trous + layers, multiframe"},
     {"atrous-variance", SEQ_ATROUS_VARIANCE, true, true, false, "nonlinear-atrous-variance-", "variance-guided a-trous", "a-trous + layers, variance-guided"},
+    {"atrous-recursive", SEQ_ATROUS_RECURSIVE, true, false, false, "nonlinear-atrous-recursive-", "recursive a-trous", "a-trous + layers, recursive accumulation"},
 };
 static const AnimationFilter *animation_filter(const std::string &name)
 {
@@ -556,12 +561,27 @@ public:
         if (af.family != SEQ_NLM && opt.halo_rccl)
             throw std::runtime_error("--halo rccl is not available with --animation-filter " + opt.animation_filter + ": the halo would have to "
                                      "carry every halo frame's layers as well, and that exchange is not built (use --halo host)");
+        const bool recursive = af.family == SEQ_ATROUS_RECURSIVE;
+        if (!recursive && !opt.motion_layer.empty())
+            throw std::runtime_error("--motion-layer applies to --animation-filter atrous-recursive only");
         // every frame's own layers, all of them checked before anything is decoded: 1..16 per frame, the same count for all
         std::vector<std::vector<std::string>> frameLayers(use_layers ? n : 0);
+        std::vector<std::string> motionNames;           // atrous-recursive with --motion-layer: the one render element of each frame that holds its motion
         int L = 0;
         for (int i = 0; i < (int)frameLayers.size(); ++i) {
             std::vector<std::string> none;
             discover_for(frameNames[i], none, frameLayers[i], false, true);
+            if (!opt.motion_layer.empty()) {            // taken out of the guide layers
+                std::vector<std::string> hits, rest;
+                for (const std::string &f : frameLayers[i]) (fs::path(f).filename().string().find(opt.motion_layer) != std::string::npos ? hits : rest).push_back(f);
+                if (hits.size() != 1)
+                    throw std::runtime_error(frameNames[i] + ": --motion-layer " + opt.motion_layer + " matches " + std::to_string(hits.size()) +
+                                             " layer file(s) of this frame, it must match exactly one");
+                if (!is_hdr(hits[0]))
+                    throw std::runtime_error("motion layer " + hits[0] + " is a .png: motion vectors are read from an .exr render element (R, G in pixels)");
+                motionNames.push_back(hits[0]);
+                frameLayers[i] = rest;
+            }
             const int li = (int)frameLayers[i].size();
             if (li < 1 || li > 16)
                 throw std::runtime_error(frameNames[i] + ": " + std::to_string(li) + " layer file(s) found, --animation-filter " + opt.animation_filter + " needs 1..16 per frame");
@@ -575,7 +595,7 @@ public:
         for (auto &fl : frameLayers) allLayers.insert(allLayers.end(), fl.begin(), fl.end());
         if (nlm_guides) for (const std::string &ln : allLayers) if (is_hdr(ln)) (void)load(ln, true);   // refuses, saying why
         const int lfmt = layer_format(allLayers);
-        const std::vector<float> jointSigma = af.family == SEQ_BILATERAL_JOINT || af.family == SEQ_ATROUS || af.family == SEQ_ATROUS_TEMPORAL || af.family == SEQ_ATROUS_VARIANCE ? layer_sigmas(frameLayers[0])            // (every frame has frame 0's layers)
+        const std::vector<float> jointSigma = af.family == SEQ_BILATERAL_JOINT || af.family == SEQ_ATROUS || af.family == SEQ_ATROUS_TEMPORAL || af.family == SEQ_ATROUS_VARIANCE || recursive ? layer_sigmas(frameLayers[0])            // (every frame has frame 0's layers)
                                               : af.family == SEQ_NLM_JOINT ? layer_sigmas(frameLayers[0], true) : std::vector<float>();
         std::cout << "\tloading " << n << " frames\n";
         // Frames are decoded STRAIGHT INTO pinned host memory (mid_image_load_pinned) and the results land in pinned
@@ -658,6 +678,22 @@ public:
                 throw std::runtime_error(frameNames[i] + ": layer " + frameLayers[i][j % L] + " is not " +
                                          (lfmt == MID_FMT_RGBA8 ? "an RGBA8" : lfmt == MID_FMT_RGBA16F ? "an RGBA16F" : "an RGBA32F") + " image of the frame's size");
         });
+        // the motion planes: R and G of the render element, times --motion-scale, one float2 per pixel
+        std::vector<std::vector<float>> motionPlanes(motionNames.size());
+        for_each_file(0, (int)motionNames.size(), [&](int i) {
+            const HostImage m = load(motionNames[i], false);
+            if (m.w != pin.frames[0].width || m.h != pin.frames[0].height || m.format != MID_FMT_RGBA32F)
+                throw std::runtime_error("motion layer " + motionNames[i] + " is not an RGBA32F image of the frame's size");
+            const float *px = (const float *)m.data();
+            motionPlanes[i].resize((size_t)m.w * m.h * 2);
+            for (size_t q = 0; q < (size_t)m.w * m.h; ++q) {
+                motionPlanes[i][2 * q] = px[4 * q] * opt.motion_sx;
+                motionPlanes[i][2 * q + 1] = px[4 * q + 1] * opt.motion_sy;
+            }
+        });
+        std::vector<const void *> motion_ptrs(motionPlanes.size());
+        for (size_t i = 0; i < motionPlanes.size(); ++i) motion_ptrs[i] = motionPlanes[i].data();
+        if (!motionNames.empty()) std::cout << "\tmotion " << motionNames[0] << " scale " << opt.motion_sx << " " << opt.motion_sy << "\n";
         std::vector<const void *> layer_ptrs(layerImgs.size());
         for (size_t j = 0; j < layerImgs.size(); ++j) layer_ptrs[j] = layerImgs[j].data();
         for (int i = 0; i < n; ++i) { if (pin.frame_pinned[i]) pinned_bytes += 2 * frame_bytes_guess + (size_t)L * layer_bytes; else ++n_pageable; }
@@ -698,7 +734,7 @@ public:
         // The k = 0 families take the block as a sub-array of frames, layers and outputs; the others the whole sequence, of which they
         // upload the block plus kk halo frames on either side, and their layers, from the host.
         auto run_stage = [&](mid_ctx *c, const mid_nlm_params &np, const mid_bilateral_params &bpp, const void *const *frames, int nf,
-                             const void *const *layers, int kk, int start, int count, void *const *outs, float *t) {
+                             const void *const *layers, const void *const *motion, int kk, int start, int count, void *const *outs, float *t) {
             const void *const *lp = use_layers ? layers : nullptr;
             switch (af.family) {
             case SEQ_BILATERAL:
@@ -720,6 +756,12 @@ public:
             case SEQ_ATROUS_VARIANCE: {    // the moments over the frames t-k..t+k, then the variance-guided passes on frame t
                 const mid_atrous_variance_params vp{bpp.width, bpp.height, 0, opt.passes, opt.atrous_sigma_lum, opt.atrous_epsilon, bpp.format};
                 MID_CHECK(mid_sequence_atrous_variance(c, &vp, jointSigma.data(), frames, nf, lp, L, kk, start, count, outs, out_fmt, 1, t)); break;
+            }
+            case SEQ_ATROUS_RECURSIVE: {   // per frame, in order: the spatial moments, the accumulation into the history, the variance-guided passes
+                const mid_temporal_accum_params ap{bpp.width, bpp.height, opt.alpha, opt.alpha_moments, opt.history_max, 4.f, bpp.format};
+                const mid_atrous_variance_params vp{bpp.width, bpp.height, 0, opt.passes, opt.atrous_sigma_lum, opt.atrous_epsilon, bpp.format};
+                MID_CHECK(mid_sequence_atrous_recursive(c, &ap, &vp, jointSigma.data(), frames, nf, lp, L, motion, opt.feedback, opt.warmup, start, count,
+                                                        outs, out_fmt, 1, t)); break;
             }
             case SEQ_NLM_JOINT:            // one patch weight from all layers (jointSigma: the h of each layer)
                 MID_CHECK(mid_sequence_nlm_joint(c, &np, jointSigma.data(), frames, nf, lp, L, kk, start, count, outs, out_fmt, 1, t)); break;
@@ -745,7 +787,7 @@ public:
             const void *wl[32];
             for (int l = 0; l < 2 * L; ++l) wl[l] = lz.data();
             void *wo[1] = {o.data()};
-            run_stage(ctxs[g], wp, wbp, wi, 2, wl, k > 0 ? 1 : 0, 0, 1, wo, nullptr);
+            run_stage(ctxs[g], wp, wbp, wi, 2, wl, nullptr, k > 0 ? 1 : 0, 0, 1, wo, nullptr);
             // (b) the pinned-memory DMA path in both directions at the real frame size (its first use in a process
             // costs several ms): frame 0 up into a scratch buffer, and back down into the first result buffer
             void *scratch = nullptr;
@@ -838,7 +880,8 @@ public:
                     if (count == 0) return;
                     mid_ctx *ctx = ctxs[g];
                     float t[3] = {0, 0, 0};
-                    run_stage(ctx, p, bp, in.data(), n, layer_ptrs.data(), k, start, count, pin.outs.data() + start, t);
+                    run_stage(ctx, p, bp, in.data(), n, layer_ptrs.data(), motion_ptrs.empty() ? nullptr : motion_ptrs.data(), k, start, count,
+                              pin.outs.data() + start, t);
                     kern[g] = t[1]; copy[g] = t[2];
                 } catch (const std::exception &e) { errors[g] = e.what(); }
             });
@@ -851,8 +894,9 @@ public:
         std::string words = af.words;
         if (af.bilateral()) words += " r=" + std::to_string(opt.radius);
         if (use_layers && af.family != SEQ_BILATERAL) words += " + " + std::to_string(L) + " layers";
-        if (af.family == SEQ_ATROUS || af.family == SEQ_ATROUS_TEMPORAL || af.family == SEQ_ATROUS_VARIANCE) words += ", " + std::to_string(opt.passes) + " passes";
-        if (af.windowed()) words += (words.empty() ? "k=" : ", k=") + std::to_string(k);
+        if (af.family == SEQ_ATROUS || af.family == SEQ_ATROUS_TEMPORAL || af.family == SEQ_ATROUS_VARIANCE || recursive) words += ", " + std::to_string(opt.passes) + " passes";
+        if (recursive) words += ", feedback=" + std::to_string(opt.feedback) + ", warmup=" + std::to_string(opt.warmup);
+        else if (af.windowed()) words += (words.empty() ? "k=" : ", k=") + std::to_string(k);
         std::cout << "\t" << n << " frames, " << words
                   << ", " << G << " device(s): " << sec << " sec, "
                   << (double)n * w * h / 1e6 / sec << " Mpixel/s end to end (host frames in -> host frames out)\n";
@@ -965,6 +1009,15 @@ static void usage()
         "  --atrous-epsilon X        atrous-variance: added to X * sqrt(variance), so that a converged pixel (variance 0) still averages\n"
         "                            texels that differ by rounding alone (default 1e-3, for luminances of order 1; > 0)\n"
         "  --search LO,HI --patch LO,HI   half-open NLM ranges (default -7,7 and -3,3; 21x21/7x7 is -10,11 and -3,4)\n"
+        "  --alpha X                 atrous-recursive: floor of the colour blend factor, (0, 1] (default 0.2)\n"
+        "  --alpha-moments X         atrous-recursive: floor of the moments' blend factor, (0, 1] (default 0.2)\n"
+        "  --history-max N           atrous-recursive: cap of the per-pixel history length (default 32)\n"
+        "  --feedback 0|1            atrous-recursive: the next colour history is the accumulated colour (0) or the level after pass 0 (1, default)\n"
+        "  --warmup N                atrous-recursive: frames accumulated before a block's first output and not written (default 16)\n"
+        "  --motion-layer SUBSTR     atrous-recursive: the .exr render element of every frame whose file name contains SUBSTR holds the\n"
+        "                            motion in its R and G channels, in pixels (pixel p was at p + motion(p) in the previous frame); it is\n"
+        "                            taken out of the guide layers.  Without it motion is zero.  A .png, no match or several are refused\n"
+        "  --motion-scale SX,SY      atrous-recursive: factors on the motion's R and G (default 1,1)\n"
         "  --temporal-k K            multiframe: frames t-K..t+K of the sorted sequence instead of the reference's list\n"
         "  --animation               denoise EVERY sibling frame with temporal NLM (window +-K, default 2) instead of the mode list\n"
         "  --animation-filter F      animation mode: nlm (default: temporal NLM), or the bilateral of every frame -- bilateral\n"
@@ -1004,6 +1057,13 @@ static void usage()
         "                            over the frames t-K..t+K (K = --temporal-k, default 2; --passes, --sigma-layers,\n"
         "                            --atrous-sigma-lum, --atrous-epsilon; the layer rules of atrous, the frame blocks and halo of\n"
         "                            joint-temporal, not with --halo rccl), outputs output-animation-nonlinear-atrous-variance-*\n"
+        "                            or atrous-recursive: recursive temporal accumulation (a history of colour and luminance moments,\n"
+        "                            blended as lerp(history, frame, max(1/N, alpha))), then the variance-guided passes, frame after\n"
+        "                            frame (--alpha, --alpha-moments, --history-max, --feedback, --warmup, --motion-layer,\n"
+        "                            --motion-scale; --passes, --sigma-layers, --atrous-sigma-lum, --atrous-epsilon as atrous-variance;\n"
+        "                            it ignores --temporal-k; not with --halo rccl), outputs output-animation-nonlinear-atrous-recursive-*.\n"
+        "                            With --gpus N every frame block starts its history --warmup frames before its block: a sharded\n"
+        "                            run equals the unsharded one bit for bit only when the warm-up reaches frame 0\n"
         "  --gpus N                  animation mode: split the sequence into N frame blocks, one per device\n"
         "  --halo host|rccl          animation mode with --gpus N: 'host' (default) streams every block plus its K halo frames from host\n"
         "                            memory through the overlapped pipeline; 'rccl' keeps each block resident in its GPU's HBM and\n"
@@ -1066,6 +1126,21 @@ int main(int argc, char **argv)
         else if (a == "--atrous-sigma-color") opt.atrous_sigma_color = (float)atof(next());
         else if (a == "--atrous-sigma-lum") opt.atrous_sigma_lum = (float)atof(next());
         else if (a == "--atrous-epsilon") opt.atrous_epsilon = (float)atof(next());
+        else if (a == "--alpha") opt.alpha = (float)atof(next());
+        else if (a == "--alpha-moments") opt.alpha_moments = (float)atof(next());
+        else if (a == "--history-max") opt.history_max = (float)atof(next());
+        else if (a == "--feedback") {
+            opt.feedback = atoi(next());
+            if (opt.feedback != 0 && opt.feedback != 1) { std::cerr << "--feedback " << opt.feedback << " is neither 0 nor 1\n"; return EXIT_FAILURE; }
+        }
+        else if (a == "--warmup") {
+            opt.warmup = atoi(next());
+            if (opt.warmup < 0) { std::cerr << "--warmup " << opt.warmup << " is negative\n"; return EXIT_FAILURE; }
+        }
+        else if (a == "--motion-layer") opt.motion_layer = next();
+        else if (a == "--motion-scale") {
+            if (sscanf(next(), "%f,%f", &opt.motion_sx, &opt.motion_sy) != 2) { std::cerr << "--motion-scale needs sx,sy\n"; usage(); return EXIT_FAILURE; }
+        }
         else if (a == "--search") { if (!pair_arg(next(), opt.search_lo, opt.search_hi)) { usage(); return EXIT_FAILURE; } }
         else if (a == "--patch") { if (!pair_arg(next(), opt.patch_lo, opt.patch_hi)) { usage(); return EXIT_FAILURE; } }
         else if (a == "--temporal-k") opt.temporal_k = atoi(next());
@@ -1099,6 +1174,10 @@ int main(int argc, char **argv)
     }
     auto listed = [&](const char *m) { return ("," + opt.modes + ",").find(std::string(",") + m + ",") != std::string::npos; };
     auto want = [&](const char *m) { return opt.modes == "all" || listed(m); };
+    if (listed("atrous-recursive")) {
+        std::cerr << "--modes atrous-recursive: the recursion needs a sequence; it is an animation filter (--animation --animation-filter atrous-recursive)\n";
+        return EXIT_FAILURE;
+    }
 
     try {
         DenoiseApplication app{opt};

@@ -113,6 +113,12 @@ struct Stage {
     const char *marker;                       // the launch range, "nlm %d": profiles and the marker tests read these names
     size_t level_bytes = 0;                   // a stage that keeps levels between its passes (a-trous): bytes of one, and how many
     int n_levels = 0;                         // per kernel stream -- reserved in the context's cache (pipe.atrous) for both streams
+    // A recursive stage (mid_sequence_atrous_recursive): output t needs what output t-1 left on the device.
+    bool in_order = false;                    // every launch on ONE kernel stream, in output order (no alternation between two)
+    const void *const *host_motion = nullptr; // one float2 plane per frame, uploaded in the frame's upload interval into one more slot
+                                              // beside its layers: the launch finds it at lt[j * (n_layers + 1) + n_layers]
+    int skip = 0;                             // leading outputs that are computed into a device slot and neither stored nor downloaded
+                                              // (warm-up); host_out[0 .. skip) is not read
 };
 
 // Outputs [first, first+count) of an n-frame host sequence; frames outside that range are only
@@ -130,6 +136,10 @@ static int run_pipeline(mid_ctx *ctx, const Stage &st, const Launch &launch, con
     const size_t npix = (size_t)st.width * st.height;
     const size_t in_bytes = npix * fmt_bytes(st.format), layer_bytes = st.layer_bytes;
     const int n_layers = st.host_layers ? st.n_layers : 0;
+    const int n_side = n_layers + (st.host_motion ? 1 : 0);      // slots beside a frame: its layers and, last, its motion plane
+    const size_t motion_bytes = npix * 2 * sizeof(float);
+    const size_t side_bytes = st.host_motion && motion_bytes > layer_bytes ? motion_bytes : layer_bytes;
+    const int skip = st.skip;
     const size_t dl_bytes = npix * fmt_bytes(out_fmt);            // one output frame, as it is written and downloaded
     const int n_up = f_hi - f_lo + 1;
     // Outputs could be filtered in batches of B frames per launch.  Measured on MI355X (16 x 1080p, 21x21/7x7):
@@ -168,33 +178,34 @@ static int run_pipeline(mid_ctx *ctx, const Stage &st, const Launch &launch, con
     bool out_pinned = true;
     std::vector<char> bounced(count, 0);
     if (proven) {
-        for (int i = 0; i < count; ++i) { bounced[i] = !host_range_in_one_mapping(host_out[i], dl_bytes); out_pinned = out_pinned && !bounced[i]; }
+        for (int i = skip; i < count; ++i) { bounced[i] = !host_range_in_one_mapping(host_out[i], dl_bytes); out_pinned = out_pinned && !bounced[i]; }
     } else {
-        for (int i = 0; i < count; ++i) out_pinned = out_pinned && host_is_pinned(host_out[i], dl_bytes);
+        for (int i = skip; i < count; ++i) out_pinned = out_pinned && host_is_pinned(host_out[i], dl_bytes);
     }
     bool direct = out_fmt == MID_FMT_RGBA8 && out_pinned;
     if (proven) {                                 // (and aligned for the kernel's 4 B / 8 B stores)
         direct = out_fmt != MID_FMT_RGBA32F && out_pinned;
-        for (int i = 0; direct && i < count; ++i) direct = ((uintptr_t)host_out[i] & (fmt_bytes(out_fmt) - 1)) == 0;
+        for (int i = skip; direct && i < count; ++i) direct = ((uintptr_t)host_out[i] & (fmt_bytes(out_fmt) - 1)) == 0;
     }
     else if (out_fmt == MID_FMT_RGBA16F) {
         direct = true;
-        for (int i = 0; direct && i < count; ++i) direct = host_range_in_one_mapping(host_out[i], dl_bytes);
+        for (int i = skip; direct && i < count; ++i) direct = host_range_in_one_mapping(host_out[i], dl_bytes);
     }
-    for (int i = 0; direct && i < count; ++i) {
+    for (int i = skip; direct && i < count; ++i) {
         void *dp = nullptr;
         if (hipHostGetDevicePointer(&dp, host_out[i], 0) != hipSuccess || !dp) { (void)hipGetLastError(); direct = false; }
     }
     mid_pipe_set &dring = ctx->pipe.ring, &dout = ctx->pipe.out, &dlayers = ctx->pipe.layers;
     if (int rc = reserve(dring, ring, in_bytes)) return rc;
-    if (n_layers) { if (int rc = reserve(dlayers, (size_t)ring * n_layers, layer_bytes)) return rc; }
-    if (!direct) { if (int rc = reserve(dout, DEPTH * B, dl_bytes)) return rc; }
-    if (st.n_levels) { if (int rc = reserve(ctx->pipe.atrous, (size_t)(overlap ? 2 : 1) * st.n_levels, st.level_bytes)) return rc; }
+    if (n_side) { if (int rc = reserve(dlayers, (size_t)ring * n_side, side_bytes)) return rc; }
+    if (!direct || skip) { if (int rc = reserve(dout, DEPTH * B, dl_bytes)) return rc; }
+    // (one set per kernel stream in use: an in-order stage launches on ctx->compute alone)
+    if (st.n_levels) { if (int rc = reserve(ctx->pipe.atrous, (size_t)(overlap && !st.in_order ? 2 : 1) * st.n_levels, st.level_bytes)) return rc; }
     if (int rc = reserve_events(ctx->pipe, 2 * (size_t)n_up + 4 * (size_t)nb)) return rc;
     ctx->pipe.last = mid_pipe_last{};
     struct Events { hipEvent_t *ev; } up0{ctx->pipe.ev.data()}, up1{up0.ev + n_up}, c0{up1.ev + n_up}, c1{c0.ev + nb}, d0{c1.ev + nb}, d1{d0.ev + nb};
     auto slot = [&](int f) { return dring.p[(f - f_lo) % ring]; };
-    auto layer_slot = [&](int f, int l) { return dlayers.p[((f - f_lo) % ring) * n_layers + l]; };   // frame f's layer l
+    auto layer_slot = [&](int f, int l) { return dlayers.p[((f - f_lo) % ring) * n_side + l]; };   // frame f's layer l (l == n_layers: its motion plane)
 
     int next_upload = f_lo;
     auto upload = [&](int f) -> int {
@@ -216,6 +227,7 @@ static int run_pipeline(mid_ctx *ctx, const Stage &st, const Launch &launch, con
         if (int rc = copy_h2d(ctx, slot(f), host_frames[f], in_bytes, ctx->upload)) return rc;
         for (int l = 0; l < n_layers; ++l)      // (its guide layers ride in the same upload interval: they share the slot's lifetime)
             if (int rc = copy_h2d(ctx, layer_slot(f, l), st.host_layers[(size_t)f * n_layers + l], layer_bytes, ctx->upload)) return rc;
+        if (st.host_motion) { if (int rc = copy_h2d(ctx, layer_slot(f, n_layers), st.host_motion[f], motion_bytes, ctx->upload)) return rc; }
         MID_HIP(hipEventRecord(up1.ev[f - f_lo], ctx->upload));
         return MID_OK;
     };
@@ -230,7 +242,7 @@ static int run_pipeline(mid_ctx *ctx, const Stage &st, const Launch &launch, con
         Range r("download %d", b0);
         MID_HIP(hipStreamWaitEvent(ctx->download, c1.ev[bi], 0));
         MID_HIP(hipEventRecord(d0.ev[bi], ctx->download));
-        for (int i = 0; i < bn; ++i)
+        for (int i = 0; i < bn && bi >= skip; ++i)      // (a warm-up output stays in its slot: the events alone are recorded)
             if (int rc = copy_d2h(ctx, host_out[b0 - first + i], dout.p[(bi % DEPTH) * B + i], dl_bytes, ctx->download,
                                   bounced[b0 - first + i] != 0)) return rc;
         MID_HIP(hipEventRecord(d1.ev[bi], ctx->download));
@@ -294,7 +306,7 @@ static int run_pipeline(mid_ctx *ctx, const Stage &st, const Launch &launch, con
         // slots leave the last round a quarter full -- overlaps the head of the next instead of idling the CUs.
         // (measured: one kernel stream 2385, two 2575, three 1892, four 1652 Mpixel/s; giving the second stream a
         // lower or higher priority than the first: 2410-2430; splitting every download over two copy streams: 1860)
-        hipStream_t cs = overlap && (bi & 1) ? ctx->compute2 : ctx->compute;
+        hipStream_t cs = overlap && (bi & 1) && !st.in_order ? ctx->compute2 : ctx->compute;
         MID_HIP(hipStreamWaitEvent(cs, up1.ev[need - f_lo], 0));
         // Output slot bi % DEPTH was written by batch bi-DEPTH and is read only by download(bi-DEPTH), which
         // itself waited for c1[bi-DEPTH]: d1[bi-DEPTH] therefore orders both the writer and the only reader of
@@ -313,16 +325,16 @@ static int run_pipeline(mid_ctx *ctx, const Stage &st, const Launch &launch, con
         for (int f = lo; f <= need; ++f) tbl[f - lo] = slot(f);
         mid_pixel *o[kMaxFrames];
         for (int i = 0; i < bn; ++i) {
-            if (direct) MID_HIP(hipHostGetDevicePointer((void **)&o[i], host_out[b0 - first + i], 0));
+            if (direct && bi >= skip) MID_HIP(hipHostGetDevicePointer((void **)&o[i], host_out[b0 - first + i], 0));
             else o[i] = (mid_pixel *)dout.p[(bi % DEPTH) * B + i];
         }
         // the window's layers, frame-major like tbl: output b0 + i reads ring slots b0+i-k .. b0+i+k and the layers uploaded with them
         static_assert(B == 1, "one output per launch: its window is what nlm_layers_temporal_fits admitted");
         static_assert(kMaxLayers <= MID_NLM_LAYERS_TEMPORAL_MAX_POINTERS, "the k = 0 stages pass up to kMaxLayers layers unchecked by that rule");
         const uint32_t *lt[MID_NLM_LAYERS_TEMPORAL_MAX_POINTERS];
-        MID_REQUIRE((need - lo + 1) * n_layers <= MID_NLM_LAYERS_TEMPORAL_MAX_POINTERS, "%s: the window's layers exceed one launch", st.who);
+        MID_REQUIRE((need - lo + 1) * n_side <= MID_NLM_LAYERS_TEMPORAL_MAX_POINTERS, "%s: the window's layers exceed one launch", st.who);
         for (int f = lo; f <= need; ++f)
-            for (int l = 0; l < n_layers; ++l) lt[(f - lo) * n_layers + l] = (const uint32_t *)layer_slot(f, l);
+            for (int l = 0; l < n_side; ++l) lt[(f - lo) * n_side + l] = (const uint32_t *)layer_slot(f, l);
         {
             Range launch_range(st.marker, b0);
             MID_HIP(hipEventRecord(c0.ev[bi], cs));
@@ -333,7 +345,7 @@ static int run_pipeline(mid_ctx *ctx, const Stage &st, const Launch &launch, con
         while (next_upload <= ahead) { if (int rc = upload(next_upload++)) return rc; }
 
         if (direct) {
-            // nothing to download: the launch wrote the caller's buffer
+            // nothing to download: the launch wrote the caller's buffer (or, in a warm-up, a slot nobody reads)
         } else if (threaded) {
             { std::lock_guard<std::mutex> l(helper.mu); helper.issued = bi; }
             helper.cv.notify_all();
@@ -663,6 +675,98 @@ extern "C" int mid_sequence_atrous_variance(mid_ctx *ctx, const mid_atrous_varia
         return (int)MID_OK;
     };
     return run_pipeline(ctx, st, launch, host_frames, n_frames, k, first, count, host_out, out_format, overlap, timings_ms);
+}
+
+// Recursive temporal accumulation of an animation (section a4j): per frame t from s = max(0, first - warmup) on, IN ORDER on one
+// kernel stream, mid_atrous_moments at k = 0 -> Vs, mid_temporal_accumulate with the history frame t-1 left (none for frame s), then
+// mid_atrous_variance on the accumulated colour and variance.  feedback 0: the next colour history is the accumulated colour;
+// feedback 1: the level after pass 0, which is then run on its own into the history buffer and continued with first_pass = 1
+// (a4i's chain identity keeps the bits of the public calls).  Frames s .. first-1 are warm-up: computed, not stored.  The window
+// of the schedule is k = 1 -- frame t-1's layers must be resident -- and ONE block of the context's cache holds the two
+// histories (colour and state each), the accumulated colour, Vs, the blended variance, the variance after pass 0, and the levels.
+extern "C" int mid_sequence_atrous_recursive(mid_ctx *ctx, const mid_temporal_accum_params *ap, const mid_atrous_variance_params *vp,
+                                             const float *layer_sigma, const void *const *host_frames, int n_frames,
+                                             const void *const *host_layers, int n_layers, const void *const *host_motion, int feedback,
+                                             int warmup, int first, int count, void *const *host_out, int out_format, int overlap,
+                                             float *timings_ms)
+{
+    Bind b(ctx, nullptr);
+    if (b.rc) return b.rc;
+    const char *who = "sequence_atrous_recursive";
+    if (int rc = refuse_if_recording(ctx->compute, "mid_sequence_atrous_recursive (four streams, host-side waits)")) return rc;
+    if (int rc = temporal_accumulate_check(ap, who, layer_sigma, host_layers != nullptr, n_layers)) return rc;
+    if (int rc = atrous_variance_check(vp, who, layer_sigma, host_layers != nullptr, n_layers)) return rc;
+    MID_REQUIRE(vp->first_pass == 0, "%s: first_pass %d: the passes start on the accumulated colour (continue a filter with mid_atrous_variance)", who, vp->first_pass);
+    MID_REQUIRE(ap->width == vp->width && ap->height == vp->height && ap->format == vp->format,
+                "%s: the two parameter blocks disagree on size or format (%dx%d 0x%x against %dx%d 0x%x)", who, ap->width, ap->height, ap->format,
+                vp->width, vp->height, vp->format);
+    MID_REQUIRE(feedback == 0 || feedback == 1, "%s: feedback %d is neither 0 (the accumulated colour) nor 1 (the level after pass 0)", who, feedback);
+    MID_REQUIRE(warmup >= 0, "%s: warmup %d < 0", who, warmup);
+    const mid_atrous_moments_params mp{ap->width, ap->height, ap->format};
+    if (int rc = atrous_moments_check(&mp, who, layer_sigma, host_layers != nullptr, n_layers, 1, 0)) return rc;
+    if (int rc = check_sequence({who, "n_frames", true, true}, host_frames, n_frames, host_layers, n_layers, 0, first, count, host_out, out_format)) return rc;
+    const int s0 = first - warmup < 0 ? 0 : first - warmup, skip = first - s0;
+    {   // the warm-up frames, frame s0 - 1 (the schedule's window uploads it) and frame first + count, their layers and motion planes
+        const int lo = s0 - 1 < 0 ? 0 : s0 - 1, hi = first + count > n_frames - 1 ? n_frames - 1 : first + count;
+        std::vector<const void *> inputs;
+        for (int f = lo; f <= hi; ++f) {
+            MID_REQUIRE(host_frames[f], "%s: frame %d is NULL", who, f);
+            inputs.push_back(host_frames[f]);
+            for (int l = 0; l < n_layers; ++l) {
+                MID_REQUIRE(host_layers[(size_t)f * n_layers + l], "%s: layer %d of frame %d is NULL", who, l, f);
+                inputs.push_back(host_layers[(size_t)f * n_layers + l]);
+            }
+            if (host_motion) {
+                MID_REQUIRE(host_motion[f], "%s: the motion plane of frame %d is NULL", who, f);
+                inputs.push_back(host_motion[f]);
+            }
+        }
+        if (int rc = check_no_alias(who, "an input frame, layer or motion plane of this call", inputs.data(), (int)inputs.size(), (const void *const *)host_out, count)) return rc;
+    }
+    const size_t npix = (size_t)ap->width * ap->height;
+    const int gfmt = fmt_guide(ap->format);
+    const size_t plane = (npix * sizeof(float) + 15) & ~(size_t)15;       // one float plane, the next one 16-byte aligned
+    mid_atrous_variance_params fp = *vp;                    // the passes read RGBA32F levels, whatever the frames are
+    fp.format = MID_FMT_WITH_GUIDE(MID_FMT_RGBA32F, gfmt);
+    Stage st{who, ap->width, ap->height, fmt_frames(ap->format), npix * fmt_bytes(gfmt), host_layers, n_layers, true, "atrous recursive %d"};
+    st.level_bytes = npix * 16 * 7 + 5 * plane; st.n_levels = 1;
+    st.in_order = true; st.host_motion = host_motion; st.skip = skip;
+    const int n_side = n_layers + (host_motion ? 1 : 0);
+    int step = 0;                                           // frames accumulated so far: the launches come in output order
+    auto launch = [&](const void *const *tbl, int, const uint32_t *const *lt, int, int t0, int bn, void *const *out, int out_fmt, hipStream_t s) {
+        char *blk = (char *)ctx->pipe.atrous.p[0];
+        mid_pixel *hc[2] = {(mid_pixel *)blk, (mid_pixel *)(blk + npix * 16)}, *hs[2] = {(mid_pixel *)(blk + npix * 32), (mid_pixel *)(blk + npix * 48)};
+        mid_pixel *acc = (mid_pixel *)(blk + npix * 64);
+        void *level[2] = {blk + npix * 80, blk + npix * 96};
+        char *fb = blk + npix * 112;
+        float *vs = (float *)fb, *vt = (float *)(fb + plane), *v1 = (float *)(fb + 2 * plane);
+        float *vlevel[2] = {(float *)(fb + 3 * plane), (float *)(fb + 4 * plane)};
+        for (int i = 0; i < bn; ++i, ++step) {
+            const int t = t0 + i, cur = step & 1, prev = cur ^ 1;
+            const uint32_t *const *ly = lt + (size_t)t * n_side;
+            const uint32_t *const *pl = step ? lt + (size_t)(t - 1) * n_side : ly;
+            const float *mv = host_motion ? (const float *)ly[n_layers] : nullptr;
+            if (int rc = atrous_moments_out(ctx, &mp, layer_sigma, tbl + t, ly, n_layers, 1, 0, 0, vs, s)) return rc;
+            mid_pixel *col = feedback ? acc : hc[cur];
+            if (int rc = temporal_accumulate_out(ctx, ap, layer_sigma, tbl[t], ly, pl, n_layers, mv, step ? hc[prev] : nullptr, step ? hs[prev] : nullptr,
+                                                 vs, col, hs[cur], vt, s)) return rc;
+            if (!feedback) {
+                if (int rc = atrous_variance_out(ctx, &fp, layer_sigma, col, vt, ly, n_layers, out[i], out_fmt, nullptr, level, vlevel, s)) return rc;
+                continue;
+            }
+            mid_atrous_variance_params p0 = fp, p1 = fp;
+            p0.n_passes = 1;
+            p1.first_pass = 1; p1.n_passes = fp.n_passes - 1;
+            if (int rc = atrous_variance_out(ctx, &p0, layer_sigma, col, vt, ly, n_layers, hc[cur], MID_FMT_RGBA32F, v1, level, vlevel, s)) return rc;
+            if (p1.n_passes >= 1) {
+                if (int rc = atrous_variance_out(ctx, &p1, layer_sigma, hc[cur], v1, ly, n_layers, out[i], out_fmt, nullptr, level, vlevel, s)) return rc;
+            } else if (int rc = atrous_variance_out(ctx, &p0, layer_sigma, col, vt, ly, n_layers, out[i], out_fmt, nullptr, level, vlevel, s)) return rc;
+        }
+        return (int)MID_OK;
+    };
+    std::vector<void *> outs((size_t)skip + count, nullptr);
+    for (int i = 0; i < count; ++i) outs[(size_t)skip + i] = host_out[i];
+    return run_pipeline(ctx, st, launch, host_frames, n_frames, 1, s0, skip + count, outs.data(), out_format, overlap, timings_ms);
 }
 
 // Device timeline of the context's last mid_sequence_nlm*, mid_sequence_bilateral or mid_sequence_nlm_layers[_temporal] call, read back from the events the call left in the context's

@@ -752,6 +752,89 @@ int mid_sequence_atrous_variance(mid_ctx *ctx, const mid_atrous_variance_params 
                                  const void *const *host_frames, int n_frames, const void *const *host_layers, int n_layers,
                                  int k, int first, int count, void *const *host_out, int out_format, int overlap, float *timings_ms);
 
+/* ---- a4j: recursive temporal accumulation with motion vectors -----------------------------
+ * SVGF's temporal stage: a history of the colour and of the luminance moments that lives from frame to frame, reprojected by
+ * per-pixel motion vectors and blended with the new frame as lerp(history, frame, max(1 / N, alpha)) with a per-pixel history
+ * length N.  Where a window of 2k+1 frames (a4h, a4i) gives 2k+1 samples per pixel for a pass over 2k+1 frames, the recursion
+ * gives 1 / alpha samples for one frame's worth of traffic.  The policy of the other temporal forms is kept: the guide layers
+ * weigh every history tap softly, there is no disocclusion threshold.  Motion vectors are an OPTIONAL input: without them the
+ * reprojection is the identity and the layers alone reject what moved.
+ * Planes.  hist_color_in / color_out: RGBA32F.  hist_state_in / state_out: one float4 per pixel, (m1, m2, N, 0) -- the first and
+ * second moment of the luminance and the history length, one 16-byte load per reprojection tap.  motion: width * height float2,
+ * 8-byte aligned, in pixels: pixel p of this frame was at p + motion(p) in the previous frame; NULL = zero motion.  var_spatial,
+ * var_out: a4i's float planes (var_spatial is mid_atrous_moments at k = 0 of this frame, or NULL; var_out may be NULL).  cur is
+ * widened as in a4i and l() is a4i's luminance; cur_layers are this frame's guide layers, prev_layers those of the frame the
+ * history belongs to (both tables are required with n_layers > 0, also where there is no history).
+ * Per pixel p = (x, y), C = cur(p) widened, l = l(C), Hc / Hs the history colour / state, Vs = var_spatial(p):
+ *   1. previous position: ppx = (float)x + mx (one fp32 add), x0 = floorf(ppx), fx = ppx - x0 (exact); likewise y.
+ *   2. taps are taken only if ppx > -1 && ppx < width && ppy > -1 && ppy < height, compared in fp32 BEFORE any float -> int
+ *      conversion: false for NaN and +-Inf, and such a pixel has no history.  motion == NULL: pp = p exactly.
+ *   3. the four taps q = (x0 + a, y0 + b) in the order b = 0, 1, inside it a = 0, 1; bw = (a ? fx : 1 - fx) * (b ? fy : 1 - fy).
+ *      A tap outside the image or with bw == 0 is SKIPPED -- not read: integer motion reads one texel, nothing leaks in from
+ *      beyond the frame.  For the others: arg = a4g's layer chain from 0 between cur_layers[l](p) and prev_layers[l](q), same
+ *      sc_l;  w = bw * 2^arg;  S += w;  hc = fma(Hc(q), w, hc) (four channels);  h1 = fma(Hs(q).x, w, h1),
+ *      h2 = fma(Hs(q).y, w, h2), hn = fma(Hs(q).z, w, hn).
+ *   4. S > 0: hc /= S, h1 /= S, h2 /= S (IEEE divisions); otherwise all are 0 (this includes a call without history).
+ *   5. N' = fminf(historyMax, hn + 1.0f): hn is the UNNORMALISED sum (sum bw <= 1 and every 2^arg <= 1), so a history that is
+ *      only half believed counts half and N' falls to 1 continuously as S -> 0.
+ *   6. a = fmaxf(1.0f / N', alpha);  color_out = fma(a, C - hc, hc) per channel.
+ *   7. am = fmaxf(1.0f / N', alphaMoments);  m1' = fma(am, l - h1, h1);  m2' = fma(am, l * l - h2, h2);
+ *      state_out = (m1', m2', N', 0).
+ *   8. v = fma(-m1', m1', m2');  Vt = v < 0 ? 0 : v (a NaN stays).  With var_spatial: tt = fminf(1, (N' - 1) / (historyFull - 1)),
+ *      var_out = fma(tt, Vt - Vs, Vs) -- SVGF's "spatial estimate while the history is short", made continuous; else var_out = Vt.
+ * Out of scope: SVGF's 3 x 3 search when the bilinear taps fail, mesh ids, and a temporal falloff of the weights.
+ * The tap geometry (steps 1 - 3 up to bw and the skip rule) is one host / device function, csrc/reproject_taps.hpp, which
+ * tools/reproject_taps_sanitize.cpp sweeps on the CPU under sanitizers.
+ * Precision: colour, m1, m2 within 1e-5 * max(1, |ref|), N' within 1e-5 * max(1, N'), the variance within 1e-5 * max(1, m2_ref)
+ * of the formula in float64 with steps 1 - 2 taken in fp32 (both terms of v carry the rounding of a value of that size).  Bit
+ * identities: no history gives the widened cur, the state (l, l * l, 1, 0) and var_out == var_spatial; motion == NULL is an
+ * all-zero motion plane; a u8 / f16 frame gives the bits of the float frame it widens to; appended all-zero layers leave the bits.
+ * Class: one kernel, one pixel per lane, 64 x 4 pixels per workgroup of four waves, no LDS (the tap addresses depend on the
+ * data; motion is locally coherent, so neighbouring lanes' taps share cache lines), no scratch memory, no register array indexed
+ * by a run-time value; the layer loop is wave-uniform; 2 n_layers + 8 pointers by value.
+ * MID_ERR_INVALID before anything is queued, the outputs untouched: NULL cur, color_out or state_out; exactly one of the two
+ * history inputs NULL; n_layers outside 0..16; with layers a NULL table, a NULL entry, or a sigma that is not finite and > 0;
+ * alpha or alphaMoments outside (0, 1] or not finite; historyMax < 1 or not finite; historyFull <= 1 or not finite; an unknown
+ * frame or guide format; the alignment rules of a4e (motion: 8 bytes; histories, states and variance planes: 16 bytes); any
+ * output overlapping any input or another output (color_out may not be hist_color_in: the gather reads neighbours); width or
+ * height < 1, or 2^30 pixels and more. */
+typedef struct mid_temporal_accum_params {
+    int32_t width, height;
+    float   alpha;          /* floor of the colour blend factor, (0, 1]; SVGF 0.2 */
+    float   alphaMoments;   /* floor of the moments' blend factor, (0, 1]; SVGF 0.2 */
+    float   historyMax;     /* cap of the history length N, >= 1, finite; default 32 */
+    float   historyFull;    /* N from which the temporal variance is used alone, > 1, finite; SVGF 4 */
+    int32_t format;         /* MID_FMT_* of `cur`, guide format through MID_FMT_WITH_GUIDE as in a4e */
+} mid_temporal_accum_params;
+int mid_temporal_accumulate(mid_ctx *ctx, const mid_temporal_accum_params *p, const float *layer_sigma /* n_layers host floats */,
+                            const void *cur, const uint32_t *const *cur_layers, const uint32_t *const *prev_layers, int n_layers /* 0..16 */,
+                            const float *motion /* width*height float2, or NULL = zero motion */,
+                            const mid_pixel *hist_color_in, const mid_pixel *hist_state_in /* both NULL: no history */,
+                            const float *var_spatial /* float plane or NULL */,
+                            mid_pixel *color_out, mid_pixel *state_out, float *var_out /* or NULL */, void *stream);
+/* An animation through the frame pipeline (section a8) with the recursion as its compute stage.  For t from s = max(0, first -
+ * warmup) on, in order: (1) Vs = mid_atrous_moments at k = 0 on frame t with its layers; (2) mid_temporal_accumulate with cur = t,
+ * the layers of t and of t-1, host_motion[t], the history frame t-1 left and Vs -- frame s has no history; (3) mid_atrous_variance
+ * (vp, first_pass 0) on the accumulated colour and var_out with frame t's layers.  feedback 0: the colour history of frame t+1 is
+ * the accumulated colour.  feedback 1 (SVGF's choice): it is the level after pass 0 -- pass 0 is run on its own into the next
+ * history buffer and passes 1.. continue from it with first_pass = 1, which is a4i's chain identity, so the bits stay those of the
+ * public calls.  Frames s .. first-1 are warm-up: computed, neither stored nor downloaded; host_out has `count` entries.  Output t
+ * has, bit for bit, the result of that chain of public calls started at frame s -- so a call with first > 0 (a frame block of a
+ * sharded run) equals the whole run bit for bit only when warmup reaches frame 0.
+ * host_motion: n_frames planes of width * height float2 (as in mid_temporal_accumulate), or NULL: zero motion; a plane rides in
+ * its frame's upload interval.  ap and vp must agree on width, height and format.  The launches of consecutive frames run IN
+ * ORDER on one kernel stream (the other stages alternate between two); uploads and downloads overlap them as elsewhere.  The two
+ * histories (ping-pong), Vs, var_out and the levels live in the context's cache and go with mid_ctx_release_cached.
+ * MID_ERR_INVALID before anything is queued, host_out and timings_ms untouched: the refusals of the three calls and of the other
+ * sequence entry points; vp->first_pass != 0; feedback outside {0, 1}; warmup < 0; a NULL frame, layer or motion plane among the
+ * frames max(0, s-1) .. min(n_frames-1, first+count); an output that is one of those. */
+int mid_sequence_atrous_recursive(mid_ctx *ctx, const mid_temporal_accum_params *ap, const mid_atrous_variance_params *vp,
+                                  const float *layer_sigma, const void *const *host_frames, int n_frames,
+                                  const void *const *host_layers, int n_layers /* 1..16 */,
+                                  const void *const *host_motion /* n_frames float2 planes, or NULL */, int feedback /* 0 | 1 */,
+                                  int warmup /* >= 0 */, int first, int count, void *const *host_out, int out_format, int overlap,
+                                  float *timings_ms);
+
 /* ---- a5: normalize ----------------------------------------------------------------------
  * One dispatch of shaders/normalize.comp (RecordCommandsOfExecuteAndTransfer(normKernel=true)):
  * out = weightColor / normWeight, or (1,0,1,1) where normWeight == 0; bindings {0: out; 1: W}. */
