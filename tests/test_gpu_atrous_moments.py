@@ -100,6 +100,21 @@ def test_a_nan_stays_a_nan(ctx):
     got = ctx.atrous_moments(bad, ly, avi.sigmas_of(2), k=0, t=1)
     ref, _ = chk.moments(bad, ly, avi.sigmas_of(2), k=0, t=1)
     assert np.array_equal(np.isnan(got), np.isnan(ref)) and np.isnan(got).sum() == 49
+    # the global class, and an Inf texel in both: d = Inf at the 49 pixels that see it, m = Inf and v = Inf - Inf, a NaN, in fp32
+    # (whether w d is Inf or, with a weight flushed to 0, NaN) as in float64; nothing is Inf in the output and nothing else is touched
+    for L in (2, 5):
+        fr, ly = inputs(shape, L, np.float32, np.float32)
+        for val, ch in ((np.nan, 1), (np.inf, 0), (-np.inf, 2)):
+            if L == 2 and np.isnan(val):
+                continue                                            # (the case above)
+            bad = [f.copy() for f in fr]
+            bad[1][8, 30, ch] = val
+            for k, t in ((0, 1), (1, 2)):
+                got = ctx.atrous_moments(bad, ly, avi.sigmas_of(L), k=k, t=t)
+                ref, m2 = chk.moments(bad, ly, avi.sigmas_of(L), k=k, t=t)
+                assert np.array_equal(np.isnan(got), np.isnan(ref)) and np.isnan(got).sum() == 49 and not np.isinf(got).any(), (L, val, k, t)
+                ok = ~np.isnan(ref)
+                assert np.all(np.abs(got[ok].astype(np.float64) - ref[ok]) <= TOL * np.maximum(1.0, m2[ok])), (L, val, k, t)
 
 
 def test_every_refusal_leaves_the_output_alone(ctx):

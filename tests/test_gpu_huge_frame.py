@@ -8,7 +8,10 @@ both addressings (the linear one wraps rows, bialteral_linear.comp:58), the fuse
 window, mid_nlm_accum into the 8.6 GB weight buffer + mid_normalize, and pack/unpack over the whole buffer; layer-guided NLM
 (mid_nlm_layers fused on the strip and the per-pixel kernel, mid_nlm_layers_accum + mid_normalize, mid_nlm_layers_temporal and its
 chain of mid_nlm_layers_pair_accum dispatches) with RGBA8 guides built on the device, against the float64 checkers on crops;
-joint layer-guided NLM (mid_nlm_joint) with two guides on its 32-row tiles, into an output that holds NaN before the call.
+joint layer-guided NLM (mid_nlm_joint) with two guides on its 32-row tiles, into an output that holds NaN before the call;
+the variance-guided a-trous filter (mid_atrous_moments in its tiled and its global class, one pass of mid_atrous_variance on the
+16-row comb, the 8-row comb at step 32 and the global taps at step 128) and mid_temporal_accumulate with a motion field, each
+into outputs that hold NaN before the call, against the float64 checkers on crops cut at the frame's edge.
 """
 import ctypes
 
@@ -17,12 +20,15 @@ import pytest
 import torch
 
 import image_denoising_filter_amd as mid
+import np_atrous_variance
 import np_nlm_joint
 import np_nlm_layers
 import np_nlm_layers_temporal
+import np_temporal_accumulate
 import oracle
 from conftest import rel_err
 from test_gpu_nlm_layers import TOL
+from test_gpu_temporal_accumulate import errors as accumulate_errors
 
 pytestmark = pytest.mark.gpu
 H, W = 16400, 16400
@@ -283,4 +289,179 @@ def test_nlm_joint_strip_kernel_beyond_4_gib(ctx, huge, ts):
     print(f"16400 x 16400, joint NLM, two guides, h = {hs}, 21x21 / 7x7 (32-row strip kernel): worst rel err over the windows {worst:.2e}")
     assert not torch.isnan(out).any(), "every tile was dealt"
     del out, gl
+    torch.cuda.empty_cache()
+
+
+# ---- the variance-guided a-trous filter and the temporal accumulation: (size_t)y * w + x in five more kernels --------------------
+# These filters SKIP a tap outside the image, they do not read zeros there: a crop is cut at the frame's edge, not zero-padded, so
+# that the crop's edge is the frame's edge exactly where the window touches it.  Only the window's pixels are compared.
+A_TOL = 1e-5
+
+
+def _cut(t_dev, y0, x0, halo):
+    """(window + halo cut at the frame's edge as a host array, the window inside it)."""
+    ya, xa = max(0, y0 - halo), max(0, x0 - halo)
+    crop = t_dev[ya:min(H, y0 + SIZE + halo), xa:min(W, x0 + SIZE + halo)].cpu().numpy()
+    return crop, (slice(y0 - ya, y0 - ya + SIZE), slice(x0 - xa, x0 - xa + SIZE))
+
+
+def _moved(a, b):
+    """The share of pixels at which a and b differ by more than 1e-3 (in any channel)."""
+    d = np.abs(np.asarray(a, np.float64) - np.asarray(b, np.float64))
+    return float((d.reshape(d.shape[0], d.shape[1], -1).max(-1) > 1e-3).mean())
+
+
+def _nan_like(ts, ref, shape=None):
+    with torch.cuda.stream(ts):
+        return torch.full(ref.shape if shape is None else shape, float("nan"), device=ref.device, dtype=torch.float32)
+
+
+def _plane(ts, seed, lo, hi):
+    """A float plane of values in [lo, hi) on the device."""
+    dev = torch.device("cuda", 0)
+    with torch.cuda.stream(ts):
+        v = torch.rand((H, W), device=dev, generator=torch.Generator(device=dev).manual_seed(seed), dtype=torch.float32)
+        v.mul_(hi - lo).add_(lo)
+    ts.synchronize()
+    return v
+
+
+def _moments_beyond_4_gib(ctx, huge, ts, sigmas):
+    """mid_atrous_moments at k = 0 with len(sigmas) guides; the conditions on the guides by the checker alone: the estimate is
+    above 1e-3 (what the centre tap alone gives is 0) and moves by more than 1e-3 when the guides are ignored, on half a window."""
+    L, halo = len(sigmas), 3
+    gl = [_guide(ts, i, 101 + i) for i in range(L)]
+    var = _nan_like(ts, huge, (H, W))
+    p = mid.AtrousMomentsParams(W, H, mid.api.fmt_with_guide(mid.FMT_RGBA32F, mid.FMT_RGBA8))
+    assert mid.lib.mid_atrous_moments(ctx.handle, ctypes.byref(p), (ctypes.c_float * 16)(*sigmas), (ctypes.c_void_p * 1)(huge.data_ptr()),
+                                      (ctypes.c_void_p * L)(*[g.data_ptr() for g in gl]), L, 1, 0, 0, var.data_ptr(), ts.cuda_stream) == 0, mid.lib.mid_last_error()
+    torch.cuda.synchronize()
+    worst = 0.0
+    for y0, x0 in WINDOWS:
+        c, win = _cut(huge, y0, x0, halo)
+        gc = [_cut(g, y0, x0, halo)[0] for g in gl]
+        ref, m2 = np_atrous_variance.moments([c], [gc], sigmas, k=0, t=0)
+        flat, _ = np_atrous_variance.moments([c], [gc], [1000.0 * s for s in sigmas], k=0, t=0)
+        assert (ref[win] > 1e-3).mean() >= 0.5 and _moved(ref[win], flat[win]) >= 0.5, (y0, x0, "the guides must matter")
+        e = float(np.max(np.abs(var[y0:y0 + SIZE, x0:x0 + SIZE].cpu().numpy().astype(np.float64) - ref[win]) / np.maximum(1.0, m2[win])))
+        worst = max(worst, e)
+        assert e <= A_TOL, (y0, x0, e)
+    assert not torch.isnan(var).any(), "every pixel was written"
+    del var, gl
+    torch.cuda.empty_cache()
+    return worst
+
+
+def test_atrous_moments_tiled_class_beyond_4_gib(ctx, huge, ts):
+    e = _moments_beyond_4_gib(ctx, huge, ts, [0.012, 0.02])
+    print(f"16400 x 16400, moments, two guides (64 x 16 LDS tiles): worst error over the windows {e:.2e}")
+
+
+def test_atrous_moments_global_class_beyond_4_gib(ctx, huge, ts):
+    e = _moments_beyond_4_gib(ctx, huge, ts, [0.02, 0.03, 0.025, 0.04, 0.03])
+    print(f"16400 x 16400, moments, five guides (global taps): worst error over the windows {e:.2e}")
+
+
+def _variance_pass_beyond_4_gib(ctx, huge, ts, gl, var_in, out, var_out, first, sigmas):
+    """One pass of mid_atrous_variance at step 2^first; returns the worst (colour, variance) error over the windows."""
+    halo = 2 * 2 ** first + 1                              # two taps of the step, and one texel for vt
+    with torch.cuda.stream(ts):
+        out.fill_(float("nan"))
+        var_out.fill_(float("nan"))
+    sl, eps = 4.0, 1e-3
+    p = mid.AtrousVarianceParams(W, H, first, 1, sl, eps, mid.api.fmt_with_guide(mid.FMT_RGBA32F, mid.FMT_RGBA8))
+    assert mid.lib.mid_atrous_variance(ctx.handle, ctypes.byref(p), (ctypes.c_float * 16)(*sigmas), huge.data_ptr(), var_in.data_ptr(),
+                                       (ctypes.c_void_p * 2)(*[g.data_ptr() for g in gl]), 2, out.data_ptr(), mid.FMT_RGBA32F, var_out.data_ptr(),
+                                       None, ts.cuda_stream) == 0, mid.lib.mid_last_error()
+    torch.cuda.synchronize()
+    worst = (0.0, 0.0)
+    for y0, x0 in WINDOWS:
+        c, win = _cut(huge, y0, x0, halo)
+        vc = _cut(var_in, y0, x0, halo)[0]
+        gc = [_cut(g, y0, x0, halo)[0] for g in gl]
+        kw = dict(passes=1, first_pass=first, sigma_lum=sl, epsilon=eps)
+        refC, refV = np_atrous_variance.atrous_variance(c, vc, gc, sigmas, **kw)
+        flatC, _ = np_atrous_variance.atrous_variance(c, vc, gc, [1000.0 * s for s in sigmas], **kw)
+        assert _moved(refC[win], c[win]) >= 0.5 and _moved(refC[win], flatC[win]) >= 0.5, (first, y0, x0, "the guides must matter")
+        ec = rel_err(_window(out, y0, x0), refC[win])
+        ev = float(np.max(np.abs(var_out[y0:y0 + SIZE, x0:x0 + SIZE].cpu().numpy().astype(np.float64) - refV[win])) / max(1.0, refV[win].max()))
+        worst = (max(worst[0], ec), max(worst[1], ev))
+        assert ec <= A_TOL and ev <= A_TOL, (first, y0, x0, ec, ev)
+    assert not torch.isnan(out).any() and not torch.isnan(var_out).any(), "every pixel was written"
+    return worst
+
+
+def _variance_buffers(ts, huge):
+    gl = [_guide(ts, i, 111 + i) for i in range(2)]
+    # vt near 0 would make the luminance scale log2(e) / epsilon, where fp32 luminance rounding alone moves the weights (the
+    # header's epsilon paragraph): the variance stays in [0.05, 0.5)
+    return gl, _plane(ts, 113, 0.05, 0.5), torch.empty_like(huge), torch.empty((H, W), device=huge.device, dtype=torch.float32)
+
+
+def test_atrous_variance_comb_beyond_4_gib(ctx, huge, ts):
+    # step 1: two rows per wave, 16-row chunks; step 32: one row per wave, 8-row chunks, 32 residue classes of 513 rows
+    gl, var_in, out, var_out = _variance_buffers(ts, huge)
+    for first, sigmas in ((0, [0.03, 0.05]), (5, [0.4, 0.6])):
+        ec, ev = _variance_pass_beyond_4_gib(ctx, huge, ts, gl, var_in, out, var_out, first, sigmas)
+        print(f"16400 x 16400, variance-guided pass at step {2 ** first} (row comb), two guides: worst colour {ec:.2e}, variance {ev:.2e}")
+    del gl, var_in, out, var_out
+    torch.cuda.empty_cache()
+
+
+def test_atrous_variance_global_taps_beyond_4_gib(ctx, huge, ts):
+    gl, var_in, out, var_out = _variance_buffers(ts, huge)
+    ec, ev = _variance_pass_beyond_4_gib(ctx, huge, ts, gl, var_in, out, var_out, 7, [0.4, 0.6])
+    print(f"16400 x 16400, variance-guided pass at step 128 (global taps), two guides: worst colour {ec:.2e}, variance {ev:.2e}")
+    del gl, var_in, out, var_out
+    torch.cuda.empty_cache()
+
+
+def test_temporal_accumulate_beyond_4_gib(ctx, huge, ts):
+    # The gather reads two 4.3 GB history planes at addresses the motion field decides.  The motion is smooth, bounded by 6 texels
+    # and a multiple of 1 / 256: x + mx is then exact in fp32 at x = 16399 as at the x of a crop, so that the checker on a crop
+    # takes the taps and the fractions of the kernel on the frame.  Along the edges it points off the frame.
+    halo, sigmas = 8, [0.1, 0.15]
+    dev, s = huge.device, ts.cuda_stream
+    cur_l = [_guide(ts, i, 121 + i) for i in range(2)]
+    prev_l = [_guide(ts, i, 123 + i) for i in range(2)]        # one scene, the guides a few codes apart from frame to frame
+    with torch.cuda.stream(ts):
+        gen = torch.Generator(device=dev).manual_seed(125)
+        hist_c = torch.rand((H, W, 4), device=dev, generator=gen, dtype=torch.float32)
+        hist_s = torch.rand((H, W, 4), device=dev, generator=gen, dtype=torch.float32)
+        hist_s[..., 1] += hist_s[..., 0] ** 2                  # m2 >= m1^2
+        hist_s[..., 2] = hist_s[..., 2] * 39.0 + 1.0           # N in [1, 40): beyond historyMax = 32 in places
+        hist_s[..., 3] = 0.0
+        yy = torch.arange(H, device=dev, dtype=torch.float32)[:, None]
+        xx = torch.arange(W, device=dev, dtype=torch.float32)[None, :]
+        motion = torch.empty((H, W, 2), device=dev, dtype=torch.float32)
+        motion[..., 0] = torch.round(1536.0 * torch.sin(0.01 * xx + 0.003 * yy + 0.5)) / 256.0
+        motion[..., 1] = torch.round(1536.0 * torch.cos(0.008 * yy - 0.002 * xx + 6.0)) / 256.0
+    ts.synchronize()
+    assert float(motion.abs().max()) <= 6.0
+    var_s = _plane(ts, 126, 0.05, 0.5)
+    col, st, var = _nan_like(ts, huge), _nan_like(ts, huge), _nan_like(ts, huge, (H, W))
+    p = mid.TemporalAccumParams(W, H, 0.2, 0.2, 32.0, 4.0, mid.api.fmt_with_guide(mid.FMT_RGBA32F, mid.FMT_RGBA8))
+    assert mid.lib.mid_temporal_accumulate(ctx.handle, ctypes.byref(p), (ctypes.c_float * 16)(*sigmas), huge.data_ptr(),
+                                           (ctypes.c_void_p * 2)(*[g.data_ptr() for g in cur_l]), (ctypes.c_void_p * 2)(*[g.data_ptr() for g in prev_l]), 2,
+                                           motion.data_ptr(), hist_c.data_ptr(), hist_s.data_ptr(), var_s.data_ptr(),
+                                           col.data_ptr(), st.data_ptr(), var.data_ptr(), s) == 0, mid.lib.mid_last_error()
+    torch.cuda.synchronize()
+    worst, off_frame = {}, 0
+    for y0, x0 in WINDOWS:
+        c, win = _cut(huge, y0, x0, halo)
+        cut = lambda t: _cut(t, y0, x0, halo)[0]
+        args = (c, [cut(g) for g in cur_l], [cut(g) for g in prev_l])
+        kw = dict(hist=(cut(hist_c), cut(hist_s)), motion=cut(motion), var_spatial=cut(var_s), alpha=0.2, alpha_moments=0.2, history_max=32, history_full=4)
+        ref = np_temporal_accumulate.temporal_accumulate(*args, sigmas, **kw)
+        flat = np_temporal_accumulate.temporal_accumulate(*args, [1000.0 * x for x in sigmas], **kw)
+        assert _moved(ref["colour"][win], c[win]) >= 0.5 and _moved(ref["colour"][win], flat["colour"][win]) >= 0.5, (y0, x0, "the guides must matter")
+        off_frame += int((ref["S"][win] == 0).sum())
+        e = accumulate_errors((_window(col, y0, x0), _window(st, y0, x0), var[y0:y0 + SIZE, x0:x0 + SIZE].cpu().numpy()),
+                              {k: v[win] for k, v in ref.items()})
+        worst = {k: max(v, worst.get(k, 0.0)) for k, v in e.items()}
+        assert max(e.values()) <= A_TOL, (y0, x0, e)
+    assert off_frame > 0, "some window pixels have their history off the frame"
+    print("16400 x 16400, temporal accumulation, two guides, motion up to 6 texels: worst over the windows " + ", ".join(f"{k} {v:.2e}" for k, v in worst.items()))
+    assert not torch.isnan(col).any() and not torch.isnan(st).any() and not torch.isnan(var).any(), "every pixel was written"
+    del col, st, var, var_s, motion, hist_c, hist_s, cur_l, prev_l
     torch.cuda.empty_cache()
