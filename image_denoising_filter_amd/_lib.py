@@ -69,6 +69,11 @@ class TemporalAccumParams(ctypes.Structure):
                 ("historyMax", ctypes.c_float), ("historyFull", ctypes.c_float), ("format", ctypes.c_int32)]
 
 
+class AlbedoParams(ctypes.Structure):
+    """mid_albedo_params (section a4k)."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("floor", ctypes.c_float), ("format", ctypes.c_int32)]
+
+
 class NormalizeParams(ctypes.Structure):
     _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32)]
 
@@ -145,6 +150,12 @@ _SIGNATURES = {
                                                      ctypes.POINTER(ctypes.c_float), c_void_pp, ctypes.c_int, c_void_pp, ctypes.c_int, c_void_pp,
                                                      ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_pp, ctypes.c_int, ctypes.c_int,
                                                      ctypes.POINTER(ctypes.c_float)]),
+    "mid_demodulate": (ctypes.c_int, [_P, ctypes.POINTER(AlbedoParams), _P, _P, _P, _P]),
+    "mid_modulate": (ctypes.c_int, [_P, ctypes.POINTER(AlbedoParams), _P, _P, _P, ctypes.c_int, _P]),
+    "mid_sequence_atrous_recursive_albedo": (ctypes.c_int, [_P, ctypes.POINTER(TemporalAccumParams), ctypes.POINTER(AtrousVarianceParams),
+                                                            ctypes.POINTER(ctypes.c_float), c_void_pp, ctypes.c_int, c_void_pp, ctypes.c_int, c_void_pp,
+                                                            c_void_pp, ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_pp,
+                                                            ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
     "mid_normalize": (ctypes.c_int, [_P, ctypes.POINTER(NormalizeParams), _P, _P, _P]),
     "mid_unpack_u8": (ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_int, _P, _P]),
     "mid_pack_u8": (ctypes.c_int, [_P, _P, ctypes.c_size_t, _P, _P]),

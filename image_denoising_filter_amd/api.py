@@ -15,7 +15,7 @@ import weakref
 
 import numpy as np
 
-from ._lib import AtrousMomentsParams, AtrousParams, AtrousVarianceParams, BilateralParams, Image, NlmParams, NormalizeParams, TemporalAccumParams, c_void_pp, lib
+from ._lib import AlbedoParams, AtrousMomentsParams, AtrousParams, AtrousVarianceParams, BilateralParams, Image, NlmParams, NormalizeParams, TemporalAccumParams, c_void_pp, lib
 
 FMT_RGBA32F, FMT_RGBA8, FMT_RGBA16F = 0, 1, 2
 
@@ -590,6 +590,37 @@ class Context:
                                            d_col.ptr, d_st.ptr, d_var.ptr, None), "mid_temporal_accumulate")
         return self.download(d_col, (h, w, 4), np.float32), self.download(d_st, (h, w, 4), np.float32), self.download(d_var, (h, w), np.float32)
 
+    def _albedo_plane(self, albedo, shape, who):
+        albedo = _img(albedo)
+        if albedo.dtype not in [np.dtype(d) for d in _GUIDE_DTYPES] or albedo.shape != shape:
+            raise ValueError(f"{who}: the albedo must be uint8 / float16 / float32 {shape}, got {albedo.dtype} {albedo.shape}")
+        return albedo
+
+    def demodulate(self, frame, albedo, floor=1e-3):
+        """Illumination of a frame (mid_demodulate): RGB divided by max(albedo, floor), alpha unchanged.  frame: (h, w, 4) uint8,
+        float16 or float32; albedo: (h, w, 4) uint8, float16 or float32, read as a guide layer is.  Returns float32 (h, w, 4)."""
+        (frame,) = _same_frames([frame], "demodulate")
+        h, w = frame.shape[:2]
+        albedo = self._albedo_plane(albedo, (h, w, 4), "demodulate")
+        p = AlbedoParams(w, h, floor, fmt_with_guide(_fmt_of(frame), _fmt_of(albedo)))
+        d_in, d_a, d_out = self.upload(frame), self.upload(albedo), self.alloc(w * h * 16)
+        _check(lib.mid_demodulate(self.handle, ctypes.byref(p), d_in.ptr, d_a.ptr, d_out.ptr, None), "mid_demodulate")
+        return self.download(d_out, (h, w, 4), np.float32)
+
+    def modulate(self, illum, albedo, floor=1e-3, out_dtype=None):
+        """The colour of an illumination plane (mid_modulate): RGB times max(albedo, floor), alpha unchanged, in out_dtype (None =
+        float32; uint8 and float16 with the rounding of pack_u8 / pack_f16).  illum: float32 (h, w, 4); albedo as for demodulate."""
+        illum = _img(illum)
+        if illum.dtype != np.float32:
+            raise TypeError(f"modulate: the illumination must be float32, got {illum.dtype}")
+        h, w = illum.shape[:2]
+        albedo = self._albedo_plane(albedo, (h, w, 4), "modulate")
+        out_dtype = _out_dtype(False, out_dtype)
+        p = AlbedoParams(w, h, floor, fmt_with_guide(FMT_RGBA32F, _fmt_of(albedo)))
+        d_in, d_a, d_out = self.upload(illum), self.upload(albedo), self.alloc(w * h * 4 * out_dtype.itemsize)
+        _check(lib.mid_modulate(self.handle, ctypes.byref(p), d_in.ptr, d_a.ptr, d_out.ptr, _OUT_FMT[out_dtype], None), "mid_modulate")
+        return self.download(d_out, (h, w, 4), out_dtype)
+
     def normalize(self, W):
         """normalize.comp."""
         W = np.ascontiguousarray(W, dtype=np.float32)
@@ -930,9 +961,10 @@ class Context:
 
     def sequence_atrous_recursive_pinned(self, hin, hout, w, h, fmt, hlayers, n_layers, sigmas, hmotion=None, feedback=1, warmup=16, first=0,
                                          count=None, passes=5, sigma_lum=4.0, epsilon=1e-3, alpha=0.2, alpha_moments=0.2, history_max=32,
-                                         history_full=4, overlap=True, out_dtype=None):
-        """mid_sequence_atrous_recursive on host pointers the caller already holds: nothing but the C call.  hin, hlayers, hout as
-        for sequence_atrous_variance_pinned; hmotion: one pointer per frame to a float32 (h, w, 2) plane, or None: zero motion.
+                                         history_full=4, overlap=True, out_dtype=None, halbedo=None, albedo_floor=1e-3):
+        """mid_sequence_atrous_recursive[_albedo] on host pointers the caller already holds: nothing but the C call.  hin, hlayers,
+        hout as for sequence_atrous_variance_pinned; hmotion: one pointer per frame to a float32 (h, w, 2) plane, or None: zero
+        motion; halbedo: one pointer per frame to an (h, w, 4) albedo plane in the layers' format, or None: no demodulation.
         Returns (wall_ms of the whole call, kernel_ms, copy_ms)."""
         n = len(hin)
         count = n - first if count is None else count
@@ -942,42 +974,61 @@ class Context:
             raise ValueError(f"{n} frames x {n_layers} layers, {len(hlayers)} layer pointers given")
         if hmotion is not None and len(hmotion) != n:
             raise ValueError(f"{n} frames, {len(hmotion)} motion planes given")
+        if halbedo is not None and len(halbedo) != n:
+            raise ValueError(f"{n} frames, {len(halbedo)} albedo planes given")
         ap = TemporalAccumParams(w, h, alpha, alpha_moments, history_max, history_full, fmt)
         vp = AtrousVarianceParams(w, h, 0, passes, sigma_lum, epsilon, fmt)
         t = (ctypes.c_float * 3)()
-        _check(lib.mid_sequence_atrous_recursive(self.handle, ctypes.byref(ap), ctypes.byref(vp), _layer_sigmas(sigmas, n_layers, "sequence_atrous_recursive"),
-                                                 (ctypes.c_void_p * n)(*hin), n, (ctypes.c_void_p * max(len(hlayers), 1))(*hlayers), n_layers,
-                                                 None if hmotion is None else (ctypes.c_void_p * n)(*hmotion), feedback, warmup, first, count,
-                                                 (ctypes.c_void_p * max(count, 1))(*hout[:max(count, 0)]), _OUT_FMT[_out_dtype(False, out_dtype)],
-                                                 1 if overlap else 0, t), "mid_sequence_atrous_recursive")
+        head = (self.handle, ctypes.byref(ap), ctypes.byref(vp), _layer_sigmas(sigmas, n_layers, "sequence_atrous_recursive"), (ctypes.c_void_p * n)(*hin), n,
+                (ctypes.c_void_p * max(len(hlayers), 1))(*hlayers), n_layers, None if hmotion is None else (ctypes.c_void_p * n)(*hmotion))
+        tail = (feedback, warmup, first, count, (ctypes.c_void_p * max(count, 1))(*hout[:max(count, 0)]), _OUT_FMT[_out_dtype(False, out_dtype)],
+                1 if overlap else 0, t)
+        if halbedo is None:
+            _check(lib.mid_sequence_atrous_recursive(*head, *tail), "mid_sequence_atrous_recursive")
+        else:
+            _check(lib.mid_sequence_atrous_recursive_albedo(*head, (ctypes.c_void_p * n)(*halbedo), albedo_floor, *tail), "mid_sequence_atrous_recursive_albedo")
         return tuple(t)
 
     def sequence_atrous_recursive(self, frames, layers, sigmas, motion=None, feedback=1, warmup=16, first=0, count=None, passes=5, sigma_lum=4.0,
                                   epsilon=1e-3, alpha=0.2, alpha_moments=0.2, history_max=32, history_full=4, overlap=True, pinned=True,
-                                  pinned_out=True, out_dtype=None):
+                                  pinned_out=True, out_dtype=None, albedo=None, albedo_floor=1e-3):
         """Outputs [first, first+count) of an animation through the pipeline with the recursive temporal accumulation as its compute
         stage (mid_sequence_atrous_recursive).  From frame s = max(0, first - warmup) on, per frame t: Vs = atrous_moments([frame], k=0),
         (colour, state, var) = temporal_accumulate(frame t, layers t, layers t-1, history, motion[t], Vs), output = atrous_variance(colour,
         var, layers t, passes); the next history is (colour, state) with feedback=0 and (the level after pass 0, state) with
         feedback=1.  motion: one float32 (h, w, 2) plane per frame, or None.  A run with first > 0 equals the whole run bit for bit
         only when warmup reaches frame 0.  pinned, pinned_out, out_dtype as for sequence_bilateral.
+        albedo: one (h, w, 4) plane per frame in the layers' dtype, or None.  With it the chain runs on illumination
+        (mid_sequence_atrous_recursive_albedo): frame t is demodulate(frame, albedo[t], albedo_floor) first, the passes return
+        float32, and output t is modulate(that, albedo[t], albedo_floor, out_dtype); the histories hold illumination.
         Returns (outputs, (wall_ms, kernel_ms, copy_ms))."""
         out_dtype = _out_dtype(False, out_dtype)
+        halb = None
+        if albedo is not None:
+            shape = np.asarray(frames[0]).shape[:2] + (4,)
+            halb = [self._albedo_plane(a, shape, "sequence_atrous_recursive") for a in albedo]
+            ldt = _img(layers[0][0]).dtype if len(layers) and len(layers[0]) else None
+            if len(halb) != len(frames) or any(a.dtype != ldt for a in halb):
+                raise ValueError(f"sequence_atrous_recursive: albedo must be one {shape} plane per frame in the layers' dtype ({ldt})")
         hmv = None
         if motion is not None:
             hmv = [np.ascontiguousarray(m, dtype=np.float32) for m in motion]
             shape = np.asarray(frames[0]).shape[:2] + (2,)
             if len(hmv) != len(frames) or any(m.shape != shape for m in hmv):
                 raise ValueError(f"sequence_atrous_recursive: motion must be one {shape} plane per frame")
-        pmv = PinnedFrames(self, hmv) if hmv is not None and pinned else None
+        pmv = palb = None
         try:
+            pmv = PinnedFrames(self, hmv) if hmv is not None and pinned else None
+            palb = PinnedFrames(self, halb) if halb is not None and pinned else None
             ptrs = None if hmv is None else (pmv.ptrs if pmv is not None else [m.ctypes.data for m in hmv])
+            aptrs = None if halb is None else (palb.ptrs if palb is not None else [a.ctypes.data for a in halb])
             return self._sequence_host("sequence_atrous_recursive", lambda hin, hout, w, h, fmt, hlayers, n_layers, count: self.sequence_atrous_recursive_pinned(
                 hin, hout, w, h, fmt, hlayers, n_layers, sigmas, ptrs, feedback, warmup, first, count, passes, sigma_lum, epsilon, alpha, alpha_moments,
-                history_max, history_full, overlap, out_dtype), frames, layers, _GUIDE_DTYPES, first, count, pinned, pinned_out, out_dtype)
+                history_max, history_full, overlap, out_dtype, aptrs, albedo_floor), frames, layers, _GUIDE_DTYPES, first, count, pinned, pinned_out, out_dtype)
         finally:
-            if pmv is not None:
-                pmv.free()
+            for b in (pmv, palb):
+                if b is not None:
+                    b.free()
 
 
 def _layer_sigmas(sigmas, n_layers, who, noun="sigmas"):

@@ -61,6 +61,9 @@ struct Options {
     int feedback = 1, warmup = 16;  // atrous-recursive: the next colour history (0: accumulated colour, 1: level after pass 0); warm-up frames of a block
     std::string motion_layer;       // atrous-recursive: substring of the .exr render element that holds the motion (R, G in pixels); empty: zero motion
     float motion_sx = 1.f, motion_sy = 1.f;   // --motion-scale
+    std::string albedo_layer;       // atrous-recursive: substring of the render element that holds the albedo; empty: the filter runs on colour
+    float albedo_floor = 1e-3f;     // --albedo-floor: lower bound of the divisor (mid_albedo_params.floor)
+    bool albedo_floor_given = false;
     int search_lo = -7, search_hi = 7, patch_lo = -3, patch_hi = 3;   // shaders/nonlocal.comp:5-6, half-open
     int temporal_k = -1;            // <0: the reference's frame list; >=0: window t-k..t+k of the sorted sequence
     int cpu_radius = 10;            // windowSize, src/main.cpp:1819
@@ -567,6 +570,7 @@ public:
         // every frame's own layers, all of them checked before anything is decoded: 1..16 per frame, the same count for all
         std::vector<std::vector<std::string>> frameLayers(use_layers ? n : 0);
         std::vector<std::string> motionNames;           // atrous-recursive with --motion-layer: the one render element of each frame that holds its motion
+        std::vector<std::string> albedoNames;           // atrous-recursive with --albedo-layer: the one render element of each frame that holds its albedo
         int L = 0;
         for (int i = 0; i < (int)frameLayers.size(); ++i) {
             std::vector<std::string> none;
@@ -582,6 +586,15 @@ public:
                 motionNames.push_back(hits[0]);
                 frameLayers[i] = rest;
             }
+            if (!opt.albedo_layer.empty()) {            // taken out of the guide layers too; a .png is as good as an .exr
+                std::vector<std::string> hits, rest;
+                for (const std::string &f : frameLayers[i]) (fs::path(f).filename().string().find(opt.albedo_layer) != std::string::npos ? hits : rest).push_back(f);
+                if (hits.size() != 1)
+                    throw std::runtime_error(frameNames[i] + ": --albedo-layer " + opt.albedo_layer + " matches " + std::to_string(hits.size()) +
+                                             " layer file(s) of this frame, it must match exactly one");
+                albedoNames.push_back(hits[0]);
+                frameLayers[i] = rest;
+            }
             const int li = (int)frameLayers[i].size();
             if (li < 1 || li > 16)
                 throw std::runtime_error(frameNames[i] + ": " + std::to_string(li) + " layer file(s) found, --animation-filter " + opt.animation_filter + " needs 1..16 per frame");
@@ -593,6 +606,7 @@ public:
         // the layers' format, one for the run: .exr layers (RGBA32F, RGBA16F with --half) guide the bilateral filters only
         std::vector<std::string> allLayers;
         for (auto &fl : frameLayers) allLayers.insert(allLayers.end(), fl.begin(), fl.end());
+        allLayers.insert(allLayers.end(), albedoNames.begin(), albedoNames.end());      // (the albedo planes obey the layers' one-format rule)
         if (nlm_guides) for (const std::string &ln : allLayers) if (is_hdr(ln)) (void)load(ln, true);   // refuses, saying why
         const int lfmt = layer_format(allLayers);
         const std::vector<float> jointSigma = af.family == SEQ_BILATERAL_JOINT || af.family == SEQ_ATROUS || af.family == SEQ_ATROUS_TEMPORAL || af.family == SEQ_ATROUS_VARIANCE || recursive ? layer_sigmas(frameLayers[0])            // (every frame has frame 0's layers)
@@ -659,7 +673,8 @@ public:
         const size_t layer_bytes = (size_t)pin.frames[0].width * pin.frames[0].height *
                                    (lfmt == MID_FMT_RGBA32F ? 16 : lfmt == MID_FMT_RGBA16F ? 8 : 4);    // (its real size; checked against the frame below)
         // frames whose input AND output -- and their layers -- fit the budget
-        const size_t n_pin = pinned_budget / (2 * frame_bytes_guess + (size_t)L * layer_bytes);
+        const size_t n_side_planes = (size_t)L + (albedoNames.empty() ? 0 : 1);      // page-locked beside a frame: its layers and its albedo plane
+        const size_t n_pin = pinned_budget / (2 * frame_bytes_guess + n_side_planes * layer_bytes);
         const int io_threads = files_at_a_time(n);
         for_each_file(1, n, [&](int i) {
             decode(i, (size_t)i < n_pin);
@@ -691,12 +706,24 @@ public:
                 motionPlanes[i][2 * q + 1] = px[4 * q + 1] * opt.motion_sy;
             }
         });
+        // the albedo planes: decoded like the layers, in their format, page-locked with their frame
+        std::vector<HostImage> albedoImgs(albedoNames.size());             // (released before `pin` and its context)
+        for_each_file(0, (int)albedoImgs.size(), [&](int i) {
+            albedoImgs[i] = load(albedoNames[i], false, (size_t)i < n_pin ? io : nullptr, lfmt == MID_FMT_RGBA16F);
+            const HostImage &a = albedoImgs[i];
+            if (a.w != pin.frames[0].width || a.h != pin.frames[0].height || a.format != lfmt)
+                throw std::runtime_error("albedo layer " + albedoNames[i] + " is not " +
+                                         (lfmt == MID_FMT_RGBA8 ? "an RGBA8" : lfmt == MID_FMT_RGBA16F ? "an RGBA16F" : "an RGBA32F") + " image of the frame's size");
+        });
+        std::vector<const void *> albedo_ptrs(albedoImgs.size());
+        for (size_t i = 0; i < albedoImgs.size(); ++i) albedo_ptrs[i] = albedoImgs[i].data();
+        if (!albedoNames.empty()) std::cout << "\talbedo " << albedoNames[0] << " floor " << opt.albedo_floor << "\n";
         std::vector<const void *> motion_ptrs(motionPlanes.size());
         for (size_t i = 0; i < motionPlanes.size(); ++i) motion_ptrs[i] = motionPlanes[i].data();
         if (!motionNames.empty()) std::cout << "\tmotion " << motionNames[0] << " scale " << opt.motion_sx << " " << opt.motion_sy << "\n";
         std::vector<const void *> layer_ptrs(layerImgs.size());
         for (size_t j = 0; j < layerImgs.size(); ++j) layer_ptrs[j] = layerImgs[j].data();
-        for (int i = 0; i < n; ++i) { if (pin.frame_pinned[i]) pinned_bytes += 2 * frame_bytes_guess + (size_t)L * layer_bytes; else ++n_pageable; }
+        for (int i = 0; i < n; ++i) { if (pin.frame_pinned[i]) pinned_bytes += 2 * frame_bytes_guess + n_side_planes * layer_bytes; else ++n_pageable; }
         const double load_sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - tl0).count();
         const int w = pin.frames[0].width, h = pin.frames[0].height, fmt = pin.frames[0].format;
         // LDR frames come back as RGBA8: the read-back conversion of GetImageFromGPU (:97-103) runs on the device
@@ -734,7 +761,8 @@ public:
         // The k = 0 families take the block as a sub-array of frames, layers and outputs; the others the whole sequence, of which they
         // upload the block plus kk halo frames on either side, and their layers, from the host.
         auto run_stage = [&](mid_ctx *c, const mid_nlm_params &np, const mid_bilateral_params &bpp, const void *const *frames, int nf,
-                             const void *const *layers, const void *const *motion, int kk, int start, int count, void *const *outs, float *t) {
+                             const void *const *layers, const void *const *motion, const void *const *albedo, int kk, int start, int count, void *const *outs,
+                             float *t) {
             const void *const *lp = use_layers ? layers : nullptr;
             switch (af.family) {
             case SEQ_BILATERAL:
@@ -760,8 +788,9 @@ public:
             case SEQ_ATROUS_RECURSIVE: {   // per frame, in order: the spatial moments, the accumulation into the history, the variance-guided passes
                 const mid_temporal_accum_params ap{bpp.width, bpp.height, opt.alpha, opt.alpha_moments, opt.history_max, 4.f, bpp.format};
                 const mid_atrous_variance_params vp{bpp.width, bpp.height, 0, opt.passes, opt.atrous_sigma_lum, opt.atrous_epsilon, bpp.format};
-                MID_CHECK(mid_sequence_atrous_recursive(c, &ap, &vp, jointSigma.data(), frames, nf, lp, L, motion, opt.feedback, opt.warmup, start, count,
-                                                        outs, out_fmt, 1, t)); break;
+                // (albedo: the chain runs on illumination -- demodulated first, modulated into the output; NULL is the plain call)
+                MID_CHECK(mid_sequence_atrous_recursive_albedo(c, &ap, &vp, jointSigma.data(), frames, nf, lp, L, motion, albedo, opt.albedo_floor, opt.feedback,
+                                                               opt.warmup, start, count, outs, out_fmt, 1, t)); break;
             }
             case SEQ_NLM_JOINT:            // one patch weight from all layers (jointSigma: the h of each layer)
                 MID_CHECK(mid_sequence_nlm_joint(c, &np, jointSigma.data(), frames, nf, lp, L, kk, start, count, outs, out_fmt, 1, t)); break;
@@ -787,7 +816,8 @@ public:
             const void *wl[32];
             for (int l = 0; l < 2 * L; ++l) wl[l] = lz.data();
             void *wo[1] = {o.data()};
-            run_stage(ctxs[g], wp, wbp, wi, 2, wl, nullptr, k > 0 ? 1 : 0, 0, 1, wo, nullptr);
+            const void *wa[2] = {lz.data(), lz.data()};            // (an albedo plane of zeros: the floor divides)
+            run_stage(ctxs[g], wp, wbp, wi, 2, wl, nullptr, albedo_ptrs.empty() ? nullptr : wa, k > 0 ? 1 : 0, 0, 1, wo, nullptr);
             // (b) the pinned-memory DMA path in both directions at the real frame size (its first use in a process
             // costs several ms): frame 0 up into a scratch buffer, and back down into the first result buffer
             void *scratch = nullptr;
@@ -880,8 +910,8 @@ public:
                     if (count == 0) return;
                     mid_ctx *ctx = ctxs[g];
                     float t[3] = {0, 0, 0};
-                    run_stage(ctx, p, bp, in.data(), n, layer_ptrs.data(), motion_ptrs.empty() ? nullptr : motion_ptrs.data(), k, start, count,
-                              pin.outs.data() + start, t);
+                    run_stage(ctx, p, bp, in.data(), n, layer_ptrs.data(), motion_ptrs.empty() ? nullptr : motion_ptrs.data(),
+                              albedo_ptrs.empty() ? nullptr : albedo_ptrs.data(), k, start, count, pin.outs.data() + start, t);
                     kern[g] = t[1]; copy[g] = t[2];
                 } catch (const std::exception &e) { errors[g] = e.what(); }
             });
@@ -1018,6 +1048,12 @@ static void usage()
         "                            motion in its R and G channels, in pixels (pixel p was at p + motion(p) in the previous frame); it is\n"
         "                            taken out of the guide layers.  Without it motion is zero.  A .png, no match or several are refused\n"
         "  --motion-scale SX,SY      atrous-recursive: factors on the motion's R and G (default 1,1)\n"
+        "  --albedo-layer SUBSTR     atrous-recursive: the render element of every frame (.png or .exr, in the guide layers' format) whose\n"
+        "                            file name contains SUBSTR holds the surface albedo; it is taken out of the guide layers.  The filter\n"
+        "                            then runs on illumination: every frame is divided by max(albedo, floor) before it is accumulated and\n"
+        "                            filtered, and the albedo is multiplied back into the output, so a texture neither stops the filter\n"
+        "                            nor is blurred.  Without it the filter runs on colour.  No match or several are refused\n"
+        "  --albedo-floor X          atrous-recursive with --albedo-layer: lower bound of the divisor, finite and > 0 (default 0.001)\n"
         "  --temporal-k K            multiframe: frames t-K..t+K of the sorted sequence instead of the reference's list\n"
         "  --animation               denoise EVERY sibling frame with temporal NLM (window +-K, default 2) instead of the mode list\n"
         "  --animation-filter F      animation mode: nlm (default: temporal NLM), or the bilateral of every frame -- bilateral\n"
@@ -1060,7 +1096,8 @@ static void usage()
         "                            or atrous-recursive: recursive temporal accumulation (a history of colour and luminance moments,\n"
         "                            blended as lerp(history, frame, max(1/N, alpha))), then the variance-guided passes, frame after\n"
         "                            frame (--alpha, --alpha-moments, --history-max, --feedback, --warmup, --motion-layer,\n"
-        "                            --motion-scale; --passes, --sigma-layers, --atrous-sigma-lum, --atrous-epsilon as atrous-variance;\n"
+        "                            --motion-scale, --albedo-layer, --albedo-floor; --passes, --sigma-layers, --atrous-sigma-lum,\n"
+        "                            --atrous-epsilon as atrous-variance;\n"
         "                            it ignores --temporal-k; not with --halo rccl), outputs output-animation-nonlinear-atrous-recursive-*.\n"
         "                            With --gpus N every frame block starts its history --warmup frames before its block: a sharded\n"
         "                            run equals the unsharded one bit for bit only when the warm-up reaches frame 0\n"
@@ -1138,6 +1175,8 @@ int main(int argc, char **argv)
             if (opt.warmup < 0) { std::cerr << "--warmup " << opt.warmup << " is negative\n"; return EXIT_FAILURE; }
         }
         else if (a == "--motion-layer") opt.motion_layer = next();
+        else if (a == "--albedo-layer") opt.albedo_layer = next();
+        else if (a == "--albedo-floor") { opt.albedo_floor = (float)atof(next()); opt.albedo_floor_given = true; }
         else if (a == "--motion-scale") {
             if (sscanf(next(), "%f,%f", &opt.motion_sx, &opt.motion_sy) != 2) { std::cerr << "--motion-scale needs sx,sy\n"; usage(); return EXIT_FAILURE; }
         }
@@ -1174,6 +1213,11 @@ int main(int argc, char **argv)
     }
     auto listed = [&](const char *m) { return ("," + opt.modes + ",").find(std::string(",") + m + ",") != std::string::npos; };
     auto want = [&](const char *m) { return opt.modes == "all" || listed(m); };
+    if ((!opt.albedo_layer.empty() || opt.albedo_floor_given) && !(opt.animation && opt.animation_filter == "atrous-recursive")) {
+        std::cerr << (!opt.albedo_layer.empty() ? "--albedo-layer" : "--albedo-floor") << " applies to --animation --animation-filter atrous-recursive only\n";
+        return EXIT_FAILURE;
+    }
+    if (opt.albedo_floor_given && opt.albedo_layer.empty()) { std::cerr << "--albedo-floor needs --albedo-layer\n"; return EXIT_FAILURE; }
     if (listed("atrous-recursive")) {
         std::cerr << "--modes atrous-recursive: the recursion needs a sequence; it is an animation filter (--animation --animation-filter atrous-recursive)\n";
         return EXIT_FAILURE;

@@ -278,6 +278,12 @@ int temporal_accumulate_out(mid_ctx *ctx, const mid_temporal_accum_params *p, co
                             mid_pixel *state_out, float *var_out, hipStream_t s);
 int temporal_accumulate_check(const mid_temporal_accum_params *p, const char *who, const float *layer_sigma, bool have_layers, int n_layers);
 
+// mid_demodulate / mid_modulate without their checks (the caller has made them), one launch on `s`: albedo.hip; used by the frame
+// pipeline (mid_sequence_atrous_recursive_albedo), not exported.  albedo_check: the size, the floor and the format word.
+int demodulate_out(mid_ctx *ctx, const mid_albedo_params *p, const void *in, const void *albedo, mid_pixel *out, hipStream_t s);
+int modulate_out(mid_ctx *ctx, const mid_albedo_params *p, const mid_pixel *in, const void *albedo, void *out, int out_fmt, hipStream_t s);
+int albedo_check(const mid_albedo_params *p, const char *who);
+
 // ROCTx ranges (csrc/markers.cpp): no-ops unless the process already holds a ROCTx (rocprofv3 --marker-trace preloads one).
 bool markers_active();
 void range_push(const char *name);

@@ -116,9 +116,11 @@ struct Stage {
     // A recursive stage (mid_sequence_atrous_recursive): output t needs what output t-1 left on the device.
     bool in_order = false;                    // every launch on ONE kernel stream, in output order (no alternation between two)
     const void *const *host_motion = nullptr; // one float2 plane per frame, uploaded in the frame's upload interval into one more slot
-                                              // beside its layers: the launch finds it at lt[j * (n_layers + 1) + n_layers]
+                                              // beside its layers: the launch finds it at lt[j * n_side + n_layers], n_side the side slots per frame
     int skip = 0;                             // leading outputs that are computed into a device slot and neither stored nor downloaded
                                               // (warm-up); host_out[0 .. skip) is not read
+    const void *const *host_albedo = nullptr; // one plane per frame in the layers' format (layer_bytes), uploaded in the frame's upload interval
+                                              // into one more side slot, after the layers and the motion plane
 };
 
 // Outputs [first, first+count) of an n-frame host sequence; frames outside that range are only
@@ -136,7 +138,7 @@ static int run_pipeline(mid_ctx *ctx, const Stage &st, const Launch &launch, con
     const size_t npix = (size_t)st.width * st.height;
     const size_t in_bytes = npix * fmt_bytes(st.format), layer_bytes = st.layer_bytes;
     const int n_layers = st.host_layers ? st.n_layers : 0;
-    const int n_side = n_layers + (st.host_motion ? 1 : 0);      // slots beside a frame: its layers and, last, its motion plane
+    const int n_side = n_layers + (st.host_motion ? 1 : 0) + (st.host_albedo ? 1 : 0);   // slots beside a frame: its layers, its motion plane, its albedo plane
     const size_t motion_bytes = npix * 2 * sizeof(float);
     const size_t side_bytes = st.host_motion && motion_bytes > layer_bytes ? motion_bytes : layer_bytes;
     const int skip = st.skip;
@@ -205,7 +207,7 @@ static int run_pipeline(mid_ctx *ctx, const Stage &st, const Launch &launch, con
     ctx->pipe.last = mid_pipe_last{};
     struct Events { hipEvent_t *ev; } up0{ctx->pipe.ev.data()}, up1{up0.ev + n_up}, c0{up1.ev + n_up}, c1{c0.ev + nb}, d0{c1.ev + nb}, d1{d0.ev + nb};
     auto slot = [&](int f) { return dring.p[(f - f_lo) % ring]; };
-    auto layer_slot = [&](int f, int l) { return dlayers.p[((f - f_lo) % ring) * n_side + l]; };   // frame f's layer l (l == n_layers: its motion plane)
+    auto layer_slot = [&](int f, int l) { return dlayers.p[((f - f_lo) % ring) * n_side + l]; };   // frame f's layer l (l >= n_layers: its motion plane, its albedo plane)
 
     int next_upload = f_lo;
     auto upload = [&](int f) -> int {
@@ -228,6 +230,7 @@ static int run_pipeline(mid_ctx *ctx, const Stage &st, const Launch &launch, con
         for (int l = 0; l < n_layers; ++l)      // (its guide layers ride in the same upload interval: they share the slot's lifetime)
             if (int rc = copy_h2d(ctx, layer_slot(f, l), st.host_layers[(size_t)f * n_layers + l], layer_bytes, ctx->upload)) return rc;
         if (st.host_motion) { if (int rc = copy_h2d(ctx, layer_slot(f, n_layers), st.host_motion[f], motion_bytes, ctx->upload)) return rc; }
+        if (st.host_albedo) { if (int rc = copy_h2d(ctx, layer_slot(f, n_side - 1), st.host_albedo[f], layer_bytes, ctx->upload)) return rc; }
         MID_HIP(hipEventRecord(up1.ev[f - f_lo], ctx->upload));
         return MID_OK;
     };
@@ -683,17 +686,22 @@ extern "C" int mid_sequence_atrous_variance(mid_ctx *ctx, const mid_atrous_varia
 // feedback 1: the level after pass 0, which is then run on its own into the history buffer and continued with first_pass = 1
 // (a4i's chain identity keeps the bits of the public calls).  Frames s .. first-1 are warm-up: computed, not stored.  The window
 // of the schedule is k = 1 -- frame t-1's layers must be resident -- and ONE block of the context's cache holds the two
-// histories (colour and state each), the accumulated colour, Vs, the blended variance, the variance after pass 0, and the levels.
-extern "C" int mid_sequence_atrous_recursive(mid_ctx *ctx, const mid_temporal_accum_params *ap, const mid_atrous_variance_params *vp,
-                                             const float *layer_sigma, const void *const *host_frames, int n_frames,
-                                             const void *const *host_layers, int n_layers, const void *const *host_motion, int feedback,
-                                             int warmup, int first, int count, void *const *host_out, int out_format, int overlap,
-                                             float *timings_ms)
+// histories (colour and state each), the accumulated colour, Vs, the blended variance, the variance after pass 0, and the levels:
+// 132 B per pixel.
+// With an albedo plane per frame (section a4k) the chain runs on ILLUMINATION: frame t is demodulated into an RGBA32F plane of the
+// block, the three steps read that plane as an RGBA32F frame, the passes' final level goes as RGBA32F into one more plane, and
+// mid_modulate with frame t's albedo stores the output.  The histories hold illumination.  The block then has 164 B per pixel.
+extern "C" int mid_sequence_atrous_recursive_albedo(mid_ctx *ctx, const mid_temporal_accum_params *ap, const mid_atrous_variance_params *vp,
+                                                    const float *layer_sigma, const void *const *host_frames, int n_frames,
+                                                    const void *const *host_layers, int n_layers, const void *const *host_motion,
+                                                    const void *const *host_albedo, float albedo_floor, int feedback, int warmup, int first,
+                                                    int count, void *const *host_out, int out_format, int overlap, float *timings_ms)
 {
     Bind b(ctx, nullptr);
     if (b.rc) return b.rc;
-    const char *who = "sequence_atrous_recursive";
-    if (int rc = refuse_if_recording(ctx->compute, "mid_sequence_atrous_recursive (four streams, host-side waits)")) return rc;
+    const char *who = host_albedo ? "sequence_atrous_recursive_albedo" : "sequence_atrous_recursive";
+    if (int rc = refuse_if_recording(ctx->compute, host_albedo ? "mid_sequence_atrous_recursive_albedo (four streams, host-side waits)"
+                                                               : "mid_sequence_atrous_recursive (four streams, host-side waits)")) return rc;
     if (int rc = temporal_accumulate_check(ap, who, layer_sigma, host_layers != nullptr, n_layers)) return rc;
     if (int rc = atrous_variance_check(vp, who, layer_sigma, host_layers != nullptr, n_layers)) return rc;
     MID_REQUIRE(vp->first_pass == 0, "%s: first_pass %d: the passes start on the accumulated colour (continue a filter with mid_atrous_variance)", who, vp->first_pass);
@@ -702,11 +710,13 @@ extern "C" int mid_sequence_atrous_recursive(mid_ctx *ctx, const mid_temporal_ac
                 vp->width, vp->height, vp->format);
     MID_REQUIRE(feedback == 0 || feedback == 1, "%s: feedback %d is neither 0 (the accumulated colour) nor 1 (the level after pass 0)", who, feedback);
     MID_REQUIRE(warmup >= 0, "%s: warmup %d < 0", who, warmup);
+    const mid_albedo_params dp{ap->width, ap->height, albedo_floor, ap->format};     // demodulate: the frames' format, the albedo in the guide format
+    if (host_albedo) { if (int rc = albedo_check(&dp, who)) return rc; }
     const mid_atrous_moments_params mp{ap->width, ap->height, ap->format};
     if (int rc = atrous_moments_check(&mp, who, layer_sigma, host_layers != nullptr, n_layers, 1, 0)) return rc;
     if (int rc = check_sequence({who, "n_frames", true, true}, host_frames, n_frames, host_layers, n_layers, 0, first, count, host_out, out_format)) return rc;
     const int s0 = first - warmup < 0 ? 0 : first - warmup, skip = first - s0;
-    {   // the warm-up frames, frame s0 - 1 (the schedule's window uploads it) and frame first + count, their layers and motion planes
+    {   // the warm-up frames, frame s0 - 1 (the schedule's window uploads it) and frame first + count, their layers, motion and albedo planes
         const int lo = s0 - 1 < 0 ? 0 : s0 - 1, hi = first + count > n_frames - 1 ? n_frames - 1 : first + count;
         std::vector<const void *> inputs;
         for (int f = lo; f <= hi; ++f) {
@@ -720,18 +730,28 @@ extern "C" int mid_sequence_atrous_recursive(mid_ctx *ctx, const mid_temporal_ac
                 MID_REQUIRE(host_motion[f], "%s: the motion plane of frame %d is NULL", who, f);
                 inputs.push_back(host_motion[f]);
             }
+            if (host_albedo) {
+                MID_REQUIRE(host_albedo[f], "%s: the albedo plane of frame %d is NULL", who, f);
+                inputs.push_back(host_albedo[f]);
+            }
         }
-        if (int rc = check_no_alias(who, "an input frame, layer or motion plane of this call", inputs.data(), (int)inputs.size(), (const void *const *)host_out, count)) return rc;
+        if (int rc = check_no_alias(who, host_albedo ? "an input frame, layer, motion or albedo plane of this call" : "an input frame, layer or motion plane of this call",
+                                    inputs.data(), (int)inputs.size(), (const void *const *)host_out, count)) return rc;
     }
     const size_t npix = (size_t)ap->width * ap->height;
     const int gfmt = fmt_guide(ap->format);
     const size_t plane = (npix * sizeof(float) + 15) & ~(size_t)15;       // one float plane, the next one 16-byte aligned
     mid_atrous_variance_params fp = *vp;                    // the passes read RGBA32F levels, whatever the frames are
     fp.format = MID_FMT_WITH_GUIDE(MID_FMT_RGBA32F, gfmt);
+    // with albedo the moments and the accumulation read the demodulated plane: an RGBA32F frame
+    mid_temporal_accum_params aq = *ap;
+    mid_atrous_moments_params mq = mp;
+    const mid_albedo_params mo{ap->width, ap->height, albedo_floor, fp.format};       // modulate: RGBA32F in
+    if (host_albedo) aq.format = mq.format = fp.format;
     Stage st{who, ap->width, ap->height, fmt_frames(ap->format), npix * fmt_bytes(gfmt), host_layers, n_layers, true, "atrous recursive %d"};
-    st.level_bytes = npix * 16 * 7 + 5 * plane; st.n_levels = 1;
-    st.in_order = true; st.host_motion = host_motion; st.skip = skip;
-    const int n_side = n_layers + (host_motion ? 1 : 0);
+    st.level_bytes = npix * 16 * 7 + 5 * plane + (host_albedo ? npix * 32 : 0); st.n_levels = 1;
+    st.in_order = true; st.host_motion = host_motion; st.skip = skip; st.host_albedo = host_albedo;
+    const int n_side = n_layers + (host_motion ? 1 : 0) + (host_albedo ? 1 : 0);
     int step = 0;                                           // frames accumulated so far: the launches come in output order
     auto launch = [&](const void *const *tbl, int, const uint32_t *const *lt, int, int t0, int bn, void *const *out, int out_fmt, hipStream_t s) {
         char *blk = (char *)ctx->pipe.atrous.p[0];
@@ -741,32 +761,53 @@ extern "C" int mid_sequence_atrous_recursive(mid_ctx *ctx, const mid_temporal_ac
         char *fb = blk + npix * 112;
         float *vs = (float *)fb, *vt = (float *)(fb + plane), *v1 = (float *)(fb + 2 * plane);
         float *vlevel[2] = {(float *)(fb + 3 * plane), (float *)(fb + 4 * plane)};
+        mid_pixel *illum = (mid_pixel *)(fb + 5 * plane), *fin = illum + npix;        // (with albedo only: the block ends before them otherwise)
         for (int i = 0; i < bn; ++i, ++step) {
             const int t = t0 + i, cur = step & 1, prev = cur ^ 1;
             const uint32_t *const *ly = lt + (size_t)t * n_side;
             const uint32_t *const *pl = step ? lt + (size_t)(t - 1) * n_side : ly;
             const float *mv = host_motion ? (const float *)ly[n_layers] : nullptr;
-            if (int rc = atrous_moments_out(ctx, &mp, layer_sigma, tbl + t, ly, n_layers, 1, 0, 0, vs, s)) return rc;
+            const void *alb = host_albedo ? (const void *)ly[n_side - 1] : nullptr;
+            const void *frame = tbl[t];
+            if (alb) {
+                if (int rc = demodulate_out(ctx, &dp, tbl[t], alb, illum, s)) return rc;
+                frame = illum;
+            }
+            // the passes' last level: the output itself, or with albedo the plane that mid_modulate reads
+            void *last = alb ? (void *)fin : out[i];
+            const int last_fmt = alb ? (int)MID_FMT_RGBA32F : out_fmt;
+            if (int rc = atrous_moments_out(ctx, &mq, layer_sigma, &frame, ly, n_layers, 1, 0, 0, vs, s)) return rc;
             mid_pixel *col = feedback ? acc : hc[cur];
-            if (int rc = temporal_accumulate_out(ctx, ap, layer_sigma, tbl[t], ly, pl, n_layers, mv, step ? hc[prev] : nullptr, step ? hs[prev] : nullptr,
+            if (int rc = temporal_accumulate_out(ctx, &aq, layer_sigma, frame, ly, pl, n_layers, mv, step ? hc[prev] : nullptr, step ? hs[prev] : nullptr,
                                                  vs, col, hs[cur], vt, s)) return rc;
             if (!feedback) {
-                if (int rc = atrous_variance_out(ctx, &fp, layer_sigma, col, vt, ly, n_layers, out[i], out_fmt, nullptr, level, vlevel, s)) return rc;
-                continue;
+                if (int rc = atrous_variance_out(ctx, &fp, layer_sigma, col, vt, ly, n_layers, last, last_fmt, nullptr, level, vlevel, s)) return rc;
+            } else {
+                mid_atrous_variance_params p0 = fp, p1 = fp;
+                p0.n_passes = 1;
+                p1.first_pass = 1; p1.n_passes = fp.n_passes - 1;
+                if (int rc = atrous_variance_out(ctx, &p0, layer_sigma, col, vt, ly, n_layers, hc[cur], MID_FMT_RGBA32F, v1, level, vlevel, s)) return rc;
+                if (p1.n_passes >= 1) {
+                    if (int rc = atrous_variance_out(ctx, &p1, layer_sigma, hc[cur], v1, ly, n_layers, last, last_fmt, nullptr, level, vlevel, s)) return rc;
+                } else if (int rc = atrous_variance_out(ctx, &p0, layer_sigma, col, vt, ly, n_layers, last, last_fmt, nullptr, level, vlevel, s)) return rc;
             }
-            mid_atrous_variance_params p0 = fp, p1 = fp;
-            p0.n_passes = 1;
-            p1.first_pass = 1; p1.n_passes = fp.n_passes - 1;
-            if (int rc = atrous_variance_out(ctx, &p0, layer_sigma, col, vt, ly, n_layers, hc[cur], MID_FMT_RGBA32F, v1, level, vlevel, s)) return rc;
-            if (p1.n_passes >= 1) {
-                if (int rc = atrous_variance_out(ctx, &p1, layer_sigma, hc[cur], v1, ly, n_layers, out[i], out_fmt, nullptr, level, vlevel, s)) return rc;
-            } else if (int rc = atrous_variance_out(ctx, &p0, layer_sigma, col, vt, ly, n_layers, out[i], out_fmt, nullptr, level, vlevel, s)) return rc;
+            if (alb) { if (int rc = modulate_out(ctx, &mo, fin, alb, out[i], out_fmt, s)) return rc; }
         }
         return (int)MID_OK;
     };
     std::vector<void *> outs((size_t)skip + count, nullptr);
     for (int i = 0; i < count; ++i) outs[(size_t)skip + i] = host_out[i];
     return run_pipeline(ctx, st, launch, host_frames, n_frames, 1, s0, skip + count, outs.data(), out_format, overlap, timings_ms);
+}
+
+extern "C" int mid_sequence_atrous_recursive(mid_ctx *ctx, const mid_temporal_accum_params *ap, const mid_atrous_variance_params *vp,
+                                             const float *layer_sigma, const void *const *host_frames, int n_frames,
+                                             const void *const *host_layers, int n_layers, const void *const *host_motion, int feedback,
+                                             int warmup, int first, int count, void *const *host_out, int out_format, int overlap,
+                                             float *timings_ms)
+{
+    return mid_sequence_atrous_recursive_albedo(ctx, ap, vp, layer_sigma, host_frames, n_frames, host_layers, n_layers, host_motion, nullptr, 0.f, feedback,
+                                                warmup, first, count, host_out, out_format, overlap, timings_ms);
 }
 
 // Device timeline of the context's last mid_sequence_nlm*, mid_sequence_bilateral or mid_sequence_nlm_layers[_temporal] call, read back from the events the call left in the context's

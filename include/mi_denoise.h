@@ -835,6 +835,60 @@ int mid_sequence_atrous_recursive(mid_ctx *ctx, const mid_temporal_accum_params 
                                   int warmup /* >= 0 */, int first, int count, void *const *host_out, int out_format, int overlap,
                                   float *timings_ms);
 
+/* ---- a4k: albedo demodulation ---------------------------------------------------------------
+ * SVGF filters ILLUMINATION, not colour: the noisy radiance is divided by the surface albedo before it is accumulated and
+ * filtered, and the albedo is multiplied back at the end.  A texture then neither stops the filter (as it does when the albedo is
+ * a guide layer) nor is blurred away (as it is when the albedo is left out).  Two streaming passes:
+ *   mid_demodulate  I = C / max(A, floor)     `in` a frame in the frame format of p->format, `out` RGBA32F
+ *   mid_modulate    O = I * max(A, floor)     `in` RGBA32F (any other frame format in p->format is refused), `out` in out_format
+ * p->format is a MID_FMT_WITH_GUIDE word: the frame format RGBA8, RGBA16F or RGBA32F, and the format of the albedo plane in the
+ * guide field.  The albedo is read exactly as a guide texel is (a3 / a4e): IEEE values, alpha ignored, no clamping, RGBA8 texels
+ * the correctly rounded c / 255.  C is widened as a4i widens a frame.
+ * Per pixel and per channel c in {R, G, B}:  d_c = fmaxf(A_c, floor)  -- a NaN or negative albedo therefore gives floor --
+ *   demodulate: I_c = C_c / d_c, one IEEE division;      modulate: O_c = I_c * d_c, one multiplication;
+ * alpha passes through unchanged in both.  mid_modulate writes out_format with the packing rules of mid_pack_u8 / mid_pack_f16
+ * (a6); its `out` may be page-locked host memory addressed from the device, which is how the frame pipeline stores its final
+ * output.  Everything else is IEEE arithmetic, nothing is clamped: a NaN or Inf colour stays one; an albedo of +Inf demodulates
+ * to 0 (of a finite colour) and modulates 0 * Inf to NaN, so an infinite albedo does NOT round-trip; an albedo below floor
+ * round-trips (both passes use floor) but the illumination is C / floor, not C / A.
+ * floor must be finite and > 0; every higher layer defaults to 1e-3, the usual choice of SVGF implementations.  It is a parameter
+ * for the reason a4i gives for epsilon: what counts as "no albedo" depends on the renderer's units.
+ * Precision: the bits of the formulas in IEEE binary32 (the build keeps -ffp-contract=off and uses no fast-math flag) -- those of
+ * numpy float32.  modulate(demodulate(C)) is within 2^-22 |C| of C for normal-range values: two roundings.
+ * Class: pointwise (a5 / a6): one pixel per lane, a 16 / 8 / 4-byte load of the frame and one of the albedo, grid-stride (at most
+ * 8 workgroups of 256 lanes per CU), index arithmetic in size_t, the formats run-time wave-uniform values, no LDS, no scratch.
+ * MID_ERR_INVALID before anything is queued, `out` untouched: a NULL pointer; floor not finite or <= 0; an unknown frame, guide or
+ * output format; the alignment rules of a4e, each plane to its texel size (4 / 8 / 16 bytes); width or height < 1, or 2^30 pixels
+ * and more; `out` overlapping `albedo`; `out` overlapping `in` -- except exactly in place with equal texel size (RGBA32F to
+ * RGBA32F), which is allowed because the pass is pointwise. */
+typedef struct mid_albedo_params {
+    int32_t width, height;
+    float   floor;        /* lower bound of the divisor, finite and > 0; default 1e-3 */
+    int32_t format;       /* MID_FMT_WITH_GUIDE(frame format, albedo format); mid_modulate: the frame format must be RGBA32F */
+} mid_albedo_params;
+int mid_demodulate(mid_ctx *ctx, const mid_albedo_params *p, const void *in, const void *albedo, mid_pixel *out, void *stream);
+int mid_modulate(mid_ctx *ctx, const mid_albedo_params *p, const mid_pixel *in, const void *albedo, void *out, int out_format,
+                 void *stream);
+/* mid_sequence_atrous_recursive with an albedo plane per frame.  host_albedo == NULL: it IS that call (albedo_floor is not read),
+ * and that entry point is this one with NULL.  Otherwise host_albedo holds n_frames host planes in the guide format of ap->format
+ * (they obey the layers' format) and, per frame t: (0) mid_demodulate of frame t with host_albedo[t] into an RGBA32F plane;
+ * (1) - (3) of mid_sequence_atrous_recursive on that plane (frame format RGBA32F), the passes' final level written as RGBA32F;
+ * (4) mid_modulate of that level with host_albedo[t] into host_out in out_format -- the kernel-stored output of the pipeline
+ * where the other stages' last pass stores it.  The histories and both feedback forms stay in illumination space.  Output t has,
+ * bit for bit, the result of that chain of public calls.  An albedo plane is one more side slot of its frame, after the layers
+ * and the motion plane, uploaded in the frame's upload interval.  The block of the context's cache grows by two RGBA32F planes
+ * (32 B per pixel) to 164 B per pixel.
+ * MID_ERR_INVALID before anything is queued, host_out and timings_ms untouched: the refusals of mid_sequence_atrous_recursive;
+ * albedo_floor not finite or <= 0; a NULL albedo plane among the frames max(0, s-1) .. min(n_frames-1, first+count); an output
+ * that is one of those planes. */
+int mid_sequence_atrous_recursive_albedo(mid_ctx *ctx, const mid_temporal_accum_params *ap, const mid_atrous_variance_params *vp,
+                                         const float *layer_sigma, const void *const *host_frames, int n_frames,
+                                         const void *const *host_layers, int n_layers /* 1..16 */,
+                                         const void *const *host_motion /* n_frames float2 planes, or NULL */,
+                                         const void *const *host_albedo /* n_frames planes in the guide format, or NULL */,
+                                         float albedo_floor, int feedback /* 0 | 1 */, int warmup /* >= 0 */, int first, int count,
+                                         void *const *host_out, int out_format, int overlap, float *timings_ms);
+
 /* ---- a5: normalize ----------------------------------------------------------------------
  * One dispatch of shaders/normalize.comp (RecordCommandsOfExecuteAndTransfer(normKernel=true)):
  * out = weightColor / normWeight, or (1,0,1,1) where normWeight == 0; bindings {0: out; 1: W}. */
