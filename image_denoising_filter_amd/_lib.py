@@ -74,6 +74,12 @@ class AlbedoParams(ctypes.Structure):
     _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("floor", ctypes.c_float), ("format", ctypes.c_int32)]
 
 
+class FireflyParams(ctypes.Structure):
+    """mid_firefly_params (section a4l)."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("radius", ctypes.c_int32), ("rank", ctypes.c_int32),
+                ("gain", ctypes.c_float), ("floor", ctypes.c_float), ("format", ctypes.c_int32)]
+
+
 class NormalizeParams(ctypes.Structure):
     _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32)]
 
@@ -156,6 +162,12 @@ _SIGNATURES = {
                                                             ctypes.POINTER(ctypes.c_float), c_void_pp, ctypes.c_int, c_void_pp, ctypes.c_int, c_void_pp,
                                                             c_void_pp, ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_pp,
                                                             ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
+    "mid_firefly_clamp": (ctypes.c_int, [_P, ctypes.POINTER(FireflyParams), _P, _P, _P]),
+    "mid_sequence_atrous_recursive_firefly": (ctypes.c_int, [_P, ctypes.POINTER(TemporalAccumParams), ctypes.POINTER(AtrousVarianceParams),
+                                                             ctypes.POINTER(ctypes.c_float), c_void_pp, ctypes.c_int, c_void_pp, ctypes.c_int, c_void_pp,
+                                                             c_void_pp, ctypes.c_float, ctypes.POINTER(FireflyParams), ctypes.c_int, ctypes.c_int,
+                                                             ctypes.c_int, ctypes.c_int, c_void_pp, ctypes.c_int, ctypes.c_int,
+                                                             ctypes.POINTER(ctypes.c_float)]),
     "mid_normalize": (ctypes.c_int, [_P, ctypes.POINTER(NormalizeParams), _P, _P, _P]),
     "mid_unpack_u8": (ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_int, _P, _P]),
     "mid_pack_u8": (ctypes.c_int, [_P, _P, ctypes.c_size_t, _P, _P]),

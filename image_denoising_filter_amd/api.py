@@ -15,7 +15,7 @@ import weakref
 
 import numpy as np
 
-from ._lib import AlbedoParams, AtrousMomentsParams, AtrousParams, AtrousVarianceParams, BilateralParams, Image, NlmParams, NormalizeParams, TemporalAccumParams, c_void_pp, lib
+from ._lib import AlbedoParams, AtrousMomentsParams, AtrousParams, AtrousVarianceParams, BilateralParams, FireflyParams, Image, NlmParams, NormalizeParams, TemporalAccumParams, c_void_pp, lib
 
 FMT_RGBA32F, FMT_RGBA8, FMT_RGBA16F = 0, 1, 2
 
@@ -621,6 +621,18 @@ class Context:
         _check(lib.mid_modulate(self.handle, ctypes.byref(p), d_in.ptr, d_a.ptr, d_out.ptr, _OUT_FMT[out_dtype], None), "mid_modulate")
         return self.download(d_out, (h, w, 4), out_dtype)
 
+    def firefly_clamp(self, frame, radius=1, rank=1, gain=1.0, floor=0.0):
+        """Firefly clamp and NaN repair of a frame (mid_firefly_clamp): a pixel whose luminance exceeds gain times the rank-th largest
+        finite luminance of its (2 radius + 1)^2 neighbourhood (and floor) is scaled down to that limit, a pixel with a non-finite
+        colour becomes a grey of the limit; alpha unchanged.  frame: (h, w, 4) uint8, float16 or float32.  Returns float32 (h, w, 4)."""
+        (frame,) = _same_frames([frame], "firefly_clamp")
+        _firefly_args(rank, radius, gain, floor, "firefly_clamp", off_allowed=False)
+        h, w = frame.shape[:2]
+        p = FireflyParams(w, h, radius, rank, gain, floor, _fmt_of(frame))
+        d_in, d_out = self.upload(frame), self.alloc(w * h * 16)
+        _check(lib.mid_firefly_clamp(self.handle, ctypes.byref(p), d_in.ptr, d_out.ptr, None), "mid_firefly_clamp")
+        return self.download(d_out, (h, w, 4), np.float32)
+
     def normalize(self, W):
         """normalize.comp."""
         W = np.ascontiguousarray(W, dtype=np.float32)
@@ -961,13 +973,16 @@ class Context:
 
     def sequence_atrous_recursive_pinned(self, hin, hout, w, h, fmt, hlayers, n_layers, sigmas, hmotion=None, feedback=1, warmup=16, first=0,
                                          count=None, passes=5, sigma_lum=4.0, epsilon=1e-3, alpha=0.2, alpha_moments=0.2, history_max=32,
-                                         history_full=4, overlap=True, out_dtype=None, halbedo=None, albedo_floor=1e-3):
-        """mid_sequence_atrous_recursive[_albedo] on host pointers the caller already holds: nothing but the C call.  hin, hlayers,
-        hout as for sequence_atrous_variance_pinned; hmotion: one pointer per frame to a float32 (h, w, 2) plane, or None: zero
-        motion; halbedo: one pointer per frame to an (h, w, 4) albedo plane in the layers' format, or None: no demodulation.
+                                         history_full=4, overlap=True, out_dtype=None, halbedo=None, albedo_floor=1e-3,
+                                         firefly_rank=0, firefly_radius=1, firefly_gain=1.0, firefly_floor=0.0):
+        """mid_sequence_atrous_recursive[_albedo | _firefly] on host pointers the caller already holds: nothing but the C call.  hin,
+        hlayers, hout as for sequence_atrous_variance_pinned; hmotion: one pointer per frame to a float32 (h, w, 2) plane, or None: zero
+        motion; halbedo: one pointer per frame to an (h, w, 4) albedo plane in the layers' format, or None: no demodulation;
+        firefly_rank 1..4: mid_firefly_clamp in front of the chain (0: the existing call).
         Returns (wall_ms of the whole call, kernel_ms, copy_ms)."""
         n = len(hin)
         count = n - first if count is None else count
+        firefly = _firefly_args(firefly_rank, firefly_radius, firefly_gain, firefly_floor, "sequence_atrous_recursive")
         if len(hout) < count:
             raise ValueError(f"{count} outputs, {len(hout)} output buffers given")
         if len(hlayers) != n * n_layers:
@@ -983,7 +998,12 @@ class Context:
                 (ctypes.c_void_p * max(len(hlayers), 1))(*hlayers), n_layers, None if hmotion is None else (ctypes.c_void_p * n)(*hmotion))
         tail = (feedback, warmup, first, count, (ctypes.c_void_p * max(count, 1))(*hout[:max(count, 0)]), _OUT_FMT[_out_dtype(False, out_dtype)],
                 1 if overlap else 0, t)
-        if halbedo is None:
+        if firefly is not None:
+            radius, rank, gain, floor = firefly
+            fp = FireflyParams(w, h, radius, rank, gain, floor, fmt & 0xff)
+            _check(lib.mid_sequence_atrous_recursive_firefly(*head, None if halbedo is None else (ctypes.c_void_p * n)(*halbedo), albedo_floor,
+                                                             ctypes.byref(fp), *tail), "mid_sequence_atrous_recursive_firefly")
+        elif halbedo is None:
             _check(lib.mid_sequence_atrous_recursive(*head, *tail), "mid_sequence_atrous_recursive")
         else:
             _check(lib.mid_sequence_atrous_recursive_albedo(*head, (ctypes.c_void_p * n)(*halbedo), albedo_floor, *tail), "mid_sequence_atrous_recursive_albedo")
@@ -991,7 +1011,8 @@ class Context:
 
     def sequence_atrous_recursive(self, frames, layers, sigmas, motion=None, feedback=1, warmup=16, first=0, count=None, passes=5, sigma_lum=4.0,
                                   epsilon=1e-3, alpha=0.2, alpha_moments=0.2, history_max=32, history_full=4, overlap=True, pinned=True,
-                                  pinned_out=True, out_dtype=None, albedo=None, albedo_floor=1e-3):
+                                  pinned_out=True, out_dtype=None, albedo=None, albedo_floor=1e-3, firefly_rank=0, firefly_radius=1,
+                                  firefly_gain=1.0, firefly_floor=0.0):
         """Outputs [first, first+count) of an animation through the pipeline with the recursive temporal accumulation as its compute
         stage (mid_sequence_atrous_recursive).  From frame s = max(0, first - warmup) on, per frame t: Vs = atrous_moments([frame], k=0),
         (colour, state, var) = temporal_accumulate(frame t, layers t, layers t-1, history, motion[t], Vs), output = atrous_variance(colour,
@@ -1001,8 +1022,11 @@ class Context:
         albedo: one (h, w, 4) plane per frame in the layers' dtype, or None.  With it the chain runs on illumination
         (mid_sequence_atrous_recursive_albedo): frame t is demodulate(frame, albedo[t], albedo_floor) first, the passes return
         float32, and output t is modulate(that, albedo[t], albedo_floor, out_dtype); the histories hold illumination.
+        firefly_rank 1..4 (0: off) puts firefly_clamp(frame, firefly_radius, firefly_rank, firefly_gain, firefly_floor) in front of
+        the chain (mid_sequence_atrous_recursive_firefly), AFTER the demodulation: firefly_floor is in illumination units then.
         Returns (outputs, (wall_ms, kernel_ms, copy_ms))."""
         out_dtype = _out_dtype(False, out_dtype)
+        _firefly_args(firefly_rank, firefly_radius, firefly_gain, firefly_floor, "sequence_atrous_recursive")
         halb = None
         if albedo is not None:
             shape = np.asarray(frames[0]).shape[:2] + (4,)
@@ -1024,11 +1048,31 @@ class Context:
             aptrs = None if halb is None else (palb.ptrs if palb is not None else [a.ctypes.data for a in halb])
             return self._sequence_host("sequence_atrous_recursive", lambda hin, hout, w, h, fmt, hlayers, n_layers, count: self.sequence_atrous_recursive_pinned(
                 hin, hout, w, h, fmt, hlayers, n_layers, sigmas, ptrs, feedback, warmup, first, count, passes, sigma_lum, epsilon, alpha, alpha_moments,
-                history_max, history_full, overlap, out_dtype, aptrs, albedo_floor), frames, layers, _GUIDE_DTYPES, first, count, pinned, pinned_out, out_dtype)
+                history_max, history_full, overlap, out_dtype, aptrs, albedo_floor, firefly_rank, firefly_radius, firefly_gain, firefly_floor), frames, layers, _GUIDE_DTYPES, first, count, pinned, pinned_out, out_dtype)
         finally:
             for b in (pmv, palb):
                 if b is not None:
                     b.free()
+
+
+def _firefly_args(rank, radius, gain, floor, who, off_allowed=True):
+    """The firefly keywords of a call, checked before any GPU work: None for rank 0 (the stage is off; the other three must then be
+    their defaults), otherwise (radius, rank, gain, floor) in the ranges of mid_firefly_params."""
+    if off_allowed and rank == 0:
+        if (radius, gain, floor) != (1, 1.0, 0.0):
+            raise ValueError(f"{who}: firefly_radius, firefly_gain and firefly_floor need firefly_rank 1..4 (it is 0: the stage is off)")
+        return None
+    if not isinstance(rank, (int, np.integer)) or isinstance(rank, bool) or not 1 <= rank <= 4:
+        raise ValueError(f"{who}: the firefly rank must be an integer in 1..4, got {rank!r}")
+    if not isinstance(radius, (int, np.integer)) or isinstance(radius, bool) or radius not in (1, 2):
+        raise ValueError(f"{who}: the firefly radius must be 1 or 2, got {radius!r}")
+    gain, floor = float(gain), float(floor)
+    f32_max = float(np.finfo(np.float32).max)          # (the C side reads floats: a double beyond them would arrive as Inf)
+    if not (0 < gain <= f32_max and float(np.float32(gain)) > 0):
+        raise ValueError(f"{who}: the firefly gain must be finite and > 0, got {gain}")
+    if not 0 <= floor <= f32_max:
+        raise ValueError(f"{who}: the firefly floor must be finite and >= 0, got {floor}")
+    return int(radius), int(rank), gain, floor
 
 
 def _layer_sigmas(sigmas, n_layers, who, noun="sigmas"):

@@ -64,6 +64,9 @@ struct Options {
     std::string albedo_layer;       // atrous-recursive: substring of the render element that holds the albedo; empty: the filter runs on colour
     float albedo_floor = 1e-3f;     // --albedo-floor: lower bound of the divisor (mid_albedo_params.floor)
     bool albedo_floor_given = false;
+    int firefly_rank = 0, firefly_radius = 1;       // atrous-recursive: --firefly-rank 1..4 switches the clamp on (mid_firefly_params); 0: off
+    float firefly_gain = 1.f, firefly_floor = 0.f;
+    const char *firefly_other = nullptr;            // the first of --firefly-radius / --firefly-gain / --firefly-floor given
     int search_lo = -7, search_hi = 7, patch_lo = -3, patch_hi = 3;   // shaders/nonlocal.comp:5-6, half-open
     int temporal_k = -1;            // <0: the reference's frame list; >=0: window t-k..t+k of the sorted sequence
     int cpu_radius = 10;            // windowSize, src/main.cpp:1819
@@ -718,6 +721,8 @@ public:
         std::vector<const void *> albedo_ptrs(albedoImgs.size());
         for (size_t i = 0; i < albedoImgs.size(); ++i) albedo_ptrs[i] = albedoImgs[i].data();
         if (!albedoNames.empty()) std::cout << "\talbedo " << albedoNames[0] << " floor " << opt.albedo_floor << "\n";
+        if (opt.firefly_rank)
+            std::cout << "\tfirefly radius " << opt.firefly_radius << " rank " << opt.firefly_rank << " gain " << opt.firefly_gain << " floor " << opt.firefly_floor << "\n";
         std::vector<const void *> motion_ptrs(motionPlanes.size());
         for (size_t i = 0; i < motionPlanes.size(); ++i) motion_ptrs[i] = motionPlanes[i].data();
         if (!motionNames.empty()) std::cout << "\tmotion " << motionNames[0] << " scale " << opt.motion_sx << " " << opt.motion_sy << "\n";
@@ -788,9 +793,11 @@ public:
             case SEQ_ATROUS_RECURSIVE: {   // per frame, in order: the spatial moments, the accumulation into the history, the variance-guided passes
                 const mid_temporal_accum_params ap{bpp.width, bpp.height, opt.alpha, opt.alpha_moments, opt.history_max, 4.f, bpp.format};
                 const mid_atrous_variance_params vp{bpp.width, bpp.height, 0, opt.passes, opt.atrous_sigma_lum, opt.atrous_epsilon, bpp.format};
-                // (albedo: the chain runs on illumination -- demodulated first, modulated into the output; NULL is the plain call)
-                MID_CHECK(mid_sequence_atrous_recursive_albedo(c, &ap, &vp, jointSigma.data(), frames, nf, lp, L, motion, albedo, opt.albedo_floor, opt.feedback,
-                                                               opt.warmup, start, count, outs, out_fmt, 1, t)); break;
+                // (albedo: the chain runs on illumination -- demodulated first, modulated into the output; NULL is the plain call.
+                // firefly: the clamp in front of the chain, after the demodulation; NULL is the call without it)
+                const mid_firefly_params fp{bpp.width, bpp.height, opt.firefly_radius, opt.firefly_rank, opt.firefly_gain, opt.firefly_floor, bpp.format & 0xff};
+                MID_CHECK(mid_sequence_atrous_recursive_firefly(c, &ap, &vp, jointSigma.data(), frames, nf, lp, L, motion, albedo, opt.albedo_floor,
+                                                                opt.firefly_rank ? &fp : nullptr, opt.feedback, opt.warmup, start, count, outs, out_fmt, 1, t)); break;
             }
             case SEQ_NLM_JOINT:            // one patch weight from all layers (jointSigma: the h of each layer)
                 MID_CHECK(mid_sequence_nlm_joint(c, &np, jointSigma.data(), frames, nf, lp, L, kk, start, count, outs, out_fmt, 1, t)); break;
@@ -1054,6 +1061,14 @@ static void usage()
         "                            filtered, and the albedo is multiplied back into the output, so a texture neither stops the filter\n"
         "                            nor is blurred.  Without it the filter runs on colour.  No match or several are refused\n"
         "  --albedo-floor X          atrous-recursive with --albedo-layer: lower bound of the divisor, finite and > 0 (default 0.001)\n"
+        "  --firefly-rank K          atrous-recursive: 1..4 switches the firefly clamp on, in front of the accumulation and after the\n"
+        "                            demodulation: a pixel brighter than G times the K-th largest finite luminance of its neighbourhood\n"
+        "                            is scaled down to that limit, a pixel with a NaN or Inf channel becomes a grey of the limit, so\n"
+        "                            neither a firefly nor a NaN enters the history.  K = 2 also removes fireflies that come in pairs\n"
+        "  --firefly-radius R        with --firefly-rank: 1 | 2, a 3x3 or 5x5 neighbourhood (default 1)\n"
+        "  --firefly-gain G          with --firefly-rank: factor on the limit, finite and > 0 (default 1)\n"
+        "  --firefly-floor X         with --firefly-rank: a luminance that is always let through, finite and >= 0, in illumination\n"
+        "                            units with --albedo-layer (default 0)\n"
         "  --temporal-k K            multiframe: frames t-K..t+K of the sorted sequence instead of the reference's list\n"
         "  --animation               denoise EVERY sibling frame with temporal NLM (window +-K, default 2) instead of the mode list\n"
         "  --animation-filter F      animation mode: nlm (default: temporal NLM), or the bilateral of every frame -- bilateral\n"
@@ -1096,7 +1111,8 @@ static void usage()
         "                            or atrous-recursive: recursive temporal accumulation (a history of colour and luminance moments,\n"
         "                            blended as lerp(history, frame, max(1/N, alpha))), then the variance-guided passes, frame after\n"
         "                            frame (--alpha, --alpha-moments, --history-max, --feedback, --warmup, --motion-layer,\n"
-        "                            --motion-scale, --albedo-layer, --albedo-floor; --passes, --sigma-layers, --atrous-sigma-lum,\n"
+        "                            --motion-scale, --albedo-layer, --albedo-floor, --firefly-rank, --firefly-radius, --firefly-gain, --firefly-floor;\n"
+        "                            --passes, --sigma-layers, --atrous-sigma-lum,\n"
         "                            --atrous-epsilon as atrous-variance;\n"
         "                            it ignores --temporal-k; not with --halo rccl), outputs output-animation-nonlinear-atrous-recursive-*.\n"
         "                            With --gpus N every frame block starts its history --warmup frames before its block: a sharded\n"
@@ -1177,6 +1193,25 @@ int main(int argc, char **argv)
         else if (a == "--motion-layer") opt.motion_layer = next();
         else if (a == "--albedo-layer") opt.albedo_layer = next();
         else if (a == "--albedo-floor") { opt.albedo_floor = (float)atof(next()); opt.albedo_floor_given = true; }
+        else if (a == "--firefly-rank") {
+            opt.firefly_rank = atoi(next());
+            if (opt.firefly_rank < 1 || opt.firefly_rank > 4) { std::cerr << "--firefly-rank " << opt.firefly_rank << " is outside 1..4\n"; return EXIT_FAILURE; }
+        }
+        else if (a == "--firefly-radius") {
+            opt.firefly_radius = atoi(next());
+            if (!opt.firefly_other) opt.firefly_other = "--firefly-radius";
+            if (opt.firefly_radius != 1 && opt.firefly_radius != 2) { std::cerr << "--firefly-radius " << opt.firefly_radius << " is neither 1 nor 2\n"; return EXIT_FAILURE; }
+        }
+        else if (a == "--firefly-gain") {
+            opt.firefly_gain = (float)atof(next());
+            if (!opt.firefly_other) opt.firefly_other = "--firefly-gain";
+            if (!(std::isfinite(opt.firefly_gain) && opt.firefly_gain > 0.f)) { std::cerr << "--firefly-gain " << opt.firefly_gain << " must be finite and > 0\n"; return EXIT_FAILURE; }
+        }
+        else if (a == "--firefly-floor") {
+            opt.firefly_floor = (float)atof(next());
+            if (!opt.firefly_other) opt.firefly_other = "--firefly-floor";
+            if (!(std::isfinite(opt.firefly_floor) && opt.firefly_floor >= 0.f)) { std::cerr << "--firefly-floor " << opt.firefly_floor << " must be finite and >= 0\n"; return EXIT_FAILURE; }
+        }
         else if (a == "--motion-scale") {
             if (sscanf(next(), "%f,%f", &opt.motion_sx, &opt.motion_sy) != 2) { std::cerr << "--motion-scale needs sx,sy\n"; usage(); return EXIT_FAILURE; }
         }
@@ -1218,6 +1253,11 @@ int main(int argc, char **argv)
         return EXIT_FAILURE;
     }
     if (opt.albedo_floor_given && opt.albedo_layer.empty()) { std::cerr << "--albedo-floor needs --albedo-layer\n"; return EXIT_FAILURE; }
+    if ((opt.firefly_rank || opt.firefly_other) && !(opt.animation && opt.animation_filter == "atrous-recursive")) {
+        std::cerr << (opt.firefly_rank ? "--firefly-rank" : opt.firefly_other) << " applies to --animation --animation-filter atrous-recursive only\n";
+        return EXIT_FAILURE;
+    }
+    if (opt.firefly_other && !opt.firefly_rank) { std::cerr << opt.firefly_other << " needs --firefly-rank\n"; return EXIT_FAILURE; }
     if (listed("atrous-recursive")) {
         std::cerr << "--modes atrous-recursive: the recursion needs a sequence; it is an animation filter (--animation --animation-filter atrous-recursive)\n";
         return EXIT_FAILURE;

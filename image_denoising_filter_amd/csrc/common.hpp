@@ -284,6 +284,11 @@ int demodulate_out(mid_ctx *ctx, const mid_albedo_params *p, const void *in, con
 int modulate_out(mid_ctx *ctx, const mid_albedo_params *p, const mid_pixel *in, const void *albedo, void *out, int out_fmt, hipStream_t s);
 int albedo_check(const mid_albedo_params *p, const char *who);
 
+// mid_firefly_clamp without its checks (the caller has made them), one launch on `s`: firefly.hip; used by the frame pipeline
+// (mid_sequence_atrous_recursive_firefly), not exported.  firefly_check: the size, radius, rank, gain, floor and the format word.
+int firefly_clamp_out(mid_ctx *ctx, const mid_firefly_params *p, const void *in, mid_pixel *out, hipStream_t s);
+int firefly_check(const mid_firefly_params *p, const char *who);
+
 // ROCTx ranges (csrc/markers.cpp): no-ops unless the process already holds a ROCTx (rocprofv3 --marker-trace preloads one).
 bool markers_active();
 void range_push(const char *name);

@@ -691,17 +691,22 @@ extern "C" int mid_sequence_atrous_variance(mid_ctx *ctx, const mid_atrous_varia
 // With an albedo plane per frame (section a4k) the chain runs on ILLUMINATION: frame t is demodulated into an RGBA32F plane of the
 // block, the three steps read that plane as an RGBA32F frame, the passes' final level goes as RGBA32F into one more plane, and
 // mid_modulate with frame t's albedo stores the output.  The histories hold illumination.  The block then has 164 B per pixel.
-extern "C" int mid_sequence_atrous_recursive_albedo(mid_ctx *ctx, const mid_temporal_accum_params *ap, const mid_atrous_variance_params *vp,
-                                                    const float *layer_sigma, const void *const *host_frames, int n_frames,
-                                                    const void *const *host_layers, int n_layers, const void *const *host_motion,
-                                                    const void *const *host_albedo, float albedo_floor, int feedback, int warmup, int first,
-                                                    int count, void *const *host_out, int out_format, int overlap, float *timings_ms)
+// With firefly parameters (section a4l) mid_firefly_clamp runs in front of the three steps, after the demodulation: it reads the
+// illumination plane, or the frame itself, into one more RGBA32F plane of the block (16 B per pixel more), which the three steps
+// read as an RGBA32F frame.
+extern "C" int mid_sequence_atrous_recursive_firefly(mid_ctx *ctx, const mid_temporal_accum_params *ap, const mid_atrous_variance_params *vp,
+                                                     const float *layer_sigma, const void *const *host_frames, int n_frames,
+                                                     const void *const *host_layers, int n_layers, const void *const *host_motion,
+                                                     const void *const *host_albedo, float albedo_floor, const mid_firefly_params *ff, int feedback,
+                                                     int warmup, int first, int count, void *const *host_out, int out_format, int overlap,
+                                                     float *timings_ms)
 {
     Bind b(ctx, nullptr);
     if (b.rc) return b.rc;
-    const char *who = host_albedo ? "sequence_atrous_recursive_albedo" : "sequence_atrous_recursive";
-    if (int rc = refuse_if_recording(ctx->compute, host_albedo ? "mid_sequence_atrous_recursive_albedo (four streams, host-side waits)"
-                                                               : "mid_sequence_atrous_recursive (four streams, host-side waits)")) return rc;
+    const char *who = ff ? "sequence_atrous_recursive_firefly" : host_albedo ? "sequence_atrous_recursive_albedo" : "sequence_atrous_recursive";
+    if (int rc = refuse_if_recording(ctx->compute, ff ? "mid_sequence_atrous_recursive_firefly (four streams, host-side waits)"
+                                                   : host_albedo ? "mid_sequence_atrous_recursive_albedo (four streams, host-side waits)"
+                                                                 : "mid_sequence_atrous_recursive (four streams, host-side waits)")) return rc;
     if (int rc = temporal_accumulate_check(ap, who, layer_sigma, host_layers != nullptr, n_layers)) return rc;
     if (int rc = atrous_variance_check(vp, who, layer_sigma, host_layers != nullptr, n_layers)) return rc;
     MID_REQUIRE(vp->first_pass == 0, "%s: first_pass %d: the passes start on the accumulated colour (continue a filter with mid_atrous_variance)", who, vp->first_pass);
@@ -712,6 +717,16 @@ extern "C" int mid_sequence_atrous_recursive_albedo(mid_ctx *ctx, const mid_temp
     MID_REQUIRE(warmup >= 0, "%s: warmup %d < 0", who, warmup);
     const mid_albedo_params dp{ap->width, ap->height, albedo_floor, ap->format};     // demodulate: the frames' format, the albedo in the guide format
     if (host_albedo) { if (int rc = albedo_check(&dp, who)) return rc; }
+    mid_firefly_params fq{};                                // the clamp reads the illumination plane (RGBA32F) or the frame itself
+    if (ff) {
+        if (int rc = firefly_check(ff, who)) return rc;
+        MID_REQUIRE(ff->width == ap->width && ff->height == ap->height, "%s: the firefly parameters are for %dx%d, the frames are %dx%d", who, ff->width,
+                    ff->height, ap->width, ap->height);
+        MID_REQUIRE(ff->format == fmt_frames(ap->format), "%s: the firefly format 0x%x is not the frames' format %d without guide bits", who, ff->format,
+                    fmt_frames(ap->format));
+        fq = *ff;
+        if (host_albedo) fq.format = MID_FMT_RGBA32F;
+    }
     const mid_atrous_moments_params mp{ap->width, ap->height, ap->format};
     if (int rc = atrous_moments_check(&mp, who, layer_sigma, host_layers != nullptr, n_layers, 1, 0)) return rc;
     if (int rc = check_sequence({who, "n_frames", true, true}, host_frames, n_frames, host_layers, n_layers, 0, first, count, host_out, out_format)) return rc;
@@ -747,9 +762,9 @@ extern "C" int mid_sequence_atrous_recursive_albedo(mid_ctx *ctx, const mid_temp
     mid_temporal_accum_params aq = *ap;
     mid_atrous_moments_params mq = mp;
     const mid_albedo_params mo{ap->width, ap->height, albedo_floor, fp.format};       // modulate: RGBA32F in
-    if (host_albedo) aq.format = mq.format = fp.format;
+    if (host_albedo || ff) aq.format = mq.format = fp.format;
     Stage st{who, ap->width, ap->height, fmt_frames(ap->format), npix * fmt_bytes(gfmt), host_layers, n_layers, true, "atrous recursive %d"};
-    st.level_bytes = npix * 16 * 7 + 5 * plane + (host_albedo ? npix * 32 : 0); st.n_levels = 1;
+    st.level_bytes = npix * 16 * 7 + 5 * plane + (host_albedo ? npix * 32 : 0) + (ff ? npix * 16 : 0); st.n_levels = 1;
     st.in_order = true; st.host_motion = host_motion; st.skip = skip; st.host_albedo = host_albedo;
     const int n_side = n_layers + (host_motion ? 1 : 0) + (host_albedo ? 1 : 0);
     int step = 0;                                           // frames accumulated so far: the launches come in output order
@@ -762,6 +777,7 @@ extern "C" int mid_sequence_atrous_recursive_albedo(mid_ctx *ctx, const mid_temp
         float *vs = (float *)fb, *vt = (float *)(fb + plane), *v1 = (float *)(fb + 2 * plane);
         float *vlevel[2] = {(float *)(fb + 3 * plane), (float *)(fb + 4 * plane)};
         mid_pixel *illum = (mid_pixel *)(fb + 5 * plane), *fin = illum + npix;        // (with albedo only: the block ends before them otherwise)
+        mid_pixel *clamped = host_albedo ? fin + npix : illum;                        // (with firefly parameters only: the block's last plane)
         for (int i = 0; i < bn; ++i, ++step) {
             const int t = t0 + i, cur = step & 1, prev = cur ^ 1;
             const uint32_t *const *ly = lt + (size_t)t * n_side;
@@ -772,6 +788,10 @@ extern "C" int mid_sequence_atrous_recursive_albedo(mid_ctx *ctx, const mid_temp
             if (alb) {
                 if (int rc = demodulate_out(ctx, &dp, tbl[t], alb, illum, s)) return rc;
                 frame = illum;
+            }
+            if (ff) {
+                if (int rc = firefly_clamp_out(ctx, &fq, frame, clamped, s)) return rc;
+                frame = clamped;
             }
             // the passes' last level: the output itself, or with albedo the plane that mid_modulate reads
             void *last = alb ? (void *)fin : out[i];
@@ -798,6 +818,16 @@ extern "C" int mid_sequence_atrous_recursive_albedo(mid_ctx *ctx, const mid_temp
     std::vector<void *> outs((size_t)skip + count, nullptr);
     for (int i = 0; i < count; ++i) outs[(size_t)skip + i] = host_out[i];
     return run_pipeline(ctx, st, launch, host_frames, n_frames, 1, s0, skip + count, outs.data(), out_format, overlap, timings_ms);
+}
+
+extern "C" int mid_sequence_atrous_recursive_albedo(mid_ctx *ctx, const mid_temporal_accum_params *ap, const mid_atrous_variance_params *vp,
+                                                    const float *layer_sigma, const void *const *host_frames, int n_frames,
+                                                    const void *const *host_layers, int n_layers, const void *const *host_motion,
+                                                    const void *const *host_albedo, float albedo_floor, int feedback, int warmup, int first,
+                                                    int count, void *const *host_out, int out_format, int overlap, float *timings_ms)
+{
+    return mid_sequence_atrous_recursive_firefly(ctx, ap, vp, layer_sigma, host_frames, n_frames, host_layers, n_layers, host_motion, host_albedo, albedo_floor,
+                                                 nullptr, feedback, warmup, first, count, host_out, out_format, overlap, timings_ms);
 }
 
 extern "C" int mid_sequence_atrous_recursive(mid_ctx *ctx, const mid_temporal_accum_params *ap, const mid_atrous_variance_params *vp,

@@ -889,6 +889,67 @@ int mid_sequence_atrous_recursive_albedo(mid_ctx *ctx, const mid_temporal_accum_
                                          float albedo_floor, int feedback /* 0 | 1 */, int warmup /* >= 0 */, int first, int count,
                                          void *const *host_out, int out_format, int overlap, float *timings_ms);
 
+/* ---- a4l: firefly clamp and NaN repair --------------------------------------------------------
+ * Every stage of the recursive chain is IEEE arithmetic in which a NaN stays a NaN (a4i, a4j, a4k).  Fed by a path tracer that is
+ * the wrong behaviour for the chain as a whole: one NaN or Inf texel enters the histories, is spread +-62 pixels by five passes
+ * and, with feedback 1, never leaves; a finite outlier of 10^3 - 10^4 x its surroundings opens the luminance term of a4i where it
+ * sits and is smeared into a blob that the history keeps for about 1 / alpha frames.  mid_firefly_clamp is the outlier clamp that
+ * production SVGF puts in front of the temporal stage: one pass that limits the luminance of every pixel by that of its
+ * neighbourhood and repairs non-finite pixels from it.
+ * Per pixel p, with C the texel widened as a4i widens a frame and l() a4i's luminance, literally
+ * fma(0.0722f, b, fma(0.7152f, g, 0.2126f * r)):
+ *   neighbours  q = p + (i, j), |i|, |j| <= radius, (i, j) != (0, 0), q inside the image.  A neighbour is VALID iff l(C(q)) is
+ *               finite (NaN and +-Inf fail); n is the number of valid neighbours.
+ *   n == 0      (a 1 x 1 frame, or a surrounding that is all non-finite): out = C in all four channels.
+ *   limit       m = the min(rank, n)-th largest valid neighbour luminance, as a multiset (equal values count separately);
+ *               T = fmaxf(gain * m, floor): one multiplication and one fmaxf; T >= 0.
+ *   centre      lc = l(C(p)).   lc finite and lc <= T: out = C, bit for bit.
+ *               lc finite and lc > T: s = T / lc (one IEEE division), out_c = C_c * s for c in {R, G, B} (one multiplication each).
+ *               lc not finite (which is the case exactly when a colour channel is non-finite): out_R = out_G = out_B = T -- the
+ *               pixel is repaired to a grey of the limit luminance.
+ *   alpha       passes through unchanged in every case.  A non-finite ALPHA is not repaired.
+ * One pass, no iteration: every limit is taken from the INPUT's luminances, so the result depends on no evaluation order, and the
+ * selection is exact (max and min only).  Precision: the bits of the formulas in IEEE binary32 (-ffp-contract=off, no fast-math)
+ * -- those of a numpy float32 evaluation; NaN payloads and signs are left open, as in a4k.
+ * Identity: a frame that is constant apart from one texel whose RGB is 4096 x its surroundings comes back, with rank 1, gain 1,
+ * floor 0, as the constant frame bit for bit (s is exactly 2^-12).  Two such texels side by side survive rank 1 -- each is the
+ * other's maximum -- and are removed by rank 2; a 2 x 2 block of them needs rank 4.
+ * floor is a luminance that is always let through, in the units of `in`: in the frame pipeline the clamp runs AFTER
+ * demodulation, so there it is in illumination units.
+ * Class: tiled (csrc/firefly.hip): a workgroup of four waves covers 64 x 16 pixels from an LDS tile of
+ * (64 + 2 radius) x (16 + 2 radius) luminances; index arithmetic in size_t.
+ * MID_ERR_INVALID before anything is queued, `out` untouched: a NULL pointer; radius outside {1, 2}; rank outside 1..4; gain not
+ * finite or <= 0; floor not finite or < 0; an unknown frame format, or guide bits set in format; `in` not aligned to its texel
+ * size, `out` not to 16 bytes; width or height < 1, or 2^30 pixels and more; `out` overlapping `in` in any way -- the pass is a
+ * stencil, so exactly in place is refused too, unlike a4k. */
+typedef struct mid_firefly_params {
+    int32_t width, height;
+    int32_t radius;   /* 1 | 2: 3x3 or 5x5 neighbourhood, centre excluded */
+    int32_t rank;     /* 1..4: the k-th largest neighbour luminance is the limit */
+    float   gain;     /* finite, > 0; default 1 */
+    float   floor;    /* finite, >= 0; a luminance always let through; default 0 */
+    int32_t format;   /* MID_FMT_* of `in`; the guide field must be 0 */
+} mid_firefly_params;
+int mid_firefly_clamp(mid_ctx *ctx, const mid_firefly_params *p, const void *in, mid_pixel *out /* RGBA32F */, void *stream);
+/* mid_sequence_atrous_recursive_albedo with the clamp in front of the chain.  fp == NULL: it IS that call, and that entry point is
+ * this one with NULL.  Otherwise, per frame t: (0) mid_demodulate, if there is an albedo; (0') mid_firefly_clamp into one more
+ * RGBA32F plane of the cache block -- it reads the illumination plane as RGBA32F, or the frame itself in the frames' format;
+ * (1) - (3) on that plane with frame format RGBA32F; (4) mid_modulate, if there is an albedo.  The clamp runs AFTER demodulation:
+ * fp->floor is in illumination units.  Output t has, bit for bit, the result of that chain of public calls.  The cache block grows
+ * by 16 B per pixel: 148 B per pixel without albedo, 180 with.  No new host plane, side slot or upload; everything runs on the one
+ * in-order kernel stream.
+ * MID_ERR_INVALID before anything is queued, host_out and timings_ms untouched: the refusals of
+ * mid_sequence_atrous_recursive_albedo; those of mid_firefly_clamp's parameters; fp->width / fp->height other than ap's; fp->format
+ * other than the frames' format with no guide bits (both values are named). */
+int mid_sequence_atrous_recursive_firefly(mid_ctx *ctx, const mid_temporal_accum_params *ap, const mid_atrous_variance_params *vp,
+                                          const float *layer_sigma, const void *const *host_frames, int n_frames,
+                                          const void *const *host_layers, int n_layers /* 1..16 */,
+                                          const void *const *host_motion /* n_frames float2 planes, or NULL */,
+                                          const void *const *host_albedo /* n_frames planes in the guide format, or NULL */,
+                                          float albedo_floor, const mid_firefly_params *fp /* NULL: no clamp */,
+                                          int feedback /* 0 | 1 */, int warmup /* >= 0 */, int first, int count,
+                                          void *const *host_out, int out_format, int overlap, float *timings_ms);
+
 /* ---- a5: normalize ----------------------------------------------------------------------
  * One dispatch of shaders/normalize.comp (RecordCommandsOfExecuteAndTransfer(normKernel=true)):
  * out = weightColor / normWeight, or (1,0,1,1) where normWeight == 0; bindings {0: out; 1: W}. */

@@ -39,6 +39,8 @@ int mid::temporal_accumulate_check(const mid_temporal_accum_params *, const char
 int mid::demodulate_out(mid_ctx *, const mid_albedo_params *, const void *, const void *, mid_pixel *, hipStream_t) { return MID_ERR_UNSUPPORTED; }   // (albedo.hip)
 int mid::modulate_out(mid_ctx *, const mid_albedo_params *, const mid_pixel *, const void *, void *, int, hipStream_t) { return MID_ERR_UNSUPPORTED; }   // (albedo.hip)
 int mid::albedo_check(const mid_albedo_params *, const char *) { return MID_ERR_UNSUPPORTED; }   // (albedo.hip)
+int mid::firefly_clamp_out(mid_ctx *, const mid_firefly_params *, const void *, mid_pixel *, hipStream_t) { return MID_ERR_UNSUPPORTED; }   // (firefly.hip)
+int mid::firefly_check(const mid_firefly_params *, const char *) { return MID_ERR_UNSUPPORTED; }   // (firefly.hip)
 int mid::nlm_check_params(const mid_nlm_params *) { return MID_ERR_UNSUPPORTED; }   // (nlm.hip)
 int mid::bilateral_check_params(const mid_bilateral_params *, const char *, bool) { return MID_ERR_UNSUPPORTED; }   // (bilateral.hip)
 
