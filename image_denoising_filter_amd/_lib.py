@@ -80,6 +80,12 @@ class FireflyParams(ctypes.Structure):
                 ("gain", ctypes.c_float), ("floor", ctypes.c_float), ("format", ctypes.c_int32)]
 
 
+class ColorBoundsParams(ctypes.Structure):
+    """mid_color_bounds_params (section a4m)."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("radius", ctypes.c_int32), ("gamma", ctypes.c_float),
+                ("format", ctypes.c_int32)]
+
+
 class NormalizeParams(ctypes.Structure):
     _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32)]
 
@@ -168,6 +174,14 @@ _SIGNATURES = {
                                                              c_void_pp, ctypes.c_float, ctypes.POINTER(FireflyParams), ctypes.c_int, ctypes.c_int,
                                                              ctypes.c_int, ctypes.c_int, c_void_pp, ctypes.c_int, ctypes.c_int,
                                                              ctypes.POINTER(ctypes.c_float)]),
+    "mid_color_bounds": (ctypes.c_int, [_P, ctypes.POINTER(ColorBoundsParams), _P, _P, _P, _P]),
+    "mid_temporal_accumulate_clip": (ctypes.c_int, [_P, ctypes.POINTER(TemporalAccumParams), ctypes.POINTER(ctypes.c_float), _P, c_void_pp, c_void_pp,
+                                                    ctypes.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mid_sequence_atrous_recursive_clip": (ctypes.c_int, [_P, ctypes.POINTER(TemporalAccumParams), ctypes.POINTER(AtrousVarianceParams),
+                                                          ctypes.POINTER(ctypes.c_float), c_void_pp, ctypes.c_int, c_void_pp, ctypes.c_int, c_void_pp,
+                                                          c_void_pp, ctypes.c_float, ctypes.POINTER(FireflyParams), ctypes.POINTER(ColorBoundsParams),
+                                                          ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_pp, ctypes.c_int, ctypes.c_int,
+                                                          ctypes.POINTER(ctypes.c_float)]),
     "mid_normalize": (ctypes.c_int, [_P, ctypes.POINTER(NormalizeParams), _P, _P, _P]),
     "mid_unpack_u8": (ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_int, _P, _P]),
     "mid_pack_u8": (ctypes.c_int, [_P, _P, ctypes.c_size_t, _P, _P]),

@@ -15,7 +15,7 @@ import weakref
 
 import numpy as np
 
-from ._lib import AlbedoParams, AtrousMomentsParams, AtrousParams, AtrousVarianceParams, BilateralParams, FireflyParams, Image, NlmParams, NormalizeParams, TemporalAccumParams, c_void_pp, lib
+from ._lib import AlbedoParams, AtrousMomentsParams, AtrousParams, AtrousVarianceParams, BilateralParams, ColorBoundsParams, FireflyParams, Image, NlmParams, NormalizeParams, TemporalAccumParams, c_void_pp, lib
 
 FMT_RGBA32F, FMT_RGBA8, FMT_RGBA16F = 0, 1, 2
 
@@ -557,14 +557,18 @@ class Context:
         return (out, self.download(d_vout, (h, w), np.float32)) if return_variance else out
 
     def temporal_accumulate(self, frame, layers, prev_layers, sigmas, hist=None, motion=None, var_spatial=None, alpha=0.2,
-                            alpha_moments=0.2, history_max=32, history_full=4):
+                            alpha_moments=0.2, history_max=32, history_full=4, clip_lo=None, clip_hi=None):
         """One step of the recursive temporal accumulation (mid_temporal_accumulate): the history `hist` = (colour, state), two
         float32 (h, w, 4) planes of the previous step (state = (m1, m2, N, 0)), or None for no history, is reprojected by `motion`
         (float32 (h, w, 2), pixels: p was at p + motion(p); None = zero motion), weighed by the guide layers (`layers` of this frame
         against `prev_layers` of the previous one: 0..16 (h, w, 4) layers each, uint8, float16 or float32 and all of one dtype;
         prev_layers None = `layers`) and blended with `frame`.  var_spatial: a float32 (h, w) plane (atrous_moments at k = 0) or
-        None.  Returns (colour, state, variance): float32 (h, w, 4), (h, w, 4) and (h, w)."""
+        None.  clip_lo, clip_hi: two float32 (h, w, 4) planes (color_bounds of the frame, usually) to which the reprojected history
+        is clipped before the blend (mid_temporal_accumulate_clip), or both None.
+        Returns (colour, state, variance): float32 (h, w, 4), (h, w, 4) and (h, w)."""
         who = "temporal_accumulate"
+        if (clip_lo is None) != (clip_hi is None):
+            raise ValueError(f"{who}: clip_lo and clip_hi are one box: both or neither")
         (frame,) = _same_frames([frame], who)
         h, w = frame.shape[:2]
         layers = list(layers)
@@ -572,22 +576,26 @@ class Context:
         n_layers, flat = _flat_layers([layers, prev_layers], 2, h, w, who, _GUIDE_DTYPES)
         hc, hs = (None, None) if hist is None else hist
         planes = []
-        for name, a, shape in (("hist[0]", hc, (h, w, 4)), ("hist[1]", hs, (h, w, 4)), ("motion", motion, (h, w, 2)), ("var_spatial", var_spatial, (h, w))):
+        for name, a, shape in (("hist[0]", hc, (h, w, 4)), ("hist[1]", hs, (h, w, 4)), ("motion", motion, (h, w, 2)), ("var_spatial", var_spatial, (h, w)),
+                               ("clip_lo", clip_lo, (h, w, 4)), ("clip_hi", clip_hi, (h, w, 4))):
             if a is not None:
                 a = np.ascontiguousarray(a, dtype=np.float32)
                 if a.shape != shape:
                     raise ValueError(f"{who}: {name} must be {shape}, got {a.shape}")
                 a = self.upload(a)
             planes.append(a)                                   # (the buffers live until the call has been downloaded)
-        p_hc, p_hs, p_mv, p_vs = (d.ptr if d is not None else None for d in planes)
+        p_hc, p_hs, p_mv, p_vs, p_lo, p_hi = (d.ptr if d is not None else None for d in planes)
         p = TemporalAccumParams(w, h, alpha, alpha_moments, history_max, history_full, _guide_fmt(_fmt_of(frame), flat, who))
         d_in = self.upload(frame)
         d_l = [self.upload(l) for l in flat]
         d_col, d_st, d_var = self.alloc(w * h * 16), self.alloc(w * h * 16), self.alloc(w * h * 4)
-        _check(lib.mid_temporal_accumulate(self.handle, ctypes.byref(p), _layer_sigmas(sigmas, n_layers, who), d_in.ptr,
-                                           (ctypes.c_void_p * max(n_layers, 1))(*[d.ptr for d in d_l[:n_layers]]),
-                                           (ctypes.c_void_p * max(n_layers, 1))(*[d.ptr for d in d_l[n_layers:]]), n_layers, p_mv, p_hc, p_hs, p_vs,
-                                           d_col.ptr, d_st.ptr, d_var.ptr, None), "mid_temporal_accumulate")
+        head = (self.handle, ctypes.byref(p), _layer_sigmas(sigmas, n_layers, who), d_in.ptr,
+                (ctypes.c_void_p * max(n_layers, 1))(*[d.ptr for d in d_l[:n_layers]]),
+                (ctypes.c_void_p * max(n_layers, 1))(*[d.ptr for d in d_l[n_layers:]]), n_layers, p_mv, p_hc, p_hs, p_vs)
+        if clip_lo is None:
+            _check(lib.mid_temporal_accumulate(*head, d_col.ptr, d_st.ptr, d_var.ptr, None), "mid_temporal_accumulate")
+        else:
+            _check(lib.mid_temporal_accumulate_clip(*head, p_lo, p_hi, d_col.ptr, d_st.ptr, d_var.ptr, None), "mid_temporal_accumulate_clip")
         return self.download(d_col, (h, w, 4), np.float32), self.download(d_st, (h, w, 4), np.float32), self.download(d_var, (h, w), np.float32)
 
     def _albedo_plane(self, albedo, shape, who):
@@ -632,6 +640,18 @@ class Context:
         d_in, d_out = self.upload(frame), self.alloc(w * h * 16)
         _check(lib.mid_firefly_clamp(self.handle, ctypes.byref(p), d_in.ptr, d_out.ptr, None), "mid_firefly_clamp")
         return self.download(d_out, (h, w, 4), np.float32)
+
+    def color_bounds(self, frame, radius=1, gamma=1.0):
+        """The neighbourhood colour box of a frame (mid_color_bounds): per pixel and colour channel mean -+ gamma standard deviations
+        over the finite texels of the (2 radius + 1)^2 window, centre included; .w of both planes is the number of those texels
+        (-Inf / +Inf and 0 where there is none).  frame: (h, w, 4) uint8, float16 or float32.  Returns (lo, hi), float32 (h, w, 4)."""
+        (frame,) = _same_frames([frame], "color_bounds")
+        radius, gamma = _clip_args(gamma, radius, "color_bounds", off_allowed=False)
+        h, w = frame.shape[:2]
+        p = ColorBoundsParams(w, h, radius, gamma, _fmt_of(frame))
+        d_in, d_lo, d_hi = self.upload(frame), self.alloc(w * h * 16), self.alloc(w * h * 16)
+        _check(lib.mid_color_bounds(self.handle, ctypes.byref(p), d_in.ptr, d_lo.ptr, d_hi.ptr, None), "mid_color_bounds")
+        return self.download(d_lo, (h, w, 4), np.float32), self.download(d_hi, (h, w, 4), np.float32)
 
     def normalize(self, W):
         """normalize.comp."""
@@ -974,15 +994,17 @@ class Context:
     def sequence_atrous_recursive_pinned(self, hin, hout, w, h, fmt, hlayers, n_layers, sigmas, hmotion=None, feedback=1, warmup=16, first=0,
                                          count=None, passes=5, sigma_lum=4.0, epsilon=1e-3, alpha=0.2, alpha_moments=0.2, history_max=32,
                                          history_full=4, overlap=True, out_dtype=None, halbedo=None, albedo_floor=1e-3,
-                                         firefly_rank=0, firefly_radius=1, firefly_gain=1.0, firefly_floor=0.0):
-        """mid_sequence_atrous_recursive[_albedo | _firefly] on host pointers the caller already holds: nothing but the C call.  hin,
+                                         firefly_rank=0, firefly_radius=1, firefly_gain=1.0, firefly_floor=0.0, clip_gamma=None, clip_radius=1):
+        """mid_sequence_atrous_recursive[_albedo | _firefly | _clip] on host pointers the caller already holds: nothing but the C call.  hin,
         hlayers, hout as for sequence_atrous_variance_pinned; hmotion: one pointer per frame to a float32 (h, w, 2) plane, or None: zero
         motion; halbedo: one pointer per frame to an (h, w, 4) albedo plane in the layers' format, or None: no demodulation;
-        firefly_rank 1..4: mid_firefly_clamp in front of the chain (0: the existing call).
+        firefly_rank 1..4: mid_firefly_clamp in front of the chain (0: the existing call); clip_gamma: the history is clipped to
+        mid_color_bounds(clip_radius, clip_gamma) of the plane the accumulation reads (None: the existing call).
         Returns (wall_ms of the whole call, kernel_ms, copy_ms)."""
         n = len(hin)
         count = n - first if count is None else count
         firefly = _firefly_args(firefly_rank, firefly_radius, firefly_gain, firefly_floor, "sequence_atrous_recursive")
+        clip = _clip_args(clip_gamma, clip_radius, "sequence_atrous_recursive")
         if len(hout) < count:
             raise ValueError(f"{count} outputs, {len(hout)} output buffers given")
         if len(hlayers) != n * n_layers:
@@ -998,9 +1020,16 @@ class Context:
                 (ctypes.c_void_p * max(len(hlayers), 1))(*hlayers), n_layers, None if hmotion is None else (ctypes.c_void_p * n)(*hmotion))
         tail = (feedback, warmup, first, count, (ctypes.c_void_p * max(count, 1))(*hout[:max(count, 0)]), _OUT_FMT[_out_dtype(False, out_dtype)],
                 1 if overlap else 0, t)
+        fp = None
         if firefly is not None:
             radius, rank, gain, floor = firefly
             fp = FireflyParams(w, h, radius, rank, gain, floor, fmt & 0xff)
+        if clip is not None:
+            cp = ColorBoundsParams(w, h, clip[0], clip[1], fmt & 0xff)
+            _check(lib.mid_sequence_atrous_recursive_clip(*head, None if halbedo is None else (ctypes.c_void_p * n)(*halbedo), albedo_floor,
+                                                          None if fp is None else ctypes.byref(fp), ctypes.byref(cp), *tail),
+                   "mid_sequence_atrous_recursive_clip")
+        elif fp is not None:
             _check(lib.mid_sequence_atrous_recursive_firefly(*head, None if halbedo is None else (ctypes.c_void_p * n)(*halbedo), albedo_floor,
                                                              ctypes.byref(fp), *tail), "mid_sequence_atrous_recursive_firefly")
         elif halbedo is None:
@@ -1012,7 +1041,7 @@ class Context:
     def sequence_atrous_recursive(self, frames, layers, sigmas, motion=None, feedback=1, warmup=16, first=0, count=None, passes=5, sigma_lum=4.0,
                                   epsilon=1e-3, alpha=0.2, alpha_moments=0.2, history_max=32, history_full=4, overlap=True, pinned=True,
                                   pinned_out=True, out_dtype=None, albedo=None, albedo_floor=1e-3, firefly_rank=0, firefly_radius=1,
-                                  firefly_gain=1.0, firefly_floor=0.0):
+                                  firefly_gain=1.0, firefly_floor=0.0, clip_gamma=None, clip_radius=1):
         """Outputs [first, first+count) of an animation through the pipeline with the recursive temporal accumulation as its compute
         stage (mid_sequence_atrous_recursive).  From frame s = max(0, first - warmup) on, per frame t: Vs = atrous_moments([frame], k=0),
         (colour, state, var) = temporal_accumulate(frame t, layers t, layers t-1, history, motion[t], Vs), output = atrous_variance(colour,
@@ -1024,9 +1053,12 @@ class Context:
         float32, and output t is modulate(that, albedo[t], albedo_floor, out_dtype); the histories hold illumination.
         firefly_rank 1..4 (0: off) puts firefly_clamp(frame, firefly_radius, firefly_rank, firefly_gain, firefly_floor) in front of
         the chain (mid_sequence_atrous_recursive_firefly), AFTER the demodulation: firefly_floor is in illumination units then.
+        clip_gamma (None: off; finite and >= 0) clips the reprojected history of every frame to color_bounds(the plane the
+        accumulation reads, clip_radius, clip_gamma) -- temporal_accumulate(..., clip_lo, clip_hi); mid_sequence_atrous_recursive_clip.
         Returns (outputs, (wall_ms, kernel_ms, copy_ms))."""
         out_dtype = _out_dtype(False, out_dtype)
         _firefly_args(firefly_rank, firefly_radius, firefly_gain, firefly_floor, "sequence_atrous_recursive")
+        _clip_args(clip_gamma, clip_radius, "sequence_atrous_recursive")
         halb = None
         if albedo is not None:
             shape = np.asarray(frames[0]).shape[:2] + (4,)
@@ -1048,7 +1080,8 @@ class Context:
             aptrs = None if halb is None else (palb.ptrs if palb is not None else [a.ctypes.data for a in halb])
             return self._sequence_host("sequence_atrous_recursive", lambda hin, hout, w, h, fmt, hlayers, n_layers, count: self.sequence_atrous_recursive_pinned(
                 hin, hout, w, h, fmt, hlayers, n_layers, sigmas, ptrs, feedback, warmup, first, count, passes, sigma_lum, epsilon, alpha, alpha_moments,
-                history_max, history_full, overlap, out_dtype, aptrs, albedo_floor, firefly_rank, firefly_radius, firefly_gain, firefly_floor), frames, layers, _GUIDE_DTYPES, first, count, pinned, pinned_out, out_dtype)
+                history_max, history_full, overlap, out_dtype, aptrs, albedo_floor, firefly_rank, firefly_radius, firefly_gain, firefly_floor,
+                clip_gamma, clip_radius), frames, layers, _GUIDE_DTYPES, first, count, pinned, pinned_out, out_dtype)
         finally:
             for b in (pmv, palb):
                 if b is not None:
@@ -1073,6 +1106,23 @@ def _firefly_args(rank, radius, gain, floor, who, off_allowed=True):
     if not 0 <= floor <= f32_max:
         raise ValueError(f"{who}: the firefly floor must be finite and >= 0, got {floor}")
     return int(radius), int(rank), gain, floor
+
+
+def _clip_args(gamma, radius, who, off_allowed=True):
+    """The history-clip keywords of a call, checked before any GPU work: None for gamma None (the clip is off; the radius must then
+    be its default), otherwise (radius, gamma) in the ranges of mid_color_bounds_params."""
+    if off_allowed and gamma is None:
+        if radius != 1:
+            raise ValueError(f"{who}: clip_radius needs clip_gamma (it is None: the history clip is off)")
+        return None
+    if not isinstance(radius, (int, np.integer)) or isinstance(radius, bool) or radius not in (1, 2):
+        raise ValueError(f"{who}: the clip radius must be 1 or 2, got {radius!r}")
+    if gamma is None or isinstance(gamma, bool):
+        raise ValueError(f"{who}: the clip gamma must be a number, finite and >= 0, got {gamma!r}")
+    gamma = float(gamma)
+    if not 0 <= gamma <= float(np.finfo(np.float32).max):      # (the C side reads floats: a double beyond them would arrive as Inf)
+        raise ValueError(f"{who}: the clip gamma must be finite and >= 0, got {gamma}")
+    return int(radius), gamma
 
 
 def _layer_sigmas(sigmas, n_layers, who, noun="sigmas"):

@@ -67,6 +67,9 @@ struct Options {
     int firefly_rank = 0, firefly_radius = 1;       // atrous-recursive: --firefly-rank 1..4 switches the clamp on (mid_firefly_params); 0: off
     float firefly_gain = 1.f, firefly_floor = 0.f;
     const char *firefly_other = nullptr;            // the first of --firefly-radius / --firefly-gain / --firefly-floor given
+    bool history_clip = false, history_clip_radius_given = false;   // atrous-recursive: --history-clip GAMMA switches the clip on (mid_color_bounds_params)
+    float history_clip_gamma = 1.f;
+    int history_clip_radius = 1;
     int search_lo = -7, search_hi = 7, patch_lo = -3, patch_hi = 3;   // shaders/nonlocal.comp:5-6, half-open
     int temporal_k = -1;            // <0: the reference's frame list; >=0: window t-k..t+k of the sorted sequence
     int cpu_radius = 10;            // windowSize, src/main.cpp:1819
@@ -723,6 +726,7 @@ public:
         if (!albedoNames.empty()) std::cout << "\talbedo " << albedoNames[0] << " floor " << opt.albedo_floor << "\n";
         if (opt.firefly_rank)
             std::cout << "\tfirefly radius " << opt.firefly_radius << " rank " << opt.firefly_rank << " gain " << opt.firefly_gain << " floor " << opt.firefly_floor << "\n";
+        if (opt.history_clip) std::cout << "\thistory-clip radius " << opt.history_clip_radius << " gamma " << opt.history_clip_gamma << "\n";
         std::vector<const void *> motion_ptrs(motionPlanes.size());
         for (size_t i = 0; i < motionPlanes.size(); ++i) motion_ptrs[i] = motionPlanes[i].data();
         if (!motionNames.empty()) std::cout << "\tmotion " << motionNames[0] << " scale " << opt.motion_sx << " " << opt.motion_sy << "\n";
@@ -794,10 +798,13 @@ public:
                 const mid_temporal_accum_params ap{bpp.width, bpp.height, opt.alpha, opt.alpha_moments, opt.history_max, 4.f, bpp.format};
                 const mid_atrous_variance_params vp{bpp.width, bpp.height, 0, opt.passes, opt.atrous_sigma_lum, opt.atrous_epsilon, bpp.format};
                 // (albedo: the chain runs on illumination -- demodulated first, modulated into the output; NULL is the plain call.
-                // firefly: the clamp in front of the chain, after the demodulation; NULL is the call without it)
+                // firefly: the clamp in front of the chain, after the demodulation; NULL is the call without it.
+                // history clip: the reprojected history clipped to the colour box of the plane the accumulation reads; NULL likewise)
                 const mid_firefly_params fp{bpp.width, bpp.height, opt.firefly_radius, opt.firefly_rank, opt.firefly_gain, opt.firefly_floor, bpp.format & 0xff};
-                MID_CHECK(mid_sequence_atrous_recursive_firefly(c, &ap, &vp, jointSigma.data(), frames, nf, lp, L, motion, albedo, opt.albedo_floor,
-                                                                opt.firefly_rank ? &fp : nullptr, opt.feedback, opt.warmup, start, count, outs, out_fmt, 1, t)); break;
+                const mid_color_bounds_params cp{bpp.width, bpp.height, opt.history_clip_radius, opt.history_clip_gamma, bpp.format & 0xff};
+                MID_CHECK(mid_sequence_atrous_recursive_clip(c, &ap, &vp, jointSigma.data(), frames, nf, lp, L, motion, albedo, opt.albedo_floor,
+                                                             opt.firefly_rank ? &fp : nullptr, opt.history_clip ? &cp : nullptr, opt.feedback, opt.warmup,
+                                                             start, count, outs, out_fmt, 1, t)); break;
             }
             case SEQ_NLM_JOINT:            // one patch weight from all layers (jointSigma: the h of each layer)
                 MID_CHECK(mid_sequence_nlm_joint(c, &np, jointSigma.data(), frames, nf, lp, L, kk, start, count, outs, out_fmt, 1, t)); break;
@@ -1069,6 +1076,11 @@ static void usage()
         "  --firefly-gain G          with --firefly-rank: factor on the limit, finite and > 0 (default 1)\n"
         "  --firefly-floor X         with --firefly-rank: a luminance that is always let through, finite and >= 0, in illumination\n"
         "                            units with --albedo-layer (default 0)\n"
+        "  --history-clip GAMMA      atrous-recursive: clip the reprojected history of every pixel, per colour channel, to the box\n"
+        "                            mean -+ GAMMA standard deviations of the current frame's neighbourhood (after the demodulation\n"
+        "                            and the firefly clamp) before it is blended: when the lighting changes and the geometry does\n"
+        "                            not, no ghost of the old lighting stays in the output.  GAMMA finite and >= 0; 1 is the usual value\n"
+        "  --history-clip-radius R   with --history-clip: 1 | 2, a 3x3 or 5x5 neighbourhood, centre included (default 1)\n"
         "  --temporal-k K            multiframe: frames t-K..t+K of the sorted sequence instead of the reference's list\n"
         "  --animation               denoise EVERY sibling frame with temporal NLM (window +-K, default 2) instead of the mode list\n"
         "  --animation-filter F      animation mode: nlm (default: temporal NLM), or the bilateral of every frame -- bilateral\n"
@@ -1111,7 +1123,8 @@ static void usage()
         "                            or atrous-recursive: recursive temporal accumulation (a history of colour and luminance moments,\n"
         "                            blended as lerp(history, frame, max(1/N, alpha))), then the variance-guided passes, frame after\n"
         "                            frame (--alpha, --alpha-moments, --history-max, --feedback, --warmup, --motion-layer,\n"
-        "                            --motion-scale, --albedo-layer, --albedo-floor, --firefly-rank, --firefly-radius, --firefly-gain, --firefly-floor;\n"
+        "                            --motion-scale, --albedo-layer, --albedo-floor, --firefly-rank, --firefly-radius, --firefly-gain, --firefly-floor,\n"
+        "                            --history-clip, --history-clip-radius;\n"
         "                            --passes, --sigma-layers, --atrous-sigma-lum,\n"
         "                            --atrous-epsilon as atrous-variance;\n"
         "                            it ignores --temporal-k; not with --halo rccl), outputs output-animation-nonlinear-atrous-recursive-*.\n"
@@ -1197,6 +1210,16 @@ int main(int argc, char **argv)
             opt.firefly_rank = atoi(next());
             if (opt.firefly_rank < 1 || opt.firefly_rank > 4) { std::cerr << "--firefly-rank " << opt.firefly_rank << " is outside 1..4\n"; return EXIT_FAILURE; }
         }
+        else if (a == "--history-clip") {
+            opt.history_clip_gamma = (float)atof(next());
+            opt.history_clip = true;
+            if (!(std::isfinite(opt.history_clip_gamma) && opt.history_clip_gamma >= 0.f)) { std::cerr << "--history-clip " << opt.history_clip_gamma << " must be finite and >= 0\n"; return EXIT_FAILURE; }
+        }
+        else if (a == "--history-clip-radius") {
+            opt.history_clip_radius = atoi(next());
+            opt.history_clip_radius_given = true;
+            if (opt.history_clip_radius != 1 && opt.history_clip_radius != 2) { std::cerr << "--history-clip-radius " << opt.history_clip_radius << " is neither 1 nor 2\n"; return EXIT_FAILURE; }
+        }
         else if (a == "--firefly-radius") {
             opt.firefly_radius = atoi(next());
             if (!opt.firefly_other) opt.firefly_other = "--firefly-radius";
@@ -1258,6 +1281,11 @@ int main(int argc, char **argv)
         return EXIT_FAILURE;
     }
     if (opt.firefly_other && !opt.firefly_rank) { std::cerr << opt.firefly_other << " needs --firefly-rank\n"; return EXIT_FAILURE; }
+    if ((opt.history_clip || opt.history_clip_radius_given) && !(opt.animation && opt.animation_filter == "atrous-recursive")) {
+        std::cerr << (opt.history_clip ? "--history-clip" : "--history-clip-radius") << " applies to --animation --animation-filter atrous-recursive only\n";
+        return EXIT_FAILURE;
+    }
+    if (opt.history_clip_radius_given && !opt.history_clip) { std::cerr << "--history-clip-radius needs --history-clip\n"; return EXIT_FAILURE; }
     if (listed("atrous-recursive")) {
         std::cerr << "--modes atrous-recursive: the recursion needs a sequence; it is an animation filter (--animation --animation-filter atrous-recursive)\n";
         return EXIT_FAILURE;

@@ -269,13 +269,15 @@ int atrous_moments_check(const mid_atrous_moments_params *p, const char *who, co
                          int n_frames, int k);
 int atrous_variance_check(const mid_atrous_variance_params *p, const char *who, const float *layer_sigma, bool have_layers, int n_layers);
 
-// mid_temporal_accumulate without its checks (the caller has made them), one launch on `s`: temporal_accumulate.hip.
+// mid_temporal_accumulate_clip without its checks (the caller has made them), one launch on `s`: temporal_accumulate.hip.
+// clip_lo == clip_hi == nullptr: the unclipped kernel.
 // temporal_accumulate_check: what the entry point checks before its tables -- the parameters, the format word, n_layers in
 // 0..16 and, with layers, both tables and every sigma finite and > 0.
 int temporal_accumulate_out(mid_ctx *ctx, const mid_temporal_accum_params *p, const float *layer_sigma, const void *cur,
                             const uint32_t *const *cur_layers, const uint32_t *const *prev_layers, int n_layers, const float *motion,
-                            const mid_pixel *hist_color_in, const mid_pixel *hist_state_in, const float *var_spatial, mid_pixel *color_out,
-                            mid_pixel *state_out, float *var_out, hipStream_t s);
+                            const mid_pixel *hist_color_in, const mid_pixel *hist_state_in, const float *var_spatial,
+                            const mid_pixel *clip_lo, const mid_pixel *clip_hi, mid_pixel *color_out, mid_pixel *state_out, float *var_out,
+                            hipStream_t s);
 int temporal_accumulate_check(const mid_temporal_accum_params *p, const char *who, const float *layer_sigma, bool have_layers, int n_layers);
 
 // mid_demodulate / mid_modulate without their checks (the caller has made them), one launch on `s`: albedo.hip; used by the frame
@@ -288,6 +290,11 @@ int albedo_check(const mid_albedo_params *p, const char *who);
 // (mid_sequence_atrous_recursive_firefly), not exported.  firefly_check: the size, radius, rank, gain, floor and the format word.
 int firefly_clamp_out(mid_ctx *ctx, const mid_firefly_params *p, const void *in, mid_pixel *out, hipStream_t s);
 int firefly_check(const mid_firefly_params *p, const char *who);
+
+// mid_color_bounds without its checks (the caller has made them), one launch on `s`: color_bounds.hip; used by the frame pipeline
+// (mid_sequence_atrous_recursive_clip), not exported.  color_bounds_check: the size, radius, gamma and the format word.
+int color_bounds_out(mid_ctx *ctx, const mid_color_bounds_params *p, const void *in, mid_pixel *lo, mid_pixel *hi, hipStream_t s);
+int color_bounds_check(const mid_color_bounds_params *p, const char *who);
 
 // ROCTx ranges (csrc/markers.cpp): no-ops unless the process already holds a ROCTx (rocprofv3 --marker-trace preloads one).
 bool markers_active();

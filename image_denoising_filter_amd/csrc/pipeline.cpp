@@ -694,17 +694,22 @@ extern "C" int mid_sequence_atrous_variance(mid_ctx *ctx, const mid_atrous_varia
 // With firefly parameters (section a4l) mid_firefly_clamp runs in front of the three steps, after the demodulation: it reads the
 // illumination plane, or the frame itself, into one more RGBA32F plane of the block (16 B per pixel more), which the three steps
 // read as an RGBA32F frame.
-extern "C" int mid_sequence_atrous_recursive_firefly(mid_ctx *ctx, const mid_temporal_accum_params *ap, const mid_atrous_variance_params *vp,
-                                                     const float *layer_sigma, const void *const *host_frames, int n_frames,
-                                                     const void *const *host_layers, int n_layers, const void *const *host_motion,
-                                                     const void *const *host_albedo, float albedo_floor, const mid_firefly_params *ff, int feedback,
-                                                     int warmup, int first, int count, void *const *host_out, int out_format, int overlap,
-                                                     float *timings_ms)
+// With colour-bounds parameters (section a4m) mid_color_bounds runs on the plane the accumulation reads -- the frame itself, or the
+// illumination / clamped plane -- into two more RGBA32F planes at the block's end (32 B per pixel more), and the accumulation is
+// mid_temporal_accumulate_clip with them.  The box of frame s is computed too (its accumulation has no history and clips nothing).
+// The block: 132 B per pixel, + 32 with albedo, + 16 with firefly parameters, + 32 with the clip: at most 212.
+extern "C" int mid_sequence_atrous_recursive_clip(mid_ctx *ctx, const mid_temporal_accum_params *ap, const mid_atrous_variance_params *vp,
+                                                  const float *layer_sigma, const void *const *host_frames, int n_frames,
+                                                  const void *const *host_layers, int n_layers, const void *const *host_motion,
+                                                  const void *const *host_albedo, float albedo_floor, const mid_firefly_params *ff,
+                                                  const mid_color_bounds_params *cb, int feedback, int warmup, int first, int count,
+                                                  void *const *host_out, int out_format, int overlap, float *timings_ms)
 {
     Bind b(ctx, nullptr);
     if (b.rc) return b.rc;
-    const char *who = ff ? "sequence_atrous_recursive_firefly" : host_albedo ? "sequence_atrous_recursive_albedo" : "sequence_atrous_recursive";
-    if (int rc = refuse_if_recording(ctx->compute, ff ? "mid_sequence_atrous_recursive_firefly (four streams, host-side waits)"
+    const char *who = cb ? "sequence_atrous_recursive_clip" : ff ? "sequence_atrous_recursive_firefly" : host_albedo ? "sequence_atrous_recursive_albedo" : "sequence_atrous_recursive";
+    if (int rc = refuse_if_recording(ctx->compute, cb ? "mid_sequence_atrous_recursive_clip (four streams, host-side waits)"
+                                                   : ff ? "mid_sequence_atrous_recursive_firefly (four streams, host-side waits)"
                                                    : host_albedo ? "mid_sequence_atrous_recursive_albedo (four streams, host-side waits)"
                                                                  : "mid_sequence_atrous_recursive (four streams, host-side waits)")) return rc;
     if (int rc = temporal_accumulate_check(ap, who, layer_sigma, host_layers != nullptr, n_layers)) return rc;
@@ -726,6 +731,16 @@ extern "C" int mid_sequence_atrous_recursive_firefly(mid_ctx *ctx, const mid_tem
                     fmt_frames(ap->format));
         fq = *ff;
         if (host_albedo) fq.format = MID_FMT_RGBA32F;
+    }
+    mid_color_bounds_params cq{};                           // the box reads the plane the accumulation reads: RGBA32F with albedo or firefly
+    if (cb) {
+        if (int rc = color_bounds_check(cb, who)) return rc;
+        MID_REQUIRE(cb->width == ap->width && cb->height == ap->height, "%s: the colour-bounds parameters are for %dx%d, the frames are %dx%d", who,
+                    cb->width, cb->height, ap->width, ap->height);
+        MID_REQUIRE(cb->format == fmt_frames(ap->format), "%s: the colour-bounds format 0x%x is not the frames' format %d without guide bits", who,
+                    cb->format, fmt_frames(ap->format));
+        cq = *cb;
+        if (host_albedo || ff) cq.format = MID_FMT_RGBA32F;
     }
     const mid_atrous_moments_params mp{ap->width, ap->height, ap->format};
     if (int rc = atrous_moments_check(&mp, who, layer_sigma, host_layers != nullptr, n_layers, 1, 0)) return rc;
@@ -764,7 +779,7 @@ extern "C" int mid_sequence_atrous_recursive_firefly(mid_ctx *ctx, const mid_tem
     const mid_albedo_params mo{ap->width, ap->height, albedo_floor, fp.format};       // modulate: RGBA32F in
     if (host_albedo || ff) aq.format = mq.format = fp.format;
     Stage st{who, ap->width, ap->height, fmt_frames(ap->format), npix * fmt_bytes(gfmt), host_layers, n_layers, true, "atrous recursive %d"};
-    st.level_bytes = npix * 16 * 7 + 5 * plane + (host_albedo ? npix * 32 : 0) + (ff ? npix * 16 : 0); st.n_levels = 1;
+    st.level_bytes = npix * 16 * 7 + 5 * plane + (host_albedo ? npix * 32 : 0) + (ff ? npix * 16 : 0) + (cb ? npix * 32 : 0); st.n_levels = 1;
     st.in_order = true; st.host_motion = host_motion; st.skip = skip; st.host_albedo = host_albedo;
     const int n_side = n_layers + (host_motion ? 1 : 0) + (host_albedo ? 1 : 0);
     int step = 0;                                           // frames accumulated so far: the launches come in output order
@@ -777,7 +792,8 @@ extern "C" int mid_sequence_atrous_recursive_firefly(mid_ctx *ctx, const mid_tem
         float *vs = (float *)fb, *vt = (float *)(fb + plane), *v1 = (float *)(fb + 2 * plane);
         float *vlevel[2] = {(float *)(fb + 3 * plane), (float *)(fb + 4 * plane)};
         mid_pixel *illum = (mid_pixel *)(fb + 5 * plane), *fin = illum + npix;        // (with albedo only: the block ends before them otherwise)
-        mid_pixel *clamped = host_albedo ? fin + npix : illum;                        // (with firefly parameters only: the block's last plane)
+        mid_pixel *clamped = host_albedo ? fin + npix : illum;                        // (with firefly parameters only: one plane after those)
+        mid_pixel *box_lo = ff ? clamped + npix : clamped, *box_hi = box_lo + npix;   // (with the clip only: the block's last two planes)
         for (int i = 0; i < bn; ++i, ++step) {
             const int t = t0 + i, cur = step & 1, prev = cur ^ 1;
             const uint32_t *const *ly = lt + (size_t)t * n_side;
@@ -798,8 +814,9 @@ extern "C" int mid_sequence_atrous_recursive_firefly(mid_ctx *ctx, const mid_tem
             const int last_fmt = alb ? (int)MID_FMT_RGBA32F : out_fmt;
             if (int rc = atrous_moments_out(ctx, &mq, layer_sigma, &frame, ly, n_layers, 1, 0, 0, vs, s)) return rc;
             mid_pixel *col = feedback ? acc : hc[cur];
+            if (cb) { if (int rc = color_bounds_out(ctx, &cq, frame, box_lo, box_hi, s)) return rc; }
             if (int rc = temporal_accumulate_out(ctx, &aq, layer_sigma, frame, ly, pl, n_layers, mv, step ? hc[prev] : nullptr, step ? hs[prev] : nullptr,
-                                                 vs, col, hs[cur], vt, s)) return rc;
+                                                 vs, cb ? box_lo : nullptr, cb ? box_hi : nullptr, col, hs[cur], vt, s)) return rc;
             if (!feedback) {
                 if (int rc = atrous_variance_out(ctx, &fp, layer_sigma, col, vt, ly, n_layers, last, last_fmt, nullptr, level, vlevel, s)) return rc;
             } else {
@@ -818,6 +835,17 @@ extern "C" int mid_sequence_atrous_recursive_firefly(mid_ctx *ctx, const mid_tem
     std::vector<void *> outs((size_t)skip + count, nullptr);
     for (int i = 0; i < count; ++i) outs[(size_t)skip + i] = host_out[i];
     return run_pipeline(ctx, st, launch, host_frames, n_frames, 1, s0, skip + count, outs.data(), out_format, overlap, timings_ms);
+}
+
+extern "C" int mid_sequence_atrous_recursive_firefly(mid_ctx *ctx, const mid_temporal_accum_params *ap, const mid_atrous_variance_params *vp,
+                                                     const float *layer_sigma, const void *const *host_frames, int n_frames,
+                                                     const void *const *host_layers, int n_layers, const void *const *host_motion,
+                                                     const void *const *host_albedo, float albedo_floor, const mid_firefly_params *ff, int feedback,
+                                                     int warmup, int first, int count, void *const *host_out, int out_format, int overlap,
+                                                     float *timings_ms)
+{
+    return mid_sequence_atrous_recursive_clip(ctx, ap, vp, layer_sigma, host_frames, n_frames, host_layers, n_layers, host_motion, host_albedo, albedo_floor,
+                                              ff, nullptr, feedback, warmup, first, count, host_out, out_format, overlap, timings_ms);
 }
 
 extern "C" int mid_sequence_atrous_recursive_albedo(mid_ctx *ctx, const mid_temporal_accum_params *ap, const mid_atrous_variance_params *vp,

@@ -12,6 +12,10 @@
 //   color_out = fmaf(a, C - hc, hc);  m1' = fmaf(am, l - h1, h1);  m2' = fmaf(am, l l - h2, h2);  state_out = (m1', m2', N', 0)
 //   v = fmaf(-m1', m1', m2');  Vt = v < 0 ? 0 : v;  var_out = Vs given ? fmaf(fminf(1, (N' - 1) / (historyFull - 1)), Vt - Vs, Vs) : Vt
 //
+// With a clip box (section a4m, mid_temporal_accumulate_clip), after the normalisation and where S > 0, per colour channel:
+//   hc' = hc < lo ? lo : (hc > hi ? hi : hc);  d = l(hc') - l(hc);  h1' = h1 + d;  h2' = fmaf(d, fmaf(2, h1, d), h2)
+// and everything below reads hc', h1', h2'.  A compile-time variant (accumulate_pixel<CLIP>): the unclipped kernel has no trace of it.
+//
 // One kernel: one pixel per lane, 64 x 4 pixels per workgroup, no LDS -- the tap addresses depend on the data.  Motion is locally
 // coherent, so the four taps of neighbouring lanes share cache lines.  The layer loop is wave-uniform and runs OUTSIDE the taps: per
 // layer the centre texel and the (up to) four previous texels are loaded and the four exponents advance together, so no centre
@@ -55,10 +59,13 @@ struct AccumArgs {
     const void *cur_layer[kMaxLayers];
     const void *prev_layer[kMaxLayers];
 };
-static_assert(2 * kMaxLayers + 8 <= MID_NLM_LAYERS_TEMPORAL_MAX_POINTERS, "the pointer table of one launch");
+static_assert(2 * kMaxLayers + 10 <= MID_NLM_LAYERS_TEMPORAL_MAX_POINTERS, "the pointer table of one launch");
 static_assert(sizeof(AccumArgs) <= 4096, "one kernel argument block");
 
-__global__ __launch_bounds__(256) void temporal_accumulate_kernel(const AccumArgs a)
+// The whole pixel; CLIP: the normalised history is clipped to [clip_lo(p), clip_hi(p)] per colour channel and the moments move with it
+// (section a4m).  Without it no instruction of the unclipped kernel changes.
+template <bool CLIP>
+__device__ __forceinline__ void accumulate_pixel(const AccumArgs &a, const float4 *clip_lo, const float4 *clip_hi)
 {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
     const int w = a.w, h = a.h, L = a.n_layers;
@@ -115,6 +122,17 @@ __global__ __launch_bounds__(256) void temporal_accumulate_kernel(const AccumArg
         hc = make_float4(0.f, 0.f, 0.f, 0.f);
         h1 = h2 = 0.f;
     }
+    if (CLIP && S > 0.f) {
+        const float4 lo = clip_lo[ci], hi = clip_hi[ci];
+        float4 hk = hc;                                    // (a NaN hc stays NaN; a NaN bound clips nothing)
+        hk.x = hc.x < lo.x ? lo.x : (hc.x > hi.x ? hi.x : hc.x);
+        hk.y = hc.y < lo.y ? lo.y : (hc.y > hi.y ? hi.y : hc.y);
+        hk.z = hc.z < lo.z ? lo.z : (hc.z > hi.z ? hi.z : hc.z);
+        const float d = lum(hk) - lum(hc);
+        h2 = fmaf(d, fmaf(2.0f, h1, d), h2);               // the mean moves by d, the variance h2 - h1^2 stays
+        h1 = h1 + d;
+        hc = hk;
+    }
     const float N = fminf(a.hist_max, hn + 1.0f);
     const float inv = 1.0f / N;
     const float al = fmaxf(inv, a.alpha), am = fmaxf(inv, a.alpha_m);
@@ -134,6 +152,16 @@ __global__ __launch_bounds__(256) void temporal_accumulate_kernel(const AccumArg
         a.var_out[ci] = vo;
     }
 }
+
+__global__ __launch_bounds__(256) void temporal_accumulate_kernel(const AccumArgs a) { accumulate_pixel<false>(a, nullptr, nullptr); }
+
+struct AccumClipArgs {
+    AccumArgs a;
+    const float4 *clip_lo, *clip_hi;
+};
+static_assert(sizeof(AccumClipArgs) <= 4096, "one kernel argument block");
+
+__global__ __launch_bounds__(256) void temporal_accumulate_clip_kernel(const AccumClipArgs c) { accumulate_pixel<true>(c.a, c.clip_lo, c.clip_hi); }
 
 bool ranges_overlap(const void *p, size_t np, const void *q, size_t nq)
 {
@@ -168,11 +196,12 @@ int temporal_accumulate_check(const mid_temporal_accum_params *p, const char *wh
     return MID_OK;
 }
 
-// mid_temporal_accumulate without its checks (the caller has made them), one launch on `s`.
+// mid_temporal_accumulate_clip without its checks (the caller has made them), one launch on `s`; without clip planes the unclipped kernel.
 int temporal_accumulate_out(mid_ctx *ctx, const mid_temporal_accum_params *p, const float *layer_sigma, const void *cur,
                             const uint32_t *const *cur_layers, const uint32_t *const *prev_layers, int n_layers, const float *motion,
-                            const mid_pixel *hist_color_in, const mid_pixel *hist_state_in, const float *var_spatial, mid_pixel *color_out,
-                            mid_pixel *state_out, float *var_out, hipStream_t s)
+                            const mid_pixel *hist_color_in, const mid_pixel *hist_state_in, const float *var_spatial,
+                            const mid_pixel *clip_lo, const mid_pixel *clip_hi, mid_pixel *color_out, mid_pixel *state_out, float *var_out,
+                            hipStream_t s)
 {
     (void)ctx;
     AccumArgs a{};
@@ -191,7 +220,11 @@ int temporal_accumulate_out(mid_ctx *ctx, const mid_temporal_accum_params *p, co
         a.cur_layer[l] = cur_layers[l];
         a.prev_layer[l] = prev_layers[l];
     }
-    hipLaunchKernelGGL(temporal_accumulate_kernel, dim3(cdiv(a.w, 64), cdiv(a.h, 4)), dim3(256), 0, s, a);
+    if (clip_lo) {
+        const AccumClipArgs c{a, (const float4 *)clip_lo, (const float4 *)clip_hi};
+        hipLaunchKernelGGL(temporal_accumulate_clip_kernel, dim3(cdiv(a.w, 64), cdiv(a.h, 4)), dim3(256), 0, s, c);
+    } else
+        hipLaunchKernelGGL(temporal_accumulate_kernel, dim3(cdiv(a.w, 64), cdiv(a.h, 4)), dim3(256), 0, s, a);
     MID_HIP(hipGetLastError());
     return MID_OK;
 }
@@ -200,14 +233,15 @@ int temporal_accumulate_out(mid_ctx *ctx, const mid_temporal_accum_params *p, co
 
 using namespace mid;
 
-extern "C" int mid_temporal_accumulate(mid_ctx *ctx, const mid_temporal_accum_params *p, const float *layer_sigma, const void *cur,
-                                       const uint32_t *const *cur_layers, const uint32_t *const *prev_layers, int n_layers,
-                                       const float *motion, const mid_pixel *hist_color_in, const mid_pixel *hist_state_in,
-                                       const float *var_spatial, mid_pixel *color_out, mid_pixel *state_out, float *var_out, void *stream)
+extern "C" int mid_temporal_accumulate_clip(mid_ctx *ctx, const mid_temporal_accum_params *p, const float *layer_sigma, const void *cur,
+                                            const uint32_t *const *cur_layers, const uint32_t *const *prev_layers, int n_layers,
+                                            const float *motion, const mid_pixel *hist_color_in, const mid_pixel *hist_state_in,
+                                            const float *var_spatial, const mid_pixel *clip_lo, const mid_pixel *clip_hi, mid_pixel *color_out,
+                                            mid_pixel *state_out, float *var_out, void *stream)
 {
     Bind b(ctx, stream);
     if (b.rc) return b.rc;
-    const char *who = "temporal_accumulate";
+    const char *who = clip_lo || clip_hi ? "temporal_accumulate_clip" : "temporal_accumulate";
     if (int rc = temporal_accumulate_check(p, who, layer_sigma, cur_layers != nullptr && prev_layers != nullptr, n_layers)) return rc;
     MID_REQUIRE(cur && color_out && state_out, "%s: NULL frame or output", who);
     MID_REQUIRE((hist_color_in == nullptr) == (hist_state_in == nullptr), "%s: the history is its colour AND its state: both or neither", who);
@@ -220,11 +254,14 @@ extern "C" int mid_temporal_accumulate(mid_ctx *ctx, const mid_temporal_accum_pa
     MID_REQUIRE(((uintptr_t)hist_color_in & 15u) == 0 && ((uintptr_t)hist_state_in & 15u) == 0, "%s: a history plane is not 16-byte aligned", who);
     MID_REQUIRE(((uintptr_t)color_out & 15u) == 0 && ((uintptr_t)state_out & 15u) == 0, "%s: color_out or state_out is not 16-byte aligned", who);
     MID_REQUIRE(((uintptr_t)var_spatial & 15u) == 0 && ((uintptr_t)var_out & 15u) == 0, "%s: a variance plane is not 16-byte aligned", who);
+    MID_REQUIRE((clip_lo == nullptr) == (clip_hi == nullptr), "%s: the clip box is its lower AND its upper plane: both or neither", who);
+    MID_REQUIRE(((uintptr_t)clip_lo & 15u) == 0 && ((uintptr_t)clip_hi & 15u) == 0, "%s: a clip plane is not 16-byte aligned", who);
     // every output against every input and against the other outputs: the gather reads neighbours, so nothing works in place
     struct Plane { const void *p; size_t n; const char *name; };
     const Plane outs[3] = {{color_out, px_bytes, "color_out"}, {state_out, px_bytes, "state_out"}, {var_out, var_bytes, "var_out"}};
-    const Plane ins[5] = {{cur, in_bytes, "the frame"}, {motion, mv_bytes, "motion"}, {hist_color_in, px_bytes, "hist_color_in"},
-                          {hist_state_in, px_bytes, "hist_state_in"}, {var_spatial, var_bytes, "var_spatial"}};
+    const Plane ins[7] = {{cur, in_bytes, "the frame"}, {motion, mv_bytes, "motion"}, {hist_color_in, px_bytes, "hist_color_in"},
+                          {hist_state_in, px_bytes, "hist_state_in"}, {var_spatial, var_bytes, "var_spatial"},
+                          {clip_lo, px_bytes, "clip_lo"}, {clip_hi, px_bytes, "clip_hi"}};
     for (int l = 0; l < n_layers; ++l) {
         MID_REQUIRE(cur_layers[l] != nullptr && prev_layers[l] != nullptr, "%s: layer %d is NULL", who, l);
         MID_REQUIRE(guide_aligned(gfmt, cur_layers[l]) && guide_aligned(gfmt, prev_layers[l]), "%s: layer %d is not %d-byte aligned (%s guide)", who, l,
@@ -241,5 +278,14 @@ extern "C" int mid_temporal_accumulate(mid_ctx *ctx, const mid_temporal_accum_pa
             MID_REQUIRE(!ranges_overlap(outs[i].p, outs[i].n, outs[j].p, outs[j].n), "%s: %s overlaps %s", who, outs[i].name, outs[j].name);
     }
     return temporal_accumulate_out(ctx, p, layer_sigma, cur, cur_layers, prev_layers, n_layers, motion, hist_color_in, hist_state_in,
-                                   var_spatial, color_out, state_out, var_out, b.s);
+                                   var_spatial, clip_lo, clip_hi, color_out, state_out, var_out, b.s);
+}
+
+extern "C" int mid_temporal_accumulate(mid_ctx *ctx, const mid_temporal_accum_params *p, const float *layer_sigma, const void *cur,
+                                       const uint32_t *const *cur_layers, const uint32_t *const *prev_layers, int n_layers,
+                                       const float *motion, const mid_pixel *hist_color_in, const mid_pixel *hist_state_in,
+                                       const float *var_spatial, mid_pixel *color_out, mid_pixel *state_out, float *var_out, void *stream)
+{
+    return mid_temporal_accumulate_clip(ctx, p, layer_sigma, cur, cur_layers, prev_layers, n_layers, motion, hist_color_in, hist_state_in, var_spatial,
+                                        nullptr, nullptr, color_out, state_out, var_out, stream);
 }

@@ -950,6 +950,82 @@ int mid_sequence_atrous_recursive_firefly(mid_ctx *ctx, const mid_temporal_accum
                                           int feedback /* 0 | 1 */, int warmup /* >= 0 */, int first, int count,
                                           void *const *host_out, int out_format, int overlap, float *timings_ms);
 
+/* ---- a4m: history clipping -------------------------------------------------------------------
+ * mid_temporal_accumulate rejects history only through the guide layers; there is deliberately no disocclusion threshold (a4j).
+ * When the lighting changes and the geometry does not -- a light switching, a moving shadow, a reflection, an emissive texture --
+ * every layer says "same surface", the history is fully believed and the output carries a ghost of the old lighting that decays
+ * as (1 - alpha)^j.  The firefly clamp (a4l) bounds the current frame by its neighbourhood; history clipping bounds the HISTORY by
+ * the current frame: neighbourhood variance clipping of the reprojected history (Salvi 2016), the "history clamping" or "anti-lag"
+ * of SVGF's production descendants.  Two pieces: mid_color_bounds computes a colour box per pixel from the current frame, and
+ * mid_temporal_accumulate_clip clips the normalised history to it before the blend.
+ *
+ * mid_color_bounds.  Per pixel p, with C the texel widened as a4i widens a frame:
+ *   window    q = p + (i, j), |i|, |j| <= radius, the centre INCLUDED, q inside the image.  q is VALID iff R, G and B of C(q) are all
+ *             finite (fabsf(c) < INFINITY); n is the number of valid q.
+ *   n == 0    lo.rgb = -INFINITY, hi.rgb = +INFINITY: nothing will be clipped.
+ *   else      per channel c over the valid q:  mu = (sum v) / n, rounded to fp32;  var = (sum (v - mu)^2) / n -- the TWO-PASS form:
+ *             the one-pass E[v^2] - mu^2 loses everything on flat HDR regions;  sigma = sqrtf(var);
+ *             lo_c = fmaf(-gamma, sigma, mu);  hi_c = fmaf(gamma, sigma, mu).
+ *   alpha     lo.w = hi.w = (float)n.  Alpha is never clipped.
+ * The order of the sums inside the window is the kernel's own: the sum of the mean is taken in binary64 and the quotient rounded
+ * once to fp32, so a window of one repeated value v has mu == v, var == 0 and lo == hi == v bit for bit, whatever v is; the
+ * deviations, their squares (one fma each) and their sum are fp32.  Scaling the frame by a power of two scales lo and hi by it,
+ * bit for bit, while nothing leaves the normal range.  A window whose deviations overflow when squared (|v - mu| >= 2^64) has
+ * sigma = +Inf: the box is everything, or NaN -- which clips nothing either -- for gamma == 0.
+ * Precision: lo and hi within 1e-5 * max(1, |mu| + gamma sigma) of the formula in float64 with mu rounded to fp32; .w exact.
+ * Class: tiled (csrc/color_bounds.hip): the firefly clamp's geometry (csrc/firefly_tile.hpp), a workgroup of four
+ * waves covers 64 x 16 pixels from an LDS tile of (64 + 2 radius) x (16 + 2 radius) x 3 floats; index arithmetic in size_t.
+ * MID_ERR_INVALID before anything is queued, `lo` and `hi` untouched: a NULL pointer; radius outside {1, 2}; gamma not finite or
+ * < 0; an unknown frame format, or guide bits set in format; `in` not aligned to its texel size, `lo` or `hi` not to 16 bytes;
+ * width or height < 1, or 2^30 pixels and more; `lo` or `hi` overlapping `in`, or each other. */
+typedef struct mid_color_bounds_params {
+    int32_t width, height;
+    int32_t radius;   /* 1 | 2: 3x3 or 5x5 window, centre INCLUDED */
+    float   gamma;    /* finite, >= 0: half-width of the box in standard deviations; default 1 */
+    int32_t format;   /* MID_FMT_* of `in`; guide bits must be 0 */
+} mid_color_bounds_params;
+int mid_color_bounds(mid_ctx *ctx, const mid_color_bounds_params *p, const void *in, mid_pixel *lo /* RGBA32F */,
+                     mid_pixel *hi /* RGBA32F */, void *stream);
+/* mid_temporal_accumulate with a clip box.  clip_lo == clip_hi == NULL: it IS mid_temporal_accumulate, and that entry point is this
+ * one with NULL.  Otherwise both are width * height RGBA32F planes (mid_color_bounds of `cur`, usually) and, after step 4 of a4j
+ * where S > 0 (with S == 0 nothing changes), per channel c in {R, G, B}, literally:
+ *   hc'_c = hc_c < lo_c ? lo_c : (hc_c > hi_c ? hi_c : hc_c)      -- a NaN hc stays NaN; a NaN bound clips nothing
+ *   d   = l(hc') - l(hc)                                           -- a4i's luminance on (x, y, z), both fma chains
+ *   h1' = h1 + d
+ *   h2' = fmaf(d, fmaf(2.0f, h1, d), h2)                           -- the mean moves by d, the variance h2 - h1^2 stays
+ * hc.w and hn (and so N') are unchanged; steps 5 - 8 read hc', h1' and h2'.  Where nothing is clipped d is exactly 0 and the bits
+ * are those of the unclipped call.  lo > hi is not refused: the formula is taken literally (hc < lo gives lo).  The `.w` of the
+ * planes is not read.  Precision and class as a4j: a compile-time variant of the same kernel, two more 16-byte loads per pixel.
+ * MID_ERR_INVALID, the outputs untouched: the refusals of mid_temporal_accumulate; exactly one of the two planes NULL; a plane
+ * not 16-byte aligned; any output overlapping a clip plane. */
+int mid_temporal_accumulate_clip(mid_ctx *ctx, const mid_temporal_accum_params *p, const float *layer_sigma /* n_layers host floats */,
+                                 const void *cur, const uint32_t *const *cur_layers, const uint32_t *const *prev_layers,
+                                 int n_layers /* 0..16 */, const float *motion /* width*height float2, or NULL = zero motion */,
+                                 const mid_pixel *hist_color_in, const mid_pixel *hist_state_in /* both NULL: no history */,
+                                 const float *var_spatial /* float plane or NULL */,
+                                 const mid_pixel *clip_lo, const mid_pixel *clip_hi /* both NULL: no clip */,
+                                 mid_pixel *color_out, mid_pixel *state_out, float *var_out /* or NULL */, void *stream);
+/* mid_sequence_atrous_recursive_firefly with the history clipped.  cp == NULL: it IS that call, and that entry point is this one
+ * with NULL.  Otherwise, per frame t: after (0) the demodulation and (0') the firefly clamp, mid_color_bounds (cp's radius and
+ * gamma) runs on THE PLANE THE ACCUMULATION READS -- the frame itself in the frames' format, or the illumination / clamped plane as
+ * RGBA32F -- into two more RGBA32F planes of the cache block (32 B per pixel more), and step (2) is mid_temporal_accumulate_clip
+ * with them.  The box is computed for frame s too, whose accumulation has no history and clips nothing: the schedule is the same
+ * for every frame.  Output t has, bit for bit, the result of that chain of public calls.  No new host plane, side slot or upload;
+ * everything runs on the one in-order kernel stream.  A frame block of a sharded run needs nothing new: the box comes from the
+ * frame itself.
+ * MID_ERR_INVALID before anything is queued, host_out and timings_ms untouched: the refusals of
+ * mid_sequence_atrous_recursive_firefly; those of mid_color_bounds's parameters; cp->width / cp->height other than ap's; cp->format
+ * other than the frames' format with no guide bits (both values are named). */
+int mid_sequence_atrous_recursive_clip(mid_ctx *ctx, const mid_temporal_accum_params *ap, const mid_atrous_variance_params *vp,
+                                       const float *layer_sigma, const void *const *host_frames, int n_frames,
+                                       const void *const *host_layers, int n_layers /* 1..16 */,
+                                       const void *const *host_motion /* n_frames float2 planes, or NULL */,
+                                       const void *const *host_albedo /* n_frames planes in the guide format, or NULL */,
+                                       float albedo_floor, const mid_firefly_params *fp /* NULL: no clamp */,
+                                       const mid_color_bounds_params *cp /* NULL: no history clip */,
+                                       int feedback /* 0 | 1 */, int warmup /* >= 0 */, int first, int count,
+                                       void *const *host_out, int out_format, int overlap, float *timings_ms);
+
 /* ---- a5: normalize ----------------------------------------------------------------------
  * One dispatch of shaders/normalize.comp (RecordCommandsOfExecuteAndTransfer(normKernel=true)):
  * out = weightColor / normWeight, or (1,0,1,1) where normWeight == 0; bindings {0: out; 1: W}. */

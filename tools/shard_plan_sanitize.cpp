@@ -34,13 +34,15 @@ int mid::atrous_moments_out(mid_ctx *, const mid_atrous_moments_params *, const 
 int mid::atrous_variance_out(mid_ctx *, const mid_atrous_variance_params *, const float *, const void *, const float *, const uint32_t *const *, int, void *, int, float *, void *const *, float *const *, hipStream_t) { return MID_ERR_UNSUPPORTED; }   // (atrous_variance.hip)
 int mid::atrous_moments_check(const mid_atrous_moments_params *, const char *, const float *, bool, int, int, int) { return MID_ERR_UNSUPPORTED; }   // (atrous_variance.hip)
 int mid::atrous_variance_check(const mid_atrous_variance_params *, const char *, const float *, bool, int) { return MID_ERR_UNSUPPORTED; }   // (atrous_variance.hip)
-int mid::temporal_accumulate_out(mid_ctx *, const mid_temporal_accum_params *, const float *, const void *, const uint32_t *const *, const uint32_t *const *, int, const float *, const mid_pixel *, const mid_pixel *, const float *, mid_pixel *, mid_pixel *, float *, hipStream_t) { return MID_ERR_UNSUPPORTED; }   // (temporal_accumulate.hip)
+int mid::temporal_accumulate_out(mid_ctx *, const mid_temporal_accum_params *, const float *, const void *, const uint32_t *const *, const uint32_t *const *, int, const float *, const mid_pixel *, const mid_pixel *, const float *, const mid_pixel *, const mid_pixel *, mid_pixel *, mid_pixel *, float *, hipStream_t) { return MID_ERR_UNSUPPORTED; }   // (temporal_accumulate.hip)
 int mid::temporal_accumulate_check(const mid_temporal_accum_params *, const char *, const float *, bool, int) { return MID_ERR_UNSUPPORTED; }   // (temporal_accumulate.hip)
 int mid::demodulate_out(mid_ctx *, const mid_albedo_params *, const void *, const void *, mid_pixel *, hipStream_t) { return MID_ERR_UNSUPPORTED; }   // (albedo.hip)
 int mid::modulate_out(mid_ctx *, const mid_albedo_params *, const mid_pixel *, const void *, void *, int, hipStream_t) { return MID_ERR_UNSUPPORTED; }   // (albedo.hip)
 int mid::albedo_check(const mid_albedo_params *, const char *) { return MID_ERR_UNSUPPORTED; }   // (albedo.hip)
 int mid::firefly_clamp_out(mid_ctx *, const mid_firefly_params *, const void *, mid_pixel *, hipStream_t) { return MID_ERR_UNSUPPORTED; }   // (firefly.hip)
 int mid::firefly_check(const mid_firefly_params *, const char *) { return MID_ERR_UNSUPPORTED; }   // (firefly.hip)
+int mid::color_bounds_out(mid_ctx *, const mid_color_bounds_params *, const void *, mid_pixel *, mid_pixel *, hipStream_t) { return MID_ERR_UNSUPPORTED; }   // (color_bounds.hip)
+int mid::color_bounds_check(const mid_color_bounds_params *, const char *) { return MID_ERR_UNSUPPORTED; }   // (color_bounds.hip)
 int mid::nlm_check_params(const mid_nlm_params *) { return MID_ERR_UNSUPPORTED; }   // (nlm.hip)
 int mid::bilateral_check_params(const mid_bilateral_params *, const char *, bool) { return MID_ERR_UNSUPPORTED; }   // (bilateral.hip)
 
