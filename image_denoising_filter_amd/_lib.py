@@ -86,6 +86,21 @@ class ColorBoundsParams(ctypes.Structure):
                 ("format", ctypes.c_int32)]
 
 
+class ImageMetricsParams(ctypes.Structure):
+    """mid_image_metrics_params (section a4n)."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("format_a", ctypes.c_int32), ("format_b", ctypes.c_int32),
+                ("peak", ctypes.c_float), ("eps", ctypes.c_float), ("ssim", ctypes.c_int32)]
+
+
+class ImageMetricsResult(ctypes.Structure):
+    """mid_image_metrics_result (section a4n)."""
+    _fields_ = [(name, ctypes.c_double) for name in ("n_valid", "n_invalid", "mse", "mse_r", "mse_g", "mse_b", "mae", "max_abs", "psnr",
+                                                      "relmse", "ssim")]
+
+
+METRICS_N = 16      # MID_METRICS_N
+
+
 class NormalizeParams(ctypes.Structure):
     _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32)]
 
@@ -182,6 +197,10 @@ _SIGNATURES = {
                                                           c_void_pp, ctypes.c_float, ctypes.POINTER(FireflyParams), ctypes.POINTER(ColorBoundsParams),
                                                           ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_pp, ctypes.c_int, ctypes.c_int,
                                                           ctypes.POINTER(ctypes.c_float)]),
+    "mid_image_metrics_workspace": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    "mid_image_metrics": (ctypes.c_int, [_P, ctypes.POINTER(ImageMetricsParams), _P, _P, _P, _P, _P]),
+    "mid_image_metrics_derive": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ImageMetricsParams),
+                                                ctypes.POINTER(ImageMetricsResult)]),
     "mid_normalize": (ctypes.c_int, [_P, ctypes.POINTER(NormalizeParams), _P, _P, _P]),
     "mid_unpack_u8": (ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_int, _P, _P]),
     "mid_pack_u8": (ctypes.c_int, [_P, _P, ctypes.c_size_t, _P, _P]),

@@ -15,7 +15,7 @@ import weakref
 
 import numpy as np
 
-from ._lib import AlbedoParams, AtrousMomentsParams, AtrousParams, AtrousVarianceParams, BilateralParams, ColorBoundsParams, FireflyParams, Image, NlmParams, NormalizeParams, TemporalAccumParams, c_void_pp, lib
+from ._lib import AlbedoParams, AtrousMomentsParams, AtrousParams, AtrousVarianceParams, BilateralParams, ColorBoundsParams, FireflyParams, Image, ImageMetricsParams, ImageMetricsResult, METRICS_N, NlmParams, NormalizeParams, TemporalAccumParams, c_void_pp, lib
 
 FMT_RGBA32F, FMT_RGBA8, FMT_RGBA16F = 0, 1, 2
 
@@ -653,6 +653,35 @@ class Context:
         _check(lib.mid_color_bounds(self.handle, ctypes.byref(p), d_in.ptr, d_lo.ptr, d_hi.ptr, None), "mid_color_bounds")
         return self.download(d_lo, (h, w, 4), np.float32), self.download(d_hi, (h, w, 4), np.float32)
 
+    def image_metrics(self, a, b, peak=1.0, eps=1e-2, ssim=True, want_map=False):
+        """Full-reference quality metrics of a test image `a` against a reference `b` (mid_image_metrics, section a4n), over the
+        pixels whose R, G and B are finite in both; alpha is ignored.  a, b: (h, w, 4) uint8, float16 or float32 of one shape, each
+        with its own dtype.  peak: the data range (1 for unit-range frames); eps: relMSE's regulariser.  Returns a dict: n_valid,
+        n_invalid, mse, mse_r, mse_g, mse_b, mae, max_abs, psnr, relmse, ssim (mid_image_metrics_derive's values; ssim is NaN with
+        ssim=False), `sums` (the 16 raw float64 sums) and, with want_map, `map`: float32 (h, w), ssim per pixel, NaN where the pixel
+        is not valid."""
+        who = "image_metrics"
+        a, b = _img(a), _img(b)
+        for name, x in (("a", a), ("b", b)):
+            if x.dtype not in [np.dtype(d) for d in _GUIDE_DTYPES]:
+                raise ValueError(f"{who}: {name} must be uint8 / float16 / float32, got {x.dtype}")
+        if a.shape != b.shape:
+            raise ValueError(f"{who}: a is {a.shape} but b is {b.shape}: the two images must have one size")
+        peak, eps, ssim, want_map = _metrics_args(peak, eps, ssim, want_map, who)
+        h, w = a.shape[:2]
+        p = ImageMetricsParams(w, h, _fmt_of(a), _fmt_of(b), peak, eps, int(ssim))
+        d_a, d_b = self.upload(a), self.upload(b)
+        d_work = self.alloc(lib.mid_image_metrics_workspace(w, h))
+        d_map = self.alloc(w * h * 4) if want_map else None
+        _check(lib.mid_image_metrics(self.handle, ctypes.byref(p), d_a.ptr, d_b.ptr, d_work.ptr, d_map.ptr if want_map else None, None),
+               "mid_image_metrics")
+        sums = self.download(d_work, (METRICS_N,), np.float64)
+        out = metrics_derive(sums, peak, ssim)
+        out["sums"] = sums
+        if want_map:
+            out["map"] = self.download(d_map, (h, w), np.float32)
+        return out
+
     def normalize(self, W):
         """normalize.comp."""
         W = np.ascontiguousarray(W, dtype=np.float32)
@@ -1123,6 +1152,34 @@ def _clip_args(gamma, radius, who, off_allowed=True):
     if not 0 <= gamma <= float(np.finfo(np.float32).max):      # (the C side reads floats: a double beyond them would arrive as Inf)
         raise ValueError(f"{who}: the clip gamma must be finite and >= 0, got {gamma}")
     return int(radius), gamma
+
+
+def _metrics_args(peak, eps, ssim, want_map, who):
+    """The keywords of image_metrics, checked before any GPU work: (peak, eps, ssim, want_map) in the ranges of
+    mid_image_metrics_params."""
+    f32_max = float(np.finfo(np.float32).max)          # (the C side reads floats: a double beyond them would arrive as Inf)
+    for name, v in (("peak", peak), ("eps", eps)):
+        if v is None or isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError(f"{who}: {name} must be a number, finite and > 0, got {v!r}")
+        if not (0 < float(v) <= f32_max and float(np.float32(v)) > 0):
+            raise ValueError(f"{who}: {name} must be finite and > 0, got {float(v)}")
+    if not isinstance(ssim, (bool, np.bool_)) or not isinstance(want_map, (bool, np.bool_)):
+        raise ValueError(f"{who}: ssim and want_map must be True or False, got {ssim!r} and {want_map!r}")
+    if want_map and not ssim:
+        raise ValueError(f"{who}: want_map needs ssim (it is False: no SSIM is computed)")
+    return float(np.float32(peak)), float(np.float32(eps)), bool(ssim), bool(want_map)
+
+
+def metrics_derive(sums, peak=1.0, ssim=True):
+    """mid_image_metrics_derive: the derived values of 16 raw sums as a dict.  Host-only (no GPU)."""
+    sums = np.ascontiguousarray(sums, dtype=np.float64)
+    if sums.shape != (METRICS_N,):
+        raise ValueError(f"metrics_derive: sums must be {METRICS_N} float64 values, got {sums.shape}")
+    p = ImageMetricsParams(0, 0, 0, 0, peak, 1.0, int(bool(ssim)))
+    r = ImageMetricsResult()
+    _check(lib.mid_image_metrics_derive(sums.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(p), ctypes.byref(r)),
+           "mid_image_metrics_derive")
+    return {name: getattr(r, name) for name, _ in ImageMetricsResult._fields_}
 
 
 def _layer_sigmas(sigmas, n_layers, who, noun="sigmas"):

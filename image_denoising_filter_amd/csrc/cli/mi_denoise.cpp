@@ -87,6 +87,11 @@ struct Options {
     long pinned_mb = 16384;         // animation mode: at most this much page-locked host memory (inputs + outputs); the rest is pageable
     int io_threads = 0;             // animation mode: files decoded / encoded at a time (0 = min(16, hardware threads))
     bool half = false;              // GPU modes and animation, .exr inputs: frames as RGBA16F (mid_image_load_f16), HALF EXR outputs
+    bool compare = false;           // --compare TEST REFERENCE: the sub-mode that measures and filters nothing (mid_image_metrics)
+    std::string compare_test, compare_ref;
+    float peak = 1.f, relmse_eps = 1e-2f;      // --peak, --relmse-eps (mid_image_metrics_params)
+    bool compare_ssim = true;       // --no-ssim clears it
+    const char *compare_other = nullptr;       // the first of --peak / --relmse-eps / --no-ssim given
 };
 
 #define MID_CHECK(call)                                                                          \
@@ -174,6 +179,41 @@ struct TraceRange {
     TraceRange(const TraceRange &) = delete;
     TraceRange &operator=(const TraceRange &) = delete;
 };
+
+// Frame / layer discovery, src/main.cpp:1343-1378, for any frame of a sequence: its siblings of its extension and ITS OWN layers
+// (the files one directory down whose path holds its id).  Differences from the reference, all documented in DESIGN.md: entries are
+// sorted by name (the reference uses directory order, which is unspecified), and the 4-character frame id comes from the file name's
+// stem (the reference's find(".") breaks on "./x").  The one statement of the rule: DenoiseApplication::discover_for and --compare's
+// pairing both call it.
+static std::string frame_id_of(const fs::path &f)
+{
+    const std::string stem = f.stem().string();
+    return stem.size() >= 4 ? stem.substr(stem.size() - 4) : stem;
+}
+
+static void discover_files(const std::string &image, std::vector<std::string> &frames, std::vector<std::string> &layers, bool want_frames,
+                           bool want_layers)
+{
+    const fs::path target(image);
+    fs::path parent = target.parent_path();
+    if (parent.empty()) parent = ".";
+    const std::string imageID = frame_id_of(target);
+    std::vector<fs::path> entries;
+    for (auto &p : fs::directory_iterator(parent)) entries.push_back(p.path());
+    std::sort(entries.begin(), entries.end());
+    for (auto &e : entries) {
+        if (fs::is_directory(e)) {
+            if (!want_layers) continue;
+            std::vector<fs::path> inner;
+            for (auto &pp : fs::directory_iterator(e)) inner.push_back(pp.path());
+            std::sort(inner.begin(), inner.end());
+            for (auto &l : inner)
+                if (!fs::is_directory(l) && l.string().find(imageID) != std::string::npos) layers.push_back(l.string());
+        } else if (e.extension() == target.extension() && want_frames) {
+            frames.push_back(e.string());
+        }
+    }
+}
 
 class DenoiseApplication {
     Options opt;
@@ -290,37 +330,16 @@ public:
     double GetTransferMs() const { return m_transferMs; }
     double GetExecMs() const { return m_execMs; }
 
-    // Frame / layer discovery, src/main.cpp:1343-1378.  Differences, all documented in DESIGN.md:
-    // entries are sorted by name (the reference uses directory order, which is unspecified), and the
-    // 4-character frame id comes from the file name's stem (the reference's find(".") breaks on "./x").
+    // Frame / layer discovery: discover_files above, for the target image ...
     void discover(std::vector<std::string> &frames, std::vector<std::string> &layers, bool want_frames, bool want_layers) const
     {
-        discover_for(opt.image, frames, layers, want_frames, want_layers);
+        discover_files(opt.image, frames, layers, want_frames, want_layers);
     }
-    // The same rule for any frame of the sequence: its siblings and ITS OWN layers (the layer files whose path holds its id).
+    // ... and for any frame of the sequence: its siblings and ITS OWN layers.
     void discover_for(const std::string &image, std::vector<std::string> &frames, std::vector<std::string> &layers, bool want_frames,
                       bool want_layers) const
     {
-        const fs::path target(image);
-        fs::path parent = target.parent_path();
-        if (parent.empty()) parent = ".";
-        const std::string stem = target.stem().string();
-        const std::string imageID = stem.size() >= 4 ? stem.substr(stem.size() - 4) : stem;
-        std::vector<fs::path> entries;
-        for (auto &p : fs::directory_iterator(parent)) entries.push_back(p.path());
-        std::sort(entries.begin(), entries.end());
-        for (auto &e : entries) {
-            if (fs::is_directory(e)) {
-                if (!want_layers) continue;
-                std::vector<fs::path> inner;
-                for (auto &pp : fs::directory_iterator(e)) inner.push_back(pp.path());
-                std::sort(inner.begin(), inner.end());
-                for (auto &l : inner)
-                    if (!fs::is_directory(l) && l.string().find(imageID) != std::string::npos) layers.push_back(l.string());
-            } else if (e.extension() == target.extension() && want_frames) {
-                frames.push_back(e.string());
-            }
-        }
+        discover_files(image, frames, layers, want_frames, want_layers);
     }
 
     // RunOnGPU, src/main.cpp:1307-1730
@@ -1002,6 +1021,109 @@ public:
     }
 };
 
+// ---- --compare TEST REFERENCE: full-reference metrics (mid_image_metrics, section a4n) ------------------------------------------
+// A sub-mode that runs no filter and writes no image: both files are decoded (.png as RGBA8, .exr as RGBA32F or, with --half, as
+// RGBA16F; the two may differ in type), uploaded and compared on one stream, pair by pair, and one line per pair is printed whose
+// numbers read back bit for bit (%.17g).  With --animation TEST's siblings of its extension are paired with REFERENCE's by the
+// 4-character frame id of discover_files's rule, and a last line gives the means of the per-frame values.
+static std::string metrics_number(double v)
+{
+    char buf[64];
+    if (std::isnan(v)) return "nan";                            // (printf would print the sign of a NaN)
+    snprintf(buf, sizeof buf, "%.17g", v);
+    return buf;
+}
+
+static std::string metrics_fields(const mid_image_metrics_result &r)
+{
+    return "n " + metrics_number(r.n_valid) + " invalid " + metrics_number(r.n_invalid) + " mse " + metrics_number(r.mse) + " psnr " +
+           metrics_number(r.psnr) + " mae " + metrics_number(r.mae) + " max " + metrics_number(r.max_abs) + " relmse " + metrics_number(r.relmse) +
+           " ssim " + metrics_number(r.ssim);
+}
+
+// the siblings of `image` with its extension, sorted by name: discover_files's frames, no layers
+static std::vector<std::string> compare_siblings(const std::string &image)
+{
+    std::vector<std::string> frames, none;
+    discover_files(image, frames, none, true, false);
+    return frames;
+}
+
+static void run_compare(const Options &opt)
+{
+    std::vector<std::pair<std::string, std::string>> pairs;
+    if (!opt.animation) pairs.emplace_back(opt.compare_test, opt.compare_ref);
+    else {
+        const std::vector<std::string> tests = compare_siblings(opt.compare_test), refs = compare_siblings(opt.compare_ref);
+        for (size_t i = 0; i < tests.size(); ++i) {
+            const std::string id = frame_id_of(tests[i]);
+            for (size_t k = 0; k < i; ++k)
+                if (frame_id_of(tests[k]) == id)
+                    throw std::runtime_error("--compare: test frames " + tests[k] + " and " + tests[i] + " share the frame id " + id + " and so the partner");
+            std::vector<std::string> found;
+            for (const std::string &r : refs) if (frame_id_of(r) == id) found.push_back(r);
+            if (found.empty()) throw std::runtime_error("--compare: test frame " + tests[i] + " has no partner with the frame id " + id + " beside " + opt.compare_ref);
+            if (found.size() > 1) throw std::runtime_error("--compare: test frame " + tests[i] + " has two partners, " + found[0] + " and " + found[1]);
+            pairs.emplace_back(tests[i], found[0]);
+        }
+        if (pairs.empty()) throw std::runtime_error("--compare: no frames beside " + opt.compare_test);
+    }
+
+    mid_ctx *ctx = nullptr;
+    MID_CHECK(mid_ctx_create(opt.device, &ctx));
+    struct CtxGuard { mid_ctx *c; ~CtxGuard() { mid_ctx_destroy(c); } } guard{ctx};
+    struct Dev {                                                // one device buffer, grown on demand, freed with the run
+        mid_ctx *c; void *p = nullptr; size_t n = 0;
+        ~Dev() { if (p) (void)mid_free(c, p); }
+        void *need(size_t bytes)
+        {
+            if (bytes > n) { if (p) { MID_CHECK(mid_free(c, p)); p = nullptr; n = 0; } MID_CHECK(mid_alloc(c, bytes, &p)); n = bytes; }
+            return p;
+        }
+    } da{ctx}, db{ctx}, dwork{ctx};
+    struct Img { mid_image img{}; ~Img() { if (img.data) mid_image_free(&img); } };
+    auto load = [&](const std::string &path, Img &im) {
+        const bool hdr = fs::path(path).extension() == ".exr";
+        if (hdr && opt.half ? mid_image_load_f16(nullptr, path.c_str(), &im.img) : mid_image_load(path.c_str(), &im.img)) throw std::runtime_error(mid_last_error());
+    };
+    auto bytes_of = [](const mid_image &i) { return (size_t)i.width * i.height * (i.format == MID_FMT_RGBA32F ? 16 : i.format == MID_FMT_RGBA16F ? 8 : 4); };
+
+    double mean[11] = {0};
+    for (const auto &pr : pairs) {
+        Img a, b;
+        {                                                       // the two files of a pair decode side by side: the run is decode-bound
+            std::string err_b;
+            std::thread tb([&] { try { load(pr.second, b); } catch (const std::exception &e) { err_b = e.what(); if (err_b.empty()) err_b = pr.second; } });
+            try { load(pr.first, a); } catch (...) { tb.join(); throw; }
+            tb.join();
+            if (!err_b.empty()) throw std::runtime_error(err_b);
+        }
+        if (a.img.width != b.img.width || a.img.height != b.img.height)
+            throw std::runtime_error("--compare: " + pr.first + " is " + std::to_string(a.img.width) + "x" + std::to_string(a.img.height) + " but " + pr.second +
+                                     " is " + std::to_string(b.img.width) + "x" + std::to_string(b.img.height));
+        mid_image_metrics_params p{a.img.width, a.img.height, a.img.format, b.img.format, opt.peak, opt.relmse_eps, opt.compare_ssim ? 1 : 0};
+        const size_t nw = mid_image_metrics_workspace(p.width, p.height);
+        if (!nw) throw std::runtime_error("--compare: " + pr.first + ": a frame of " + std::to_string(p.width) + "x" + std::to_string(p.height) + " is too large");
+        void *pa = da.need(bytes_of(a.img)), *pb = db.need(bytes_of(b.img)), *pw = dwork.need(nw);
+        MID_CHECK(mid_memcpy_h2d(ctx, pa, a.img.data, bytes_of(a.img), nullptr));
+        MID_CHECK(mid_memcpy_h2d(ctx, pb, b.img.data, bytes_of(b.img), nullptr));
+        MID_CHECK(mid_image_metrics(ctx, &p, pa, pb, pw, nullptr, nullptr));
+        double sums[MID_METRICS_N];
+        MID_CHECK(mid_memcpy_d2h(ctx, sums, pw, sizeof sums, nullptr));
+        MID_CHECK(mid_stream_sync(ctx, nullptr));
+        mid_image_metrics_result r;
+        MID_CHECK(mid_image_metrics_derive(sums, &p, &r));
+        std::cout << "metrics " << pr.first << " vs " << pr.second << " " << metrics_fields(r) << "\n";
+        const double vals[11] = {r.n_valid, r.n_invalid, r.mse, r.mse_r, r.mse_g, r.mse_b, r.mae, r.max_abs, r.psnr, r.relmse, r.ssim};
+        for (int i = 0; i < 11; ++i) mean[i] += vals[i];
+    }
+    if (opt.animation) {
+        const double n = (double)pairs.size();
+        mid_image_metrics_result m{mean[0] / n, mean[1] / n, mean[2] / n, mean[3] / n, mean[4] / n, mean[5] / n, mean[6] / n, mean[7] / n, mean[8] / n, mean[9] / n, mean[10] / n};
+        std::cout << "metrics mean over " << pairs.size() << " frames " << metrics_fields(m) << "\n";
+    }
+}
+
 static void usage()
 {
     std::cout <<
@@ -1147,6 +1269,18 @@ static void usage()
         "                            channels bit for bit), filter them as such and write HALF EXR outputs (the fp32 result rounded\n"
         "                            to nearest even).  PNG inputs and the CPU runs ignore it; not with --halo rccl.  .exr LAYERS of\n"
         "                            the bilateral modes load as RGBA16F with it as well, whatever the frames are\n"
+        "  --compare TEST REFERENCE  a sub-mode that runs no filter and writes no image: how close TEST is to REFERENCE (a converged\n"
+        "                            render, usually), over the pixels whose R, G and B are finite in both.  One line is printed:\n"
+        "                            metrics <test> vs <reference> n <valid> invalid <k> mse <..> psnr <..> mae <..> max <..> relmse <..>\n"
+        "                            ssim <..>, every number with 17 significant digits (it reads back bit for bit).  .png files load as\n"
+        "                            RGBA8, .exr as RGBA32F or, with --half, as RGBA16F; the two may differ in type, not in size.\n"
+        "                            With --animation TEST's siblings of its extension are paired with REFERENCE's siblings by the\n"
+        "                            4-character frame id: one line per pair in sorted order, then `metrics mean over <n> frames ...`,\n"
+        "                            the means of the per-frame values; a test frame with no partner, or a partner shared by two, is\n"
+        "                            refused by name.  Not with --modes, --animation-filter or --gpus\n"
+        "  --peak X                  with --compare: the data range PSNR and SSIM refer to, finite and > 0 (default 1; 255 for integer levels)\n"
+        "  --relmse-eps X            with --compare: relMSE is the mean of d^2 / (reference^2 + X), finite and > 0 (default 0.01)\n"
+        "  --no-ssim                 with --compare: the pointwise metrics only; ssim is printed as nan\n"
         "  --cpu-radius R --cpu-sigma-s S --cpu-sigma-c C   CPU path (default 10 10.0 0.2)\n"
         "  --cpu-threads A,B         thread counts of the CPU runs (default 1,8)\n"
         "  --cpu-fix-blue            use the blue channel in the CPU range distance (the reference does not)\n";
@@ -1157,14 +1291,26 @@ static bool pair_arg(const char *s, int &a, int &b) { return sscanf(s, "%d,%d", 
 int main(int argc, char **argv)
 {
     Options opt;
-    bool have_image = false;
+    bool have_image = false, modes_given = false, filter_given = false, gpus_given = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char * { if (i + 1 >= argc) { usage(); exit(EXIT_FAILURE); } return argv[++i]; };
         if (a == "-h" || a == "--help") { usage(); return EXIT_SUCCESS; }
         else if (a == "--outdir") opt.outdir = next();
         else if (a == "--device") opt.device = atoi(next());
-        else if (a == "--modes") opt.modes = next();
+        else if (a == "--modes") { opt.modes = next(); modes_given = true; }
+        else if (a == "--compare") { opt.compare = true; opt.compare_test = next(); opt.compare_ref = next(); }
+        else if (a == "--peak") {
+            opt.peak = (float)atof(next());
+            if (!opt.compare_other) opt.compare_other = "--peak";
+            if (!(std::isfinite(opt.peak) && opt.peak > 0.f)) { std::cerr << "--peak " << opt.peak << " must be finite and > 0\n"; return EXIT_FAILURE; }
+        }
+        else if (a == "--relmse-eps") {
+            opt.relmse_eps = (float)atof(next());
+            if (!opt.compare_other) opt.compare_other = "--relmse-eps";
+            if (!(std::isfinite(opt.relmse_eps) && opt.relmse_eps > 0.f)) { std::cerr << "--relmse-eps " << opt.relmse_eps << " must be finite and > 0\n"; return EXIT_FAILURE; }
+        }
+        else if (a == "--no-ssim") { opt.compare_ssim = false; if (!opt.compare_other) opt.compare_other = "--no-ssim"; }
         else if (a == "--gpu-only") opt.run_cpu = false;
         else if (a == "--cpu-only") opt.run_gpu = false;
         else if (a == "--radius") opt.radius = atoi(next());
@@ -1243,6 +1389,7 @@ int main(int argc, char **argv)
         else if (a == "--temporal-k") opt.temporal_k = atoi(next());
         else if (a == "--animation") opt.animation = true;
         else if (a == "--animation-filter") {
+            filter_given = true;
             opt.animation_filter = next();
             if (!animation_filter(opt.animation_filter)) {
                 std::string names;
@@ -1250,7 +1397,7 @@ int main(int argc, char **argv)
                 std::cerr << "unknown --animation-filter " << opt.animation_filter << " (" << names << ")\n"; usage(); return EXIT_FAILURE; }
         }
         else if (a == "--half") opt.half = true;
-        else if (a == "--gpus") opt.gpus = atoi(next());
+        else if (a == "--gpus") { opt.gpus = atoi(next()); gpus_given = true; }
         else if (a == "--share-device") opt.share_device = true;
         else if (a == "--pinned-mb") opt.pinned_mb = atol(next());
         else if (a == "--io-threads") opt.io_threads = atoi(next());
@@ -1286,6 +1433,15 @@ int main(int argc, char **argv)
         return EXIT_FAILURE;
     }
     if (opt.history_clip_radius_given && !opt.history_clip) { std::cerr << "--history-clip-radius needs --history-clip\n"; return EXIT_FAILURE; }
+    if (opt.compare_other && !opt.compare) { std::cerr << opt.compare_other << " applies to --compare only\n"; return EXIT_FAILURE; }
+    if (opt.compare) {
+        const char *with = modes_given ? "--modes" : filter_given ? "--animation-filter" : gpus_given ? "--gpus" : nullptr;
+        if (with) { std::cerr << "--compare runs no filter: it cannot be combined with " << with << "\n"; return EXIT_FAILURE; }
+        if (have_image) { std::cerr << "--compare takes its two files itself: the positional image " << opt.image << " has no meaning with it\n"; return EXIT_FAILURE; }
+        try { run_compare(opt); }
+        catch (const std::exception &e) { std::cout.flush(); std::cerr << e.what() << "\n"; return EXIT_FAILURE; }   // stdout holds `metrics` lines only
+        return EXIT_SUCCESS;
+    }
     if (listed("atrous-recursive")) {
         std::cerr << "--modes atrous-recursive: the recursion needs a sequence; it is an animation filter (--animation --animation-filter atrous-recursive)\n";
         return EXIT_FAILURE;

@@ -296,6 +296,11 @@ int firefly_check(const mid_firefly_params *p, const char *who);
 int color_bounds_out(mid_ctx *ctx, const mid_color_bounds_params *p, const void *in, mid_pixel *lo, mid_pixel *hi, hipStream_t s);
 int color_bounds_check(const mid_color_bounds_params *p, const char *who);
 
+// mid_image_metrics without its pointer checks (the caller has made them), two launches on `s`: image_metrics.hip.
+// image_metrics_check: the size, the two format words, peak, eps and the ssim flag.
+int image_metrics_out(mid_ctx *ctx, const mid_image_metrics_params *p, const void *a, const void *b, void *work, float *map, hipStream_t s);
+int image_metrics_check(const mid_image_metrics_params *p, const char *who);
+
 // ROCTx ranges (csrc/markers.cpp): no-ops unless the process already holds a ROCTx (rocprofv3 --marker-trace preloads one).
 bool markers_active();
 void range_push(const char *name);

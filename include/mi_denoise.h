@@ -1026,6 +1026,92 @@ int mid_sequence_atrous_recursive_clip(mid_ctx *ctx, const mid_temporal_accum_pa
                                        int feedback /* 0 | 1 */, int warmup /* >= 0 */, int first, int count,
                                        void *const *host_out, int out_format, int overlap, float *timings_ms);
 
+/* ---- a4n: full-reference image quality metrics ------------------------------------------------
+ * What tells one setting of the chain above from another: the distance of a test image `a` from a reference image `b` (a
+ * converged render, usually) as MSE, PSNR, MAE, the largest difference, relMSE and SSIM.  The sums are taken on the GPU by a
+ * reduction whose bits depend on the inputs and the parameters alone; the definitions of the derived values are one host function.
+ * a and b have p->width x p->height texels, each in its own format (MID_FMT_RGBA8 | RGBA16F | RGBA32F, no guide bits); alpha is
+ * ignored; a == b is allowed.  Texels are widened as a4i widens a frame and then converted to binary64, which is exact.
+ * A pixel is VALID iff R, G and B of both a(p) and b(p) are finite.  Everything below runs over valid pixels only, in binary64.
+ *
+ * Pointwise sums, with d_c = a_c - b_c (one binary64 subtraction): the numbers of valid and of not valid pixels; per channel
+ * sum d_c^2, sum |d_c| and sum d_c^2 / (b_c^2 + eps) (one multiplication, one addition, one division per term); max |d_c| over
+ * pixels and channels.
+ *
+ * SSIM (Wang, Bovik, Sheikh, Simoncelli 2004), with p->ssim == 1, on a4i's luminance l() taken in fp32 exactly as a4i takes it and
+ * then widened to binary64 (la, lb):
+ *   window    q = p + (i, j), |i|, |j| <= 5, q inside the image and VALID;   w(q) = g_|i| * g_|j|,  g_k = exp(-k^2 / 4.5)
+ *             (a Gaussian of sigma 1.5), the six binary64 constants MID_METRICS_G0 .. MID_METRICS_G5 below
+ *   W = sum w.  Taps that are missing are skipped and the weights renormalised, as every filter here treats the border.
+ *   mu_a = (sum w la) / W;  S_aa = (sum w la^2) / W - mu_a^2;  likewise mu_b, S_bb;  S_ab = (sum w la lb) / W - mu_a mu_b.  No clamping.
+ *   C1 = (0.01 peak)^2,  C2 = (0.03 peak)^2
+ *   ssim(p) = ((2 mu_a mu_b + C1) (2 S_ab + C2)) / ((mu_a^2 + mu_b^2 + C1) (S_aa + S_bb + C2))      for a VALID centre p
+ * The order of the sums is the kernel's own: per row of the window the eleven taps left to right, then the eleven rows top to
+ * bottom, each moment by fma.  With a == b every expression of the numerator equals its partner of the denominator bit for bit, so
+ * ssim(p) is exactly 1.0.  Scaling a, b and peak by 2^k and eps by 4^k leaves relMSE's sums and every ssim(p) unchanged, bit for
+ * bit, while nothing leaves the normal range.  A VALID pixel whose fp32 luminance overflows takes part as +-Inf: the ssim of the
+ * windows that hold it is NaN, and so is the sum.
+ * map: NULL, or a width x height float plane that receives ssim(p) rounded to fp32 and a quiet NaN where p is not VALID.  With
+ * p->ssim == 0 map must be NULL and the SSIM sum is 0.
+ *
+ * Result and workspace.  work: a caller-owned device buffer of mid_image_metrics_workspace(width, height) bytes, 16-byte aligned.
+ * After the call its first MID_METRICS_N doubles are the sums, at the MID_METRICS_* indices below (slots 13 .. 15 are 0); the rest
+ * is scratch.  Nothing is kept in the context: two calls on two streams with two workspaces cannot meet.
+ * Determinism: the frame is cut into the firefly clamp's 64 x 16 tiles (csrc/firefly_tile.hpp) and min(tiles, 4096) workgroups are
+ * launched -- a number that depends on the size alone, not on the device; workgroup g takes the tiles g, g + G, ... in that order,
+ * a lane adds its four pixels of every tile top to bottom, the lanes of a wave are added by a butterfly, the four waves in index
+ * order, and the workgroup stores one row of MID_METRICS_N partials to `work`; a second launch of one workgroup adds the rows in
+ * index order, sixty-four interleaved chains joined by a fixed tree.  No atomics.  p->ssim == 0 runs the same reduction without the
+ * windows: its pointwise sums have the bits of p->ssim == 1.
+ * Class (csrc/image_metrics.hip): tiled, a workgroup of four waves per 64 x 16 tile, lanes along x, a lane owning
+ * four pixels of one column; with ssim two LDS tiles of (64 + 10) x (16 + 10) fp32 luminances (15392 bytes), NaN in the first
+ * where the pixel is outside the image or not VALID -- a marker that gives the tap weight 0 by a select; the horizontal eleven-tap
+ * sums of w, w la, w lb, w la^2, w lb^2, w la lb of a lane's fourteen rows stay in registers and feed the vertical sums of its four
+ * pixels.  Index arithmetic in size_t; the formats are run-time, wave-uniform values.
+ * MID_ERR_INVALID before anything is queued, `work` and `map` untouched: a NULL ctx, p, a, b or work; width or height < 1, or
+ * 2^30 pixels and more; an unknown format, or guide bits set; a or b not aligned to its texel, work not to 16 bytes, map not to
+ * 4; peak or eps not finite or <= 0; ssim outside {0, 1}; map given with ssim == 0; work or map overlapping an input or each other. */
+#define MID_METRICS_N 16
+enum {
+    MID_METRICS_N_VALID = 0, MID_METRICS_N_INVALID = 1,
+    MID_METRICS_SQ_R = 2, MID_METRICS_SQ_G = 3, MID_METRICS_SQ_B = 4,           /* sum d_c^2 */
+    MID_METRICS_ABS_R = 5, MID_METRICS_ABS_G = 6, MID_METRICS_ABS_B = 7,        /* sum |d_c| */
+    MID_METRICS_MAX_ABS = 8,                                                    /* max |d_c| */
+    MID_METRICS_REL_R = 9, MID_METRICS_REL_G = 10, MID_METRICS_REL_B = 11,      /* sum d_c^2 / (b_c^2 + eps) */
+    MID_METRICS_SSIM = 12                                                       /* sum ssim(p); 13 .. 15 are 0 */
+};
+/* g_k = exp(-k^2 / 4.5), k = 0 .. 5, to the nearest binary64 */
+#define MID_METRICS_G0 1.0
+#define MID_METRICS_G1 0.80073740291680806
+#define MID_METRICS_G2 0.41111229050718745
+#define MID_METRICS_G3 0.1353352832366127
+#define MID_METRICS_G4 0.028565500784550377
+#define MID_METRICS_G5 0.0038659201394728076
+typedef struct mid_image_metrics_params {
+    int32_t width, height;
+    int32_t format_a, format_b;   /* MID_FMT_* of `a` and of `b`; guide bits must be 0 */
+    float   peak;                 /* finite, > 0: the data range (1 for unit-range frames, 255 for integer levels); default 1 */
+    float   eps;                  /* finite, > 0: relMSE's regulariser, in squared units of the data; default 1e-2 */
+    int32_t ssim;                 /* 0 | 1 */
+} mid_image_metrics_params;
+typedef struct mid_image_metrics_result {
+    double n_valid, n_invalid;
+    double mse;                   /* (sum over c of sum d_c^2) / (3 n_valid) */
+    double mse_r, mse_g, mse_b;   /* (sum d_c^2) / n_valid */
+    double mae;                   /* (sum over c of sum |d_c|) / (3 n_valid) */
+    double max_abs;               /* max |d_c|; 0 where nothing is valid */
+    double psnr;                  /* 10 log10(peak^2 / mse); +Inf at mse == 0 */
+    double relmse;                /* (sum over c of sum d_c^2 / (b_c^2 + eps)) / (3 n_valid) */
+    double ssim;                  /* (sum ssim(p)) / n_valid; NaN with p->ssim == 0: it was not computed */
+} mid_image_metrics_result;
+size_t mid_image_metrics_workspace(int width, int height);   /* 0 for a size mid_image_metrics refuses */
+int mid_image_metrics(mid_ctx *ctx, const mid_image_metrics_params *p, const void *a, const void *b, void *work,
+                      float *map /* width * height floats, or NULL */, void *stream);
+/* The derived values of MID_METRICS_N sums copied to the host: a pure host function, the one statement of the definitions in the
+ * struct above.  Every ratio is NaN at n_valid == 0.  Reads width / height of p not at all: peak and ssim only.
+ * MID_ERR_INVALID for a NULL pointer, or peak not finite or <= 0. */
+int mid_image_metrics_derive(const double *sums_host, const mid_image_metrics_params *p, mid_image_metrics_result *out);
+
 /* ---- a5: normalize ----------------------------------------------------------------------
  * One dispatch of shaders/normalize.comp (RecordCommandsOfExecuteAndTransfer(normKernel=true)):
  * out = weightColor / normWeight, or (1,0,1,1) where normWeight == 0; bindings {0: out; 1: W}. */
