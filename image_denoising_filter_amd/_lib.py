@@ -101,6 +101,12 @@ class ImageMetricsResult(ctypes.Structure):
 METRICS_N = 16      # MID_METRICS_N
 
 
+class GuidedParams(ctypes.Structure):
+    """mid_guided_params (section a4o)."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("radius", ctypes.c_int32), ("eps", ctypes.c_float),
+                ("format", ctypes.c_int32)]
+
+
 class NormalizeParams(ctypes.Structure):
     _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32)]
 
@@ -201,6 +207,10 @@ _SIGNATURES = {
     "mid_image_metrics": (ctypes.c_int, [_P, ctypes.POINTER(ImageMetricsParams), _P, _P, _P, _P, _P]),
     "mid_image_metrics_derive": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ImageMetricsParams),
                                                 ctypes.POINTER(ImageMetricsResult)]),
+    "mid_guided_workspace": (ctypes.c_int, [ctypes.POINTER(GuidedParams), ctypes.POINTER(ctypes.c_size_t)]),
+    "mid_guided_filter": (ctypes.c_int, [_P, ctypes.POINTER(GuidedParams), _P, _P, _P, _P, ctypes.c_int, _P]),
+    "mid_sequence_guided": (ctypes.c_int, [_P, ctypes.POINTER(GuidedParams), c_void_pp, ctypes.c_int, c_void_pp, ctypes.c_int, ctypes.c_int,
+                                           c_void_pp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
     "mid_normalize": (ctypes.c_int, [_P, ctypes.POINTER(NormalizeParams), _P, _P, _P]),
     "mid_unpack_u8": (ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_int, _P, _P]),
     "mid_pack_u8": (ctypes.c_int, [_P, _P, ctypes.c_size_t, _P, _P]),

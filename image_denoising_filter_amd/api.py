@@ -15,7 +15,7 @@ import weakref
 
 import numpy as np
 
-from ._lib import AlbedoParams, AtrousMomentsParams, AtrousParams, AtrousVarianceParams, BilateralParams, ColorBoundsParams, FireflyParams, Image, ImageMetricsParams, ImageMetricsResult, METRICS_N, NlmParams, NormalizeParams, TemporalAccumParams, c_void_pp, lib
+from ._lib import AlbedoParams, AtrousMomentsParams, AtrousParams, AtrousVarianceParams, BilateralParams, ColorBoundsParams, FireflyParams, GuidedParams, Image, ImageMetricsParams, ImageMetricsResult, METRICS_N, NlmParams, NormalizeParams, TemporalAccumParams, c_void_pp, lib
 
 FMT_RGBA32F, FMT_RGBA8, FMT_RGBA16F = 0, 1, 2
 
@@ -682,6 +682,34 @@ class Context:
             out["map"] = self.download(d_map, (h, w), np.float32)
         return out
 
+    def guided_filter(self, frame, guide=None, radius=8, eps=1e-2, out_dtype=None):
+        """The guided filter (mid_guided_filter, section a4o): inside every (2 radius + 1)^2 window the frame is fitted as an affine
+        function of the guide's colour, and the averaged fit is evaluated at the pixel's own guide texel; alpha unchanged, a pixel
+        with a non-finite colour (in the frame or in the guide) passes through.  frame, guide: (h, w, 4) uint8, float16 or float32 of
+        one shape, each with its own dtype; guide=None: the frame guides itself.  eps: the regulariser, in squared guide units.
+        Returns (h, w, 4) in out_dtype (None = float32; uint8 and float16 with the rounding of pack_u8 / pack_f16)."""
+        who = "guided_filter"
+        frame = _img(frame)
+        if frame.dtype not in [np.dtype(d) for d in _GUIDE_DTYPES]:
+            raise ValueError(f"{who}: the frame must be uint8 / float16 / float32, got {frame.dtype}")
+        if guide is not None:
+            guide = _img(guide)
+            if guide.dtype not in [np.dtype(d) for d in _GUIDE_DTYPES]:
+                raise ValueError(f"{who}: the guide must be uint8 / float16 / float32, got {guide.dtype}")
+            if guide.shape != frame.shape:
+                raise ValueError(f"{who}: the frame is {frame.shape} but the guide is {guide.shape}: the two must have one size")
+        radius, eps = _guided_args(radius, eps, who)
+        out_dtype = _guided_out_dtype(out_dtype, who)
+        h, w = frame.shape[:2]
+        p = GuidedParams(w, h, radius, eps, fmt_with_guide(_fmt_of(frame), _fmt_of(frame if guide is None else guide)))
+        nbytes = ctypes.c_size_t()
+        _check(lib.mid_guided_workspace(ctypes.byref(p), ctypes.byref(nbytes)), "mid_guided_workspace")
+        d_in, d_g = self.upload(frame), None if guide is None else self.upload(guide)
+        d_work, d_out = self.alloc(nbytes.value), self.alloc(w * h * 4 * out_dtype.itemsize)
+        _check(lib.mid_guided_filter(self.handle, ctypes.byref(p), d_in.ptr, None if d_g is None else d_g.ptr, d_work.ptr, d_out.ptr,
+                                     _OUT_FMT[out_dtype], None), "mid_guided_filter")
+        return self.download(d_out, (h, w, 4), out_dtype)
+
     def normalize(self, W):
         """normalize.comp."""
         W = np.ascontiguousarray(W, dtype=np.float32)
@@ -976,6 +1004,47 @@ class Context:
             hin, hout, w, h, fmt, hlayers, n_layers, sigmas, passes, first_pass, color_sigma, first, count, overlap, out_dtype),
             frames, layers, _GUIDE_DTYPES, first, count, pinned, pinned_out, out_dtype)
 
+    def sequence_guided_pinned(self, hin, hout, w, h, fmt, hguides=None, radius=8, eps=1e-2, first=0, count=None, overlap=True, out_dtype=None):
+        """mid_sequence_guided on host pointers the caller already holds: nothing but the C call.  hin: all n frames of the sequence;
+        hguides: None (the frames guide themselves) or n host pointers, one guide plane per frame (RGBA8, or what fmt_with_guide
+        names in `fmt`); hout: `count` output buffers.  Returns (wall_ms of the whole call, kernel_ms, copy_ms)."""
+        n = len(hin)
+        count = n - first if count is None else count
+        radius, eps = _guided_args(radius, eps, "sequence_guided")
+        if len(hout) < count:
+            raise ValueError(f"{count} outputs, {len(hout)} output buffers given")
+        if hguides is not None and len(hguides) != n:
+            raise ValueError(f"{n} frames, {len(hguides)} guide pointers given")
+        prm = GuidedParams(w, h, radius, eps, fmt)
+        t = (ctypes.c_float * 3)()
+        _check(lib.mid_sequence_guided(self.handle, ctypes.byref(prm), (ctypes.c_void_p * n)(*hin), n,
+                                       None if hguides is None else (ctypes.c_void_p * n)(*hguides), first, count,
+                                       (ctypes.c_void_p * max(count, 1))(*hout[:max(count, 0)]), _OUT_FMT[_guided_out_dtype(out_dtype, "sequence_guided")],
+                                       1 if overlap else 0, t), "mid_sequence_guided")
+        return tuple(t)
+
+    def sequence_guided(self, frames, guides=None, radius=8, eps=1e-2, first=0, count=None, overlap=True, pinned=True, out_dtype=None):
+        """Outputs [first, first+count) of an animation through the overlapped pipeline with the guided filter as its compute stage
+        (mid_sequence_guided): output t is ctx.guided_filter(frames[t], guides[t], radius, eps) in out_dtype.  guides: None, or one
+        (h, w, 4) uint8 / float16 / float32 plane per frame, all of one dtype.  pinned=False: the NumPy arrays themselves (pageable
+        memory) are the sources and destinations.  Returns (outputs, (wall_ms, kernel_ms, copy_ms))."""
+        who = "sequence_guided"
+        _guided_args(radius, eps, who)
+        out_dtype = _guided_out_dtype(out_dtype, who)
+        frames = [_img(f) for f in frames]
+        for i, f in enumerate(frames):
+            if f.dtype not in [np.dtype(d) for d in _GUIDE_DTYPES]:
+                raise ValueError(f"{who}: frame {i} must be uint8 / float16 / float32, got {f.dtype}")
+        if guides is not None and len(guides) != len(frames):
+            raise ValueError(f"{who}: {len(guides)} guides for {len(frames)} frames")
+        layers = None if guides is None else [[g] for g in guides]
+        frames = _same_frames(frames, who)
+        if layers is not None:
+            _flat_layers(layers, len(frames), frames[0].shape[0], frames[0].shape[1], who, _GUIDE_DTYPES)
+        return self._sequence_host(who, lambda hin, hout, w, h, fmt, hlayers, n_layers, count: self.sequence_guided_pinned(
+            hin, hout, w, h, fmt, hlayers, radius, eps, first, count, overlap, out_dtype),
+            frames, layers, _GUIDE_DTYPES, first, count, pinned, pinned, out_dtype, plain=True)
+
     def sequence_atrous_joint_temporal_pinned(self, hin, hout, w, h, fmt, hlayers, n_layers, sigmas, k=2, first=0, count=None, passes=5,
                                               color_sigma=0.0, overlap=True, out_dtype=None):
         """mid_sequence_atrous_joint_temporal on host pointers the caller already holds: nothing but the C call.  hin, hlayers,
@@ -1168,6 +1237,24 @@ def _metrics_args(peak, eps, ssim, want_map, who):
     if want_map and not ssim:
         raise ValueError(f"{who}: want_map needs ssim (it is False: no SSIM is computed)")
     return float(np.float32(peak)), float(np.float32(eps)), bool(ssim), bool(want_map)
+
+
+def _guided_args(radius, eps, who):
+    """The keywords of guided_filter, checked before any GPU work: (radius, eps) in the ranges of mid_guided_params."""
+    if not isinstance(radius, (int, np.integer)) or isinstance(radius, bool) or not 1 <= radius <= 16:
+        raise ValueError(f"{who}: the radius must be an integer in 1..16, got {radius!r}")
+    if eps is None or isinstance(eps, bool) or not isinstance(eps, (int, float, np.integer, np.floating)):
+        raise ValueError(f"{who}: eps must be a number, finite and > 0, got {eps!r}")
+    if not (0 < float(eps) <= float(np.finfo(np.float32).max) and float(np.float32(eps)) > 0):   # (the C side reads a float)
+        raise ValueError(f"{who}: eps must be finite and > 0, got {float(eps)}")
+    return int(radius), float(np.float32(eps))
+
+
+def _guided_out_dtype(out_dtype, who):
+    dt = np.dtype(np.float32 if out_dtype is None else out_dtype)
+    if dt not in _OUT_FMT:
+        raise ValueError(f"{who}: out_dtype must be uint8, float16 or float32, got {dt}")
+    return dt
 
 
 def metrics_derive(sums, peak=1.0, ssim=True):

@@ -87,6 +87,10 @@ struct Options {
     long pinned_mb = 16384;         // animation mode: at most this much page-locked host memory (inputs + outputs); the rest is pageable
     int io_threads = 0;             // animation mode: files decoded / encoded at a time (0 = min(16, hardware threads))
     bool half = false;              // GPU modes and animation, .exr inputs: frames as RGBA16F (mid_image_load_f16), HALF EXR outputs
+    int guided_radius = 8;          // the guided filter (--modes guided, --animation-filter guided): mid_guided_params.radius, 1..16
+    float guided_eps = 1e-2f;       // and its regulariser, in squared guide units
+    std::string guide_layer;        // substring of the render element that is the guide; empty: every frame guides itself
+    const char *guided_other = nullptr;        // the first of --guided-radius / --guided-eps / --guide-layer given
     bool compare = false;           // --compare TEST REFERENCE: the sub-mode that measures and filters nothing (mid_image_metrics)
     std::string compare_test, compare_ref;
     float peak = 1.f, relmse_eps = 1e-2f;      // --peak, --relmse-eps (mid_image_metrics_params)
@@ -100,7 +104,7 @@ struct Options {
     } while (0)
 
 // --animation-filter, parsed once: the mid_sequence_* family a value runs, what that family reads, and the words of the value.
-enum SeqFamily { SEQ_NLM, SEQ_BILATERAL, SEQ_NLM_LAYERS, SEQ_NLM_LAYERS_TEMPORAL, SEQ_BILATERAL_TEMPORAL, SEQ_BILATERAL_JOINT, SEQ_NLM_JOINT, SEQ_ATROUS, SEQ_ATROUS_TEMPORAL, SEQ_ATROUS_VARIANCE, SEQ_ATROUS_RECURSIVE };
+enum SeqFamily { SEQ_NLM, SEQ_BILATERAL, SEQ_NLM_LAYERS, SEQ_NLM_LAYERS_TEMPORAL, SEQ_BILATERAL_TEMPORAL, SEQ_BILATERAL_JOINT, SEQ_NLM_JOINT, SEQ_ATROUS, SEQ_ATROUS_TEMPORAL, SEQ_ATROUS_VARIANCE, SEQ_ATROUS_RECURSIVE, SEQ_GUIDED };
 struct AnimationFilter {
     const char *name;
     SeqFamily family;
@@ -111,7 +115,7 @@ struct AnimationFilter {
     const char *words;      // of the summary line, before r= / the layers / k=
     const char *banner;     // "Running on GPU (animation, <banner>)"
     bool bilateral() const { return family == SEQ_BILATERAL || family == SEQ_BILATERAL_TEMPORAL || family == SEQ_BILATERAL_JOINT; }
-    bool windowed() const { return family != SEQ_BILATERAL && family != SEQ_NLM_LAYERS && family != SEQ_ATROUS; }     // blocks with k halo frames on either side
+    bool windowed() const { return family != SEQ_BILATERAL && family != SEQ_NLM_LAYERS && family != SEQ_ATROUS && family != SEQ_GUIDED; }     // blocks with k halo frames on either side
 };
 static const AnimationFilter kAnimationFilters[] = {
     {"nlm", SEQ_NLM, false, true, false, "", "", "temporal nonlocal"},
@@ -130,6 +134,8 @@ static const AnimationFilter kAnimationFilters[] = {
     {"atrous-temporal", SEQ_ATROUS_TEMPORAL, true, true, false, "nonlinear-atrous-multiframe-", "a-trous", "a-trous + layers, multiframe"},
     {"atrous-variance", SEQ_ATROUS_VARIANCE, true, true, false, "nonlinear-atrous-variance-", "variance-guided a-trous", "a-trous + layers, variance-guided"},
     {"atrous-recursive", SEQ_ATROUS_RECURSIVE, true, false, false, "nonlinear-atrous-recursive-", "recursive a-trous", "a-trous + layers, recursive accumulation"},
+    // (layers: the one render element --guide-layer names, if it is given; RunAnimation decides)
+    {"guided", SEQ_GUIDED, false, false, false, "nonlinear-guided-", "guided filter", "guided filter"},
 };
 static const AnimationFilter *animation_filter(const std::string &name)
 {
@@ -558,6 +564,79 @@ public:
         std::cout << "\tcleaning up\n";
     }
 
+    // --modes guided: the guided filter of the target (mid_guided_filter, section a4o), guided by the one render element --guide-layer
+    // names (.png as RGBA8, .exr as RGBA32F or, with --half, RGBA16F) or, without the option, by the target itself: no layer is loaded then.
+    // Output output-nonlinear-guided.{png,exr}; with --half on an .exr target the kernel stores RGBA16F and the file is a HALF EXR.
+    void RunGuided()
+    {
+        TraceRange mode_range("RunGuided");
+        m_execMs = m_transferMs = 0;
+        std::cout << "\tinit hip for device " << opt.device << "\n";
+        mid_ctx *ctx = nullptr;
+        MID_CHECK(mid_ctx_create(opt.device, &ctx));
+        struct CtxGuard { mid_ctx *c; ~CtxGuard() { mid_ctx_destroy(c); } } guard{ctx};
+        std::string guideName;
+        if (!opt.guide_layer.empty()) {
+            std::vector<std::string> none, layerNames, hits;
+            discover(none, layerNames, false, true);
+            for (const std::string &f : layerNames) if (fs::path(f).filename().string().find(opt.guide_layer) != std::string::npos) hits.push_back(f);
+            if (hits.size() != 1)
+                throw std::runtime_error(opt.image + ": --guide-layer " + opt.guide_layer + " matches " + std::to_string(hits.size()) +
+                                         " layer file(s) of this frame, it must match exactly one");
+            guideName = hits[0];
+        }
+        std::cout << "\tguided guide " << (guideName.empty() ? std::string("self") : guideName) << " radius " << opt.guided_radius << " eps " << opt.guided_eps << "\n";
+        std::cout << "\tloading image data\n";
+        const bool hdr = is_hdr(opt.image), half = hdr && opt.half;
+        mid_ctx *pin = opt.pageable_host ? nullptr : ctx;
+        HostImage target = load(opt.image, false, pin, half);
+        const int w = target.w, h = target.h, fmt = target.format;
+        const size_t npix = (size_t)w * h;
+        HostImage guide;
+        int gfmt = fmt;
+        if (!guideName.empty()) {
+            guide = load(guideName, false, pin, is_hdr(guideName) && opt.half);
+            if (guide.w != w || guide.h != h) throw std::runtime_error(guideName + ": layer size differs from the target image");
+            gfmt = guide.format;
+        }
+        const int out_fmt = half ? MID_FMT_RGBA16F : MID_FMT_RGBA32F;
+        const size_t out_bytes = npix * (half ? 8 : 16);
+        const mid_guided_params p{w, h, opt.guided_radius, opt.guided_eps, MID_FMT_WITH_GUIDE(fmt, gfmt)};
+        size_t work_bytes = 0;
+        MID_CHECK(mid_guided_workspace(&p, &work_bytes));
+        std::vector<unsigned char> result(out_bytes);
+        mid_timer *tm = nullptr;
+        MID_CHECK(mid_timer_create(ctx, &tm));
+        struct TimerGuard { mid_timer *t; ~TimerGuard() { mid_timer_destroy(t); } } tguard{tm};
+        auto timed = [&](double &acc, auto &&fn) {
+            MID_CHECK(mid_timer_tick(tm, nullptr));
+            fn();
+            MID_CHECK(mid_timer_tock(tm, nullptr));
+            float ms = 0;
+            MID_CHECK(mid_timer_ms(tm, &ms));
+            acc += ms;
+        };
+        std::cout << "\tperforming computations\n";
+        void *dIn = nullptr, *dGuide = nullptr, *dWork = nullptr, *dOut = nullptr;
+        MID_CHECK(mid_alloc(ctx, target.size(), &dIn));
+        if (!guideName.empty()) MID_CHECK(mid_alloc(ctx, guide.size(), &dGuide));
+        MID_CHECK(mid_alloc(ctx, work_bytes, &dWork));
+        MID_CHECK(mid_alloc(ctx, out_bytes, &dOut));
+        timed(m_transferMs, [&] {
+            MID_CHECK(mid_memcpy_h2d(ctx, dIn, target.data(), target.size(), nullptr));
+            if (dGuide) MID_CHECK(mid_memcpy_h2d(ctx, dGuide, guide.data(), guide.size(), nullptr));
+        });
+        timed(m_execMs, [&] { MID_CHECK(mid_guided_filter(ctx, &p, dIn, dGuide, dWork, dOut, out_fmt, nullptr)); });
+        std::cout << "\tgetting image back\n";
+        timed(m_transferMs, [&] { MID_CHECK(mid_memcpy_d2h(ctx, result.data(), dOut, out_bytes, nullptr)); });
+        MID_CHECK(mid_stream_sync(ctx, nullptr));
+        mid_free(ctx, dIn); if (dGuide) mid_free(ctx, dGuide); mid_free(ctx, dWork); mid_free(ctx, dOut);
+        const std::string outputFileName = "output-nonlinear-guided";
+        if (half) MID_CHECK(mid_image_save(out_path(outputFileName + ".exr").c_str(), result.data(), w, h, MID_FMT_RGBA16F));
+        else save(outputFileName, (const Pixel *)result.data(), w, h, hdr);
+        std::cout << "\tcleaning up\n";
+    }
+
     // Animation mode (BASELINE config 5; not in the reference, which filters one target per run): every
     // sibling frame of the target is denoised with temporal NLM over frames t-k..t+k.  Frames are split
     // into contiguous blocks, one per device; each device streams its block plus k halo frames on either
@@ -582,7 +661,8 @@ public:
         // the schedule of layers-temporal)
         const AnimationFilter &af = *animation_filter(opt.animation_filter);        // (main has refused unknown names)
         const int n = (int)frameNames.size(), k = !af.temporal ? 0 : opt.temporal_k < 0 ? 2 : opt.temporal_k;
-        const bool use_layers = af.layers, nlm_guides = af.family == SEQ_NLM_LAYERS || af.family == SEQ_NLM_LAYERS_TEMPORAL || af.family == SEQ_NLM_JOINT;
+        const bool guided = af.family == SEQ_GUIDED;
+        const bool use_layers = af.layers || (guided && !opt.guide_layer.empty()), nlm_guides = af.family == SEQ_NLM_LAYERS || af.family == SEQ_NLM_LAYERS_TEMPORAL || af.family == SEQ_NLM_JOINT;
         if (!af.windowed() && opt.halo_rccl)
             throw std::runtime_error("--halo rccl is not available with --animation-filter " + opt.animation_filter +
                                      ": its frames read no other frame, there is no halo to exchange");
@@ -619,6 +699,14 @@ public:
                                              " layer file(s) of this frame, it must match exactly one");
                 albedoNames.push_back(hits[0]);
                 frameLayers[i] = rest;
+            }
+            if (guided) {                                // the one render element that guides; every other one is left alone
+                std::vector<std::string> hits;
+                for (const std::string &f : frameLayers[i]) if (fs::path(f).filename().string().find(opt.guide_layer) != std::string::npos) hits.push_back(f);
+                if (hits.size() != 1)
+                    throw std::runtime_error(frameNames[i] + ": --guide-layer " + opt.guide_layer + " matches " + std::to_string(hits.size()) +
+                                             " layer file(s) of this frame, it must match exactly one");
+                frameLayers[i] = hits;
             }
             const int li = (int)frameLayers[i].size();
             if (li < 1 || li > 16)
@@ -745,6 +833,8 @@ public:
         if (!albedoNames.empty()) std::cout << "\talbedo " << albedoNames[0] << " floor " << opt.albedo_floor << "\n";
         if (opt.firefly_rank)
             std::cout << "\tfirefly radius " << opt.firefly_radius << " rank " << opt.firefly_rank << " gain " << opt.firefly_gain << " floor " << opt.firefly_floor << "\n";
+        if (guided)
+            std::cout << "\tguided guide " << (use_layers ? frameLayers[0][0] : std::string("self")) << " radius " << opt.guided_radius << " eps " << opt.guided_eps << "\n";
         if (opt.history_clip) std::cout << "\thistory-clip radius " << opt.history_clip_radius << " gamma " << opt.history_clip_gamma << "\n";
         std::vector<const void *> motion_ptrs(motionPlanes.size());
         for (size_t i = 0; i < motionPlanes.size(); ++i) motion_ptrs[i] = motionPlanes[i].data();
@@ -824,6 +914,10 @@ public:
                 MID_CHECK(mid_sequence_atrous_recursive_clip(c, &ap, &vp, jointSigma.data(), frames, nf, lp, L, motion, albedo, opt.albedo_floor,
                                                              opt.firefly_rank ? &fp : nullptr, opt.history_clip ? &cp : nullptr, opt.feedback, opt.warmup,
                                                              start, count, outs, out_fmt, 1, t)); break;
+            }
+            case SEQ_GUIDED: {             // the local linear fit to the guide plane (or to the frame itself), every frame alone
+                const mid_guided_params gp{bpp.width, bpp.height, opt.guided_radius, opt.guided_eps, bpp.format};
+                MID_CHECK(mid_sequence_guided(c, &gp, frames, nf, lp, start, count, outs, out_fmt, 1, t)); break;
             }
             case SEQ_NLM_JOINT:            // one patch weight from all layers (jointSigma: the h of each layer)
                 MID_CHECK(mid_sequence_nlm_joint(c, &np, jointSigma.data(), frames, nf, lp, L, kk, start, count, outs, out_fmt, 1, t)); break;
@@ -1151,7 +1245,11 @@ static void usage()
         "                            luminance -- estimated from a 7x7 neighbourhood weighed by the layers, it sets the width of a\n"
         "                            luminance term per pixel (wide where the image is noisy, narrow where it has converged) and is\n"
         "                            filtered along with the colour (--passes, --sigma-layers, --atrous-sigma-lum, --atrous-epsilon;\n"
-        "                            the layer rules of atrous), output output-nonlinear-atrous-variance.{png,exr}.\n"
+        "                            the layer rules of atrous), output output-nonlinear-atrous-variance.{png,exr};\n"
+        "                            and guided (not part of all): the guided filter -- inside every (2 R + 1)^2 window the image is fitted\n"
+        "                            as an affine function of the guide's colour and the averaged fit is evaluated at the pixel's own guide\n"
+        "                            texel, so the guide's edges and texture are reproduced and the cost does not depend on R\n"
+        "                            (--guided-radius, --guided-eps, --guide-layer), output output-nonlinear-guided.{png,exr}.\n"
         "                            Layer files: .png (RGBA8) -- or, for the bilateral modes only (layers and joint here, layers,\n"
         "                            layers-temporal, joint and joint-temporal under --animation-filter), .exr: normals, depth, HDR albedo as rendered, read as\n"
         "                            RGBA32F, or as RGBA16F with --half; all layers of a run must have one format; nlm-layers and\n"
@@ -1174,6 +1272,12 @@ static void usage()
         "                            the pixel's luminance (default 4; 0: no luminance term)\n"
         "  --atrous-epsilon X        atrous-variance: added to X * sqrt(variance), so that a converged pixel (variance 0) still averages\n"
         "                            texels that differ by rounding alone (default 1e-3, for luminances of order 1; > 0)\n"
+        "  --guided-radius R         guided (--modes guided, --animation-filter guided): window radius, 1..16 (default 8)\n"
+        "  --guided-eps X            guided: the regulariser, finite and > 0, in squared units of the guide (default 0.01): windows whose\n"
+        "                            guide varies by much less than sqrt(X) are averaged, windows that vary by more carry the guide's edge\n"
+        "  --guide-layer SUBSTR      guided: the render element whose file name contains SUBSTR is the guide (.png read as RGBA8, .exr as\n"
+        "                            RGBA32F, or RGBA16F with --half); no match or several are refused.  Without it the image guides\n"
+        "                            itself and no layers are loaded.  The run prints `guided guide <file|self> radius <r> eps <x>`\n"
         "  --search LO,HI --patch LO,HI   half-open NLM ranges (default -7,7 and -3,3; 21x21/7x7 is -10,11 and -3,4)\n"
         "  --alpha X                 atrous-recursive: floor of the colour blend factor, (0, 1] (default 0.2)\n"
         "  --alpha-moments X         atrous-recursive: floor of the moments' blend factor, (0, 1] (default 0.2)\n"
@@ -1251,7 +1355,11 @@ static void usage()
         "                            --atrous-epsilon as atrous-variance;\n"
         "                            it ignores --temporal-k; not with --halo rccl), outputs output-animation-nonlinear-atrous-recursive-*.\n"
         "                            With --gpus N every frame block starts its history --warmup frames before its block: a sharded\n"
-        "                            run equals the unsharded one bit for bit only when the warm-up reaches frame 0\n"
+        "                            run equals the unsharded one bit for bit only when the warm-up reaches frame 0;\n"
+        "                            or guided: the guided filter of every frame alone, guided by the one render element of each frame\n"
+        "                            that --guide-layer names, or by the frame itself (--guided-radius, --guided-eps; it ignores\n"
+        "                            --temporal-k, frame blocks have no halo, not with --halo rccl), outputs\n"
+        "                            output-animation-nonlinear-guided-*\n"
         "  --gpus N                  animation mode: split the sequence into N frame blocks, one per device\n"
         "  --halo host|rccl          animation mode with --gpus N: 'host' (default) streams every block plus its K halo frames from host\n"
         "                            memory through the overlapped pipeline; 'rccl' keeps each block resident in its GPU's HBM and\n"
@@ -1311,6 +1419,17 @@ int main(int argc, char **argv)
             if (!(std::isfinite(opt.relmse_eps) && opt.relmse_eps > 0.f)) { std::cerr << "--relmse-eps " << opt.relmse_eps << " must be finite and > 0\n"; return EXIT_FAILURE; }
         }
         else if (a == "--no-ssim") { opt.compare_ssim = false; if (!opt.compare_other) opt.compare_other = "--no-ssim"; }
+        else if (a == "--guided-radius") {
+            opt.guided_radius = atoi(next());
+            if (!opt.guided_other) opt.guided_other = "--guided-radius";
+            if (opt.guided_radius < 1 || opt.guided_radius > 16) { std::cerr << "--guided-radius " << opt.guided_radius << " is outside 1..16\n"; return EXIT_FAILURE; }
+        }
+        else if (a == "--guided-eps") {
+            opt.guided_eps = (float)atof(next());
+            if (!opt.guided_other) opt.guided_other = "--guided-eps";
+            if (!(std::isfinite(opt.guided_eps) && opt.guided_eps > 0.f)) { std::cerr << "--guided-eps " << opt.guided_eps << " must be finite and > 0\n"; return EXIT_FAILURE; }
+        }
+        else if (a == "--guide-layer") { opt.guide_layer = next(); if (!opt.guided_other) opt.guided_other = "--guide-layer"; }
         else if (a == "--gpu-only") opt.run_cpu = false;
         else if (a == "--cpu-only") opt.run_gpu = false;
         else if (a == "--radius") opt.radius = atoi(next());
@@ -1433,6 +1552,10 @@ int main(int argc, char **argv)
         return EXIT_FAILURE;
     }
     if (opt.history_clip_radius_given && !opt.history_clip) { std::cerr << "--history-clip-radius needs --history-clip\n"; return EXIT_FAILURE; }
+    if (opt.guided_other && !(opt.animation ? opt.animation_filter == "guided" : listed("guided"))) {
+        std::cerr << opt.guided_other << " applies to --modes guided and --animation --animation-filter guided only\n";
+        return EXIT_FAILURE;
+    }
     if (opt.compare_other && !opt.compare) { std::cerr << opt.compare_other << " applies to --compare only\n"; return EXIT_FAILURE; }
     if (opt.compare) {
         const char *with = modes_given ? "--modes" : filter_given ? "--animation-filter" : gpus_given ? "--gpus" : nullptr;
@@ -1472,6 +1595,7 @@ int main(int argc, char **argv)
             if (listed("joint")) { std::cout << "######\nRunning on GPU (joint bialteral)\n######\n"; app.RunOnGPU(false, true, false, false, true, true); print_time(); }
             if (listed("nlm-joint")) { std::cout << "######\nRunning on GPU (joint nonlocal)\n######\n"; app.RunOnGPU(true, true, false, false, true, true); print_time(); }
             if (listed("atrous")) { std::cout << "######\nRunning on GPU (a-trous + layers)\n######\n"; app.RunOnGPU(false, true, false, false, true, true, 1); print_time(); }
+            if (listed("guided")) { std::cout << "######\nRunning on GPU (guided filter)\n######\n"; app.RunGuided(); print_time(); }
             if (listed("atrous-variance")) { std::cout << "######\nRunning on GPU (a-trous + layers, variance-guided)\n######\n"; app.RunOnGPU(false, true, false, false, true, true, 2); print_time(); }
         }
         if (opt.run_cpu) {

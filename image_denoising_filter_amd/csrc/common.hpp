@@ -301,6 +301,12 @@ int color_bounds_check(const mid_color_bounds_params *p, const char *who);
 int image_metrics_out(mid_ctx *ctx, const mid_image_metrics_params *p, const void *a, const void *b, void *work, float *map, hipStream_t s);
 int image_metrics_check(const mid_image_metrics_params *p, const char *who);
 
+// mid_guided_filter without its pointer checks (the caller has made them), two launches on `s`: guided.hip.  guide == nullptr or
+// guide == in: the frame guides itself.  guided_check: the size, radius, eps and the format word; guided_work_bytes: what `work` holds.
+int guided_out(mid_ctx *ctx, const mid_guided_params *p, const void *in, const void *guide, void *work, void *out, int out_fmt, hipStream_t s);
+int guided_check(const mid_guided_params *p, const char *who);
+size_t guided_work_bytes(const mid_guided_params *p);
+
 // ROCTx ranges (csrc/markers.cpp): no-ops unless the process already holds a ROCTx (rocprofv3 --marker-trace preloads one).
 bool markers_active();
 void range_push(const char *name);

@@ -615,6 +615,32 @@ extern "C" int mid_sequence_atrous_joint(mid_ctx *ctx, const mid_atrous_params *
     return run_pipeline(ctx, st, launch, host_frames, n_frames, 0, first, count, host_out, out_format, overlap, timings_ms);
 }
 
+// The guided filter of every frame (section a4o): mid_sequence_atrous_joint's schedule at k = 0 with guided_out as the compute
+// stage.  A frame's guide plane travels as the stage's single layer (none when the frames guide themselves); the workspace comes
+// from the context's cache as the a-trous levels do, one per kernel stream.
+extern "C" int mid_sequence_guided(mid_ctx *ctx, const mid_guided_params *p, const void *const *host_frames, int n_frames,
+                                   const void *const *host_guides, int first, int count, void *const *host_out, int out_format,
+                                   int overlap, float *timings_ms)
+{
+    Bind b(ctx, nullptr);
+    if (b.rc) return b.rc;
+    const char *who = "sequence_guided";
+    if (int rc = refuse_if_recording(ctx->compute, "mid_sequence_guided (four streams, host-side waits)")) return rc;
+    if (int rc = guided_check(p, who)) return rc;
+    const int n_layers = host_guides ? 1 : 0;
+    if (int rc = check_sequence({who, "n_frames", true, true}, host_frames, n_frames, host_guides, n_layers, 0, first, count, host_out, out_format)) return rc;
+    const size_t npix = (size_t)p->width * p->height;
+    Stage st{who, p->width, p->height, fmt_frames(p->format), npix * fmt_bytes(fmt_guide(p->format)), host_guides, n_layers, true, "guided %d"};
+    st.level_bytes = guided_work_bytes(p); st.n_levels = 1;
+    auto launch = [&](const void *const *tbl, int, const uint32_t *const *lt, int, int t0, int bn, void *const *out, int out_fmt, hipStream_t s) {
+        void *work = ctx->pipe.atrous.p[s == ctx->compute2 ? 1 : 0];
+        for (int i = 0; i < bn; ++i)              // (k = 0: output t0 + i reads slot t0 + i and its guide only)
+            if (int rc = guided_out(ctx, p, tbl[t0 + i], n_layers ? (const void *)lt[t0 + i] : nullptr, work, out[i], out_fmt, s)) return rc;
+        return (int)MID_OK;
+    };
+    return run_pipeline(ctx, st, launch, host_frames, n_frames, 0, first, count, host_out, out_format, overlap, timings_ms);
+}
+
 // The a-trous filter over neighbouring frames: mid_sequence_atrous_joint with a window -- mid_sequence_bilateral_joint's schedule
 // and layer ring at k, the launch callable of sequence_bilateral_temporal's window tables, the levels of the call above.
 extern "C" int mid_sequence_atrous_joint_temporal(mid_ctx *ctx, const mid_atrous_params *p, const float *layer_sigma,

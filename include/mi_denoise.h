@@ -1112,6 +1112,73 @@ int mid_image_metrics(mid_ctx *ctx, const mid_image_metrics_params *p, const voi
  * MID_ERR_INVALID for a NULL pointer, or peak not finite or <= 0. */
 int mid_image_metrics_derive(const double *sums_host, const mid_image_metrics_params *p, mid_image_metrics_result *out);
 
+/* ---- a4o: the guided filter --------------------------------------------------------------------
+ * Every filter above is a weighted average: the guide layers decide the weights and nothing else.  The guided filter (He, Sun,
+ * Tang 2010, with a colour guide; Bauszat et al. 2011 use it on path-traced frames) fits, inside every window, the frame as an
+ * AFFINE function of the guide's colour, p ~ a^T I + b, and evaluates the averaged fit at the pixel's own guide texel: the output
+ * is locally a linear transform of the guide, whose edges and texture are reproduced, not merely respected.  Everything is made of
+ * box means, so the cost does not depend on the radius.
+ * p(q), I(q): the RGB of `in` and of `guide`, widened as a4i widens a frame; the guide's alpha is ignored.  guide == NULL, or guide
+ * == in as pointers: I = p and the guide format is the frame's (with guide == in the format word must say so).
+ * A texel q is VALID iff all six values are finite.  w(k): the window |i|, |j| <= radius around k, cut at the image.  n_k: the
+ * number of VALID texels of w(k).
+ * Stage 1, per window centre k inside the image with n_k > 0, every mean over the VALID q of w(k), divided by n_k:
+ *   mu = mean I (3);  nu = mean p (3);  Sigma = mean(I I^T) - mu mu^T (3 x 3, symmetric);
+ *   C = mean(I p^T) - mu nu^T (3 x 3: row = guide channel j, column = output channel c);
+ *   a_k = (Sigma + eps U)^-1 C (U the identity);   b_k = nu - a_k^T mu.             A window with n_k = 0 has no model.
+ * Stage 2, per pixel i: abar, bbar = the means of a_k, b_k over the k of w(i) that have a model, m_i their number.
+ *   i VALID and m_i > 0:   out_c = fmaf(abar_0c, I_i0, fmaf(abar_1c, I_i1, fmaf(abar_2c, I_i2, bbar_c)))     -- fp32, this order
+ *   otherwise:             out.rgb = p_i unchanged: a NaN stays a NaN (the firefly clamp, a4l, is the repair)
+ *   out.a = in.a in every case.  `out` is stored in out_format by the rule of mid_atrous_joint's outputs (float4, or mid_pack_u8 /
+ *   mid_pack_f16 of it).
+ * Arithmetic (csrc/guided.hip).  The window sums are taken in binary64 -- the product of two fp32 values is exact
+ * there -- of I - s_I and p - s_p, s the texel of the workgroup's first output pixel (a channel of it that is not finite: 0):
+ * covariances do not change under a shift, and a flat HDR region or a depth-like guide no longer cancels in mean(I I^T) - mu mu^T.
+ * The solve is the adjugate of the symmetric positive definite Sigma + eps U in binary64; a, b are rounded once to fp32 into `work`
+ * (with b back in the unshifted units); the stage-2 sums are binary64 and abar, bbar are rounded once to fp32; then the chain above.
+ * Error: with T_ic = sum_j mean_k|a_k,jc| |I_ij| + mean_k|b_k,c|, the five roundings named and the three fmas are at most 7 units
+ * of 2^-24 T, and the bound is |out - exact| <= 8 * 2^-24 * T_ic, PROVIDED the binary64 sums stay below the eighth unit.  With D
+ * the largest deviation of a guide channel from s_I inside the workgroup's 256 x (32 + 2 radius) footprint: a column's running sum
+ * takes at most 96 roundings of 2^-53 * 34 D^2 (2^-41.3 D^2), the 33 columns of a window bring 2^-36.3 D^2 of that, and the two
+ * prefix slots add 10 roundings each of 2^-53 * 256 * 33 D^2 (2^-35.6 D^2 together): 2^-34.9 D^2 on a window sum, 2^-34.9 D^2 / n_k
+ * on a mean, and through (Sigma + eps U)^-1 at most 2^-34.9 D^2 / (n_k eps) relative on a.  That stays below 2^-24 when
+ *     D^2 / eps <= 2^10 * n_min,      n_min the smallest non-zero n_k of the frame ((radius + 1)^2 where every texel is VALID).
+ * (A unit-range guide at radius 2 and eps = 1e-3 has D^2 / eps <= 1000 against 9216; a depth guide of +-30 units around s at
+ * eps = 1 has 900.)  The bound is a worst case over every rounding going one way.
+ * work: caller-provided device scratch of mid_guided_workspace bytes = 52 bytes per pixel (thirteen fp32 planes: a_jc at plane
+ * 3 j + c, b_c at 9 + c, the model flag at 12) and no constant, 16-byte aligned; the stage-1 models cross it as fp32; its contents
+ * after the call are unspecified.  Nothing is kept in the context: two calls on two streams with two workspaces cannot meet.
+ * Class: two launches; a workgroup of four waves holds 256 columns, lanes along x, and walks a segment of 32 output rows; the
+ * vertical sums of a column stay in its lane's registers (row entering added, row leaving subtracted) and RESTART with every
+ * segment; per output row the column sums cross LDS once as prefix sums along x and a window is the difference of two slots
+ * (csrc/guided_box.hpp).  Index arithmetic in size_t; min(tiles, 8192) workgroups; no atomics, so the bits depend on the inputs
+ * and the parameters alone.
+ * MID_ERR_INVALID before anything is queued, `out` and `work` untouched: a NULL p, in, work, out or bytes; radius outside 1..16;
+ * eps not finite or <= 0; an unknown frame, guide or output format, or bits above 15; in, guide or out not aligned to its texel
+ * size, work not to 16 bytes; width or height < 1, or 2^30 pixels and more; out or work overlapping in, guide or each other in any
+ * way (the pass is a stencil: exactly in place is refused too); guide == in with a guide format that is not the frame's. */
+typedef struct mid_guided_params {
+    int32_t width, height;
+    int32_t radius;   /* 1..16: (2 radius + 1)^2 windows, clipped at the image */
+    float   eps;      /* finite, > 0: the regulariser, in squared guide units */
+    int32_t format;   /* MID_FMT_* of `in`; MID_FMT_WITH_GUIDE(fmt, guide_fmt) names the guide's format (guide field 0: RGBA8) */
+} mid_guided_params;
+int mid_guided_workspace(const mid_guided_params *p, size_t *bytes);
+int mid_guided_filter(mid_ctx *ctx, const mid_guided_params *p, const void *in, const void *guide /* NULL: `in` guides itself */,
+                      void *work, void *out, int out_format, void *stream);
+/* The frame pipeline (section 8d) with the guided filter as its compute stage, at k = 0 as mid_sequence_atrous_joint: outputs
+ * [first, first + count) of the sequence, output t with the bits of mid_guided_filter on frame t (and host_guides[t]) in
+ * out_format.  host_frames: n_frames HOST pointers in the frame format of p->format; host_guides: n_frames HOST pointers, one
+ * plane per frame in the guide format of p->format, uploaded with its frame -- or NULL: every frame guides itself.  The workspace
+ * comes from the context's cache, one per kernel stream (mid_ctx_release_cached frees it).  Outputs are stored by the kernel or
+ * downloaded by the rule of mid_sequence_bilateral; overlap and timings_ms as for mid_sequence_nlm.  Launch range "guided t".
+ * MID_ERR_INVALID, before anything is queued, for: what mid_guided_filter refuses in p; a NULL frame, guide or output of the
+ * range; bad first or count; an unknown out_format; an output that is also an input frame or guide of the range (or appears
+ * twice); a call while the context's stream records. */
+int mid_sequence_guided(mid_ctx *ctx, const mid_guided_params *p, const void *const *host_frames, int n_frames,
+                        const void *const *host_guides /* one plane per frame, or NULL */, int first, int count,
+                        void *const *host_out, int out_format, int overlap, float *timings_ms);
+
 /* ---- a5: normalize ----------------------------------------------------------------------
  * One dispatch of shaders/normalize.comp (RecordCommandsOfExecuteAndTransfer(normKernel=true)):
  * out = weightColor / normWeight, or (1,0,1,1) where normWeight == 0; bindings {0: out; 1: W}. */

@@ -43,6 +43,9 @@ int mid::firefly_clamp_out(mid_ctx *, const mid_firefly_params *, const void *, 
 int mid::firefly_check(const mid_firefly_params *, const char *) { return MID_ERR_UNSUPPORTED; }   // (firefly.hip)
 int mid::color_bounds_out(mid_ctx *, const mid_color_bounds_params *, const void *, mid_pixel *, mid_pixel *, hipStream_t) { return MID_ERR_UNSUPPORTED; }   // (color_bounds.hip)
 int mid::color_bounds_check(const mid_color_bounds_params *, const char *) { return MID_ERR_UNSUPPORTED; }   // (color_bounds.hip)
+int mid::guided_out(mid_ctx *, const mid_guided_params *, const void *, const void *, void *, void *, int, hipStream_t) { return MID_ERR_UNSUPPORTED; }   // (guided.hip)
+int mid::guided_check(const mid_guided_params *, const char *) { return MID_ERR_UNSUPPORTED; }   // (guided.hip)
+size_t mid::guided_work_bytes(const mid_guided_params *) { return 0; }   // (guided.hip)
 int mid::nlm_check_params(const mid_nlm_params *) { return MID_ERR_UNSUPPORTED; }   // (nlm.hip)
 int mid::bilateral_check_params(const mid_bilateral_params *, const char *, bool) { return MID_ERR_UNSUPPORTED; }   // (bilateral.hip)
 
