@@ -3,7 +3,7 @@ HIPCC   ?= /opt/rocm/bin/hipcc
 ARCH    ?= gfx950
 CSRC    := image_denoising_filter_amd/csrc
 LIB     := image_denoising_filter_amd/libmi_denoise.so
-SRCS    := $(CSRC)/capi.cpp $(CSRC)/hostcopy.cpp $(CSRC)/markers.cpp $(CSRC)/recording.cpp $(CSRC)/pointwise.hip $(CSRC)/bilateral.hip $(CSRC)/bilateral_temporal.hip $(CSRC)/bilateral_joint.hip $(CSRC)/atrous.hip $(CSRC)/atrous_temporal.hip $(CSRC)/atrous_variance.hip $(CSRC)/temporal_accumulate.hip $(CSRC)/albedo.hip $(CSRC)/firefly.hip $(CSRC)/color_bounds.hip $(CSRC)/image_metrics.hip $(CSRC)/guided.hip $(CSRC)/nlm.hip $(CSRC)/nlm_small.hip $(CSRC)/nlm_edge.hip $(CSRC)/nlm_rt.hip $(CSRC)/nlm_rt4.hip $(CSRC)/nlm_layers.hip $(CSRC)/nlm_layers_temporal.hip $(CSRC)/nlm_joint.hip $(CSRC)/pipeline.cpp $(CSRC)/sharded.cpp \
+SRCS    := $(CSRC)/capi.cpp $(CSRC)/hostcopy.cpp $(CSRC)/markers.cpp $(CSRC)/recording.cpp $(CSRC)/pointwise.hip $(CSRC)/bilateral.hip $(CSRC)/bilateral_temporal.hip $(CSRC)/bilateral_joint.hip $(CSRC)/atrous.hip $(CSRC)/atrous_temporal.hip $(CSRC)/atrous_variance.hip $(CSRC)/temporal_accumulate.hip $(CSRC)/albedo.hip $(CSRC)/firefly.hip $(CSRC)/color_bounds.hip $(CSRC)/image_metrics.hip $(CSRC)/guided.hip $(CSRC)/median.hip $(CSRC)/nlm.hip $(CSRC)/nlm_small.hip $(CSRC)/nlm_edge.hip $(CSRC)/nlm_rt.hip $(CSRC)/nlm_rt4.hip $(CSRC)/nlm_layers.hip $(CSRC)/nlm_layers_temporal.hip $(CSRC)/nlm_joint.hip $(CSRC)/pipeline.cpp $(CSRC)/sharded.cpp \
            $(CSRC)/codec/png.cpp $(CSRC)/codec/exr.cpp $(CSRC)/codec/piz.cpp $(CSRC)/codec/image_capi.cpp
 OBJS    := $(patsubst $(CSRC)/%,build/%.o,$(SRCS))
 HIPFLAGS := -x hip --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -fno-slp-vectorize -Wall -Wno-unused-function -Iinclude
@@ -28,7 +28,7 @@ EXTRA_nlm_small.hip := -mllvm -amdgpu-sched-strategy=iterative-ilp
 EXTRA_nlm_rt4.hip := $(EXTRA_nlm.hip)
 EXTRA_nlm_edge.hip := $(EXTRA_nlm.hip)
 
-build/%.o: $(CSRC)/% $(CSRC)/common.hpp $(CSRC)/bilateral_shapes.hpp $(CSRC)/nlm_strip.hpp $(CSRC)/nlm_guide.hpp $(CSRC)/nlm_vbox_plan.hpp $(CSRC)/reproject_taps.hpp $(CSRC)/firefly_tile.hpp $(CSRC)/guided_box.hpp $(CSRC)/codec/image_io.hpp include/mi_denoise.h
+build/%.o: $(CSRC)/% $(CSRC)/common.hpp $(CSRC)/bilateral_shapes.hpp $(CSRC)/nlm_strip.hpp $(CSRC)/nlm_guide.hpp $(CSRC)/nlm_vbox_plan.hpp $(CSRC)/reproject_taps.hpp $(CSRC)/firefly_tile.hpp $(CSRC)/guided_box.hpp $(CSRC)/median_tile.hpp $(CSRC)/codec/image_io.hpp include/mi_denoise.h
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(HIPFLAGS) $(EXTRA_$(notdir $<)) -c $< -o $@
 

@@ -107,6 +107,11 @@ class GuidedParams(ctypes.Structure):
                 ("format", ctypes.c_int32)]
 
 
+class MedianParams(ctypes.Structure):
+    """mid_median_params (section a4p)."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("radius", ctypes.c_int32), ("format", ctypes.c_int32)]
+
+
 class NormalizeParams(ctypes.Structure):
     _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32)]
 
@@ -211,6 +216,11 @@ _SIGNATURES = {
     "mid_guided_filter": (ctypes.c_int, [_P, ctypes.POINTER(GuidedParams), _P, _P, _P, _P, ctypes.c_int, _P]),
     "mid_sequence_guided": (ctypes.c_int, [_P, ctypes.POINTER(GuidedParams), c_void_pp, ctypes.c_int, c_void_pp, ctypes.c_int, ctypes.c_int,
                                            c_void_pp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
+    "mid_median_filter": (ctypes.c_int, [_P, ctypes.POINTER(MedianParams), ctypes.POINTER(ctypes.c_float), _P, c_void_pp, ctypes.c_int, _P,
+                                         ctypes.c_int, _P]),
+    "mid_sequence_median": (ctypes.c_int, [_P, ctypes.POINTER(MedianParams), ctypes.POINTER(ctypes.c_float), c_void_pp, ctypes.c_int, c_void_pp,
+                                           ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_pp, ctypes.c_int, ctypes.c_int,
+                                           ctypes.POINTER(ctypes.c_float)]),
     "mid_normalize": (ctypes.c_int, [_P, ctypes.POINTER(NormalizeParams), _P, _P, _P]),
     "mid_unpack_u8": (ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_int, _P, _P]),
     "mid_pack_u8": (ctypes.c_int, [_P, _P, ctypes.c_size_t, _P, _P]),

@@ -15,7 +15,7 @@ import weakref
 
 import numpy as np
 
-from ._lib import AlbedoParams, AtrousMomentsParams, AtrousParams, AtrousVarianceParams, BilateralParams, ColorBoundsParams, FireflyParams, GuidedParams, Image, ImageMetricsParams, ImageMetricsResult, METRICS_N, NlmParams, NormalizeParams, TemporalAccumParams, c_void_pp, lib
+from ._lib import AlbedoParams, AtrousMomentsParams, AtrousParams, AtrousVarianceParams, BilateralParams, ColorBoundsParams, FireflyParams, GuidedParams, Image, ImageMetricsParams, ImageMetricsResult, METRICS_N, MedianParams, NlmParams, NormalizeParams, TemporalAccumParams, c_void_pp, lib
 
 FMT_RGBA32F, FMT_RGBA8, FMT_RGBA16F = 0, 1, 2
 
@@ -710,6 +710,55 @@ class Context:
                                      _OUT_FMT[out_dtype], None), "mid_guided_filter")
         return self.download(d_out, (h, w, 4), out_dtype)
 
+    def median_filter(self, frame, layers=None, sigmas=None, radius=1, out_dtype=None):
+        """The median of the (2 radius + 1)^2 window, per channel of r, g, b (mid_median_filter, section a4p); alpha unchanged.
+        layers=None: the plain median.  Otherwise the lower weighted median under one weight per tap from all guide layers, the
+        product of exp(-0.5 |G_l(p) - G_l(q)|^2 / sigma_l^2): 1..16 (h, w, 4) layers, uint8, float16 or float32 and all of one dtype,
+        with one sigma per layer.  Texels that are not finite take no part, so a NaN pixel with valid neighbours is repaired.
+        Returns (h, w, 4) in out_dtype (None = float32; uint8 and float16 with the rounding of pack_u8 / pack_f16)."""
+        who = "median_filter"
+        (frame,) = _same_frames([frame], who)
+        h, w = frame.shape[:2]
+        radius = _median_args(radius, layers, sigmas, who)
+        n_layers, flat = (0, []) if layers is None else _flat_layers([layers], 1, h, w, who, _GUIDE_DTYPES)
+        out_dtype = _guided_out_dtype(out_dtype, who)
+        p = MedianParams(w, h, radius, _guide_fmt(_fmt_of(frame), flat, who))
+        sg = None if layers is None else _layer_sigmas(sigmas, n_layers, who)
+        d_in = self.upload(frame)
+        d_l = [self.upload(l) for l in flat]
+        d_out = self.alloc(w * h * 4 * out_dtype.itemsize)
+        _check(lib.mid_median_filter(self.handle, ctypes.byref(p), sg, d_in.ptr,
+                                     None if layers is None else (ctypes.c_void_p * max(len(d_l), 1))(*[d.ptr for d in d_l]), n_layers, d_out.ptr,
+                                     _OUT_FMT[out_dtype], None), "mid_median_filter")
+        return self.download(d_out, (h, w, 4), out_dtype)
+
+    def sequence_median_pinned(self, hin, hout, w, h, fmt, hlayers=None, n_layers=0, sigmas=None, radius=1, first=0, count=None, overlap=True,
+                               out_dtype=None):
+        """mid_sequence_median on host pointers the caller already holds: nothing but the C call.  hin: all n frames of the sequence;
+        hlayers: None (the plain median) or n * n_layers host pointers, frame-major (RGBA8, or what fmt_with_guide names in `fmt`);
+        hout: `count` output buffers; sigmas: n_layers sigmas.  Returns (wall_ms of the whole call, kernel_ms, copy_ms)."""
+        count = len(hin) - first if count is None else count
+        return self._sequence_call("mid_sequence_median", "mid_sequence_median", MedianParams(w, h, radius, fmt), hin, hout, count,
+                                   f"{count} outputs", overlap, layers=(hlayers, n_layers), plain=True, window=(first, count),
+                                   out_dtype=(out_dtype,), sigmas=(None if hlayers is None else sigmas,))
+
+    def sequence_median(self, frames, layers=None, sigmas=None, radius=1, first=0, count=None, overlap=True, pinned=True, pinned_out=True,
+                        out_dtype=None):
+        """Outputs [first, first+count) of an animation through the overlapped pipeline with the median as its compute stage
+        (mid_sequence_median): output t is ctx.median_filter(frames[t], layers[t], sigmas, radius) in out_dtype.  layers: None, or one
+        list of guide layers per frame.  pinned, pinned_out, out_dtype as for sequence_bilateral.
+        Returns (outputs, (wall_ms, kernel_ms, copy_ms))."""
+        who = "sequence_median"
+        radius = _median_args(radius, layers, sigmas, who)
+        out_dtype = _guided_out_dtype(out_dtype, who)
+        frames = _same_frames(frames, who)
+        if layers is not None:
+            n_layers, _ = _flat_layers(layers, len(frames), frames[0].shape[0], frames[0].shape[1], who, _GUIDE_DTYPES)
+            _layer_sigmas(sigmas, n_layers, who)
+        return self._sequence_host(who, lambda hin, hout, w, h, fmt, hlayers, n_layers, count: self.sequence_median_pinned(
+            hin, hout, w, h, fmt, hlayers, n_layers, sigmas, radius, first, count, overlap, out_dtype),
+            frames, layers, _GUIDE_DTYPES, first, count, pinned, pinned_out, out_dtype, plain=True)
+
     def normalize(self, W):
         """normalize.comp."""
         W = np.ascontiguousarray(W, dtype=np.float32)
@@ -1248,6 +1297,18 @@ def _guided_args(radius, eps, who):
     if not (0 < float(eps) <= float(np.finfo(np.float32).max) and float(np.float32(eps)) > 0):   # (the C side reads a float)
         raise ValueError(f"{who}: eps must be finite and > 0, got {float(eps)}")
     return int(radius), float(np.float32(eps))
+
+
+def _median_args(radius, layers, sigmas, who):
+    """The keywords of median_filter, checked before any GPU work: the radius of mid_median_params; sigmas come with layers, and
+    layers with sigmas."""
+    if not isinstance(radius, (int, np.integer)) or isinstance(radius, bool) or not 1 <= radius <= 3:
+        raise ValueError(f"{who}: the radius must be an integer in 1..3, got {radius!r}")
+    if layers is None and sigmas is not None:
+        raise ValueError(f"{who}: sigmas without layers (the plain median takes neither)")
+    if layers is not None and sigmas is None:
+        raise ValueError(f"{who}: layers without sigmas (one sigma per layer)")
+    return int(radius)
 
 
 def _guided_out_dtype(out_dtype, who):

@@ -91,6 +91,9 @@ struct Options {
     float guided_eps = 1e-2f;       // and its regulariser, in squared guide units
     std::string guide_layer;        // substring of the render element that is the guide; empty: every frame guides itself
     const char *guided_other = nullptr;        // the first of --guided-radius / --guided-eps / --guide-layer given
+    int median_radius = 1;          // the median (--modes median, --animation-filter median): mid_median_params.radius, 1..3
+    bool median_plain = false;      // --median-plain: no layers are loaded, the plain median
+    const char *median_other = nullptr;        // the first of --median-radius / --median-plain given
     bool compare = false;           // --compare TEST REFERENCE: the sub-mode that measures and filters nothing (mid_image_metrics)
     std::string compare_test, compare_ref;
     float peak = 1.f, relmse_eps = 1e-2f;      // --peak, --relmse-eps (mid_image_metrics_params)
@@ -104,7 +107,7 @@ struct Options {
     } while (0)
 
 // --animation-filter, parsed once: the mid_sequence_* family a value runs, what that family reads, and the words of the value.
-enum SeqFamily { SEQ_NLM, SEQ_BILATERAL, SEQ_NLM_LAYERS, SEQ_NLM_LAYERS_TEMPORAL, SEQ_BILATERAL_TEMPORAL, SEQ_BILATERAL_JOINT, SEQ_NLM_JOINT, SEQ_ATROUS, SEQ_ATROUS_TEMPORAL, SEQ_ATROUS_VARIANCE, SEQ_ATROUS_RECURSIVE, SEQ_GUIDED };
+enum SeqFamily { SEQ_NLM, SEQ_BILATERAL, SEQ_NLM_LAYERS, SEQ_NLM_LAYERS_TEMPORAL, SEQ_BILATERAL_TEMPORAL, SEQ_BILATERAL_JOINT, SEQ_NLM_JOINT, SEQ_ATROUS, SEQ_ATROUS_TEMPORAL, SEQ_ATROUS_VARIANCE, SEQ_ATROUS_RECURSIVE, SEQ_GUIDED, SEQ_MEDIAN };
 struct AnimationFilter {
     const char *name;
     SeqFamily family;
@@ -115,7 +118,7 @@ struct AnimationFilter {
     const char *words;      // of the summary line, before r= / the layers / k=
     const char *banner;     // "Running on GPU (animation, <banner>)"
     bool bilateral() const { return family == SEQ_BILATERAL || family == SEQ_BILATERAL_TEMPORAL || family == SEQ_BILATERAL_JOINT; }
-    bool windowed() const { return family != SEQ_BILATERAL && family != SEQ_NLM_LAYERS && family != SEQ_ATROUS && family != SEQ_GUIDED; }     // blocks with k halo frames on either side
+    bool windowed() const { return family != SEQ_BILATERAL && family != SEQ_NLM_LAYERS && family != SEQ_ATROUS && family != SEQ_GUIDED && family != SEQ_MEDIAN; }     // blocks with k halo frames on either side
 };
 static const AnimationFilter kAnimationFilters[] = {
     {"nlm", SEQ_NLM, false, true, false, "", "", "temporal nonlocal"},
@@ -136,6 +139,8 @@ static const AnimationFilter kAnimationFilters[] = {
     {"atrous-recursive", SEQ_ATROUS_RECURSIVE, true, false, false, "nonlinear-atrous-recursive-", "recursive a-trous", "a-trous + layers, recursive accumulation"},
     // (layers: the one render element --guide-layer names, if it is given; RunAnimation decides)
     {"guided", SEQ_GUIDED, false, false, false, "nonlinear-guided-", "guided filter", "guided filter"},
+    // (layers: unless --median-plain; RunAnimation decides)
+    {"median", SEQ_MEDIAN, true, false, false, "nonlinear-median-", "median", "median"},
 };
 static const AnimationFilter *animation_filter(const std::string &name)
 {
@@ -637,6 +642,74 @@ public:
         std::cout << "\tcleaning up\n";
     }
 
+    // --modes median: the median of the target (mid_median_filter, section a4p) -- weighted by the frame's RenderElements layers, loaded
+    // and given their sigmas as for --modes atrous (--sigma-layers, else --sigma-c; .png or .exr, one format per run), or with
+    // --median-plain the plain median, for which no layer is loaded.  Output output-nonlinear-median.{png,exr}; with --half on an .exr
+    // target the kernel stores RGBA16F and the file is a HALF EXR.
+    void RunMedian()
+    {
+        TraceRange mode_range("RunMedian");
+        m_execMs = m_transferMs = 0;
+        std::cout << "\tinit hip for device " << opt.device << "\n";
+        mid_ctx *ctx = nullptr;
+        MID_CHECK(mid_ctx_create(opt.device, &ctx));
+        struct CtxGuard { mid_ctx *c; ~CtxGuard() { mid_ctx_destroy(c); } } guard{ctx};
+        std::vector<std::string> none, layerNames;
+        if (!opt.median_plain) {
+            discover(none, layerNames, false, true);
+            if (layerNames.empty() || layerNames.size() > 16)
+                throw std::runtime_error(opt.image + ": " + std::to_string(layerNames.size()) + " layer file(s) found, --modes median needs 1..16 (or --median-plain)");
+        }
+        const int L = (int)layerNames.size(), lfmt = layer_format(layerNames);
+        std::cout << "\tmedian radius " << opt.median_radius << " layers " << L << "\n";
+        const std::vector<float> sigma = layer_sigmas(layerNames);
+        std::cout << "\tloading image data\n";
+        const bool hdr = is_hdr(opt.image), half = hdr && opt.half;
+        mid_ctx *pin = opt.pageable_host ? nullptr : ctx;
+        HostImage target = load(opt.image, false, pin, half);
+        const int w = target.w, h = target.h, fmt = target.format;
+        const size_t npix = (size_t)w * h;
+        std::vector<HostImage> layerImgs(L);
+        for_each_file(0, L, [&](int i) {
+            layerImgs[i] = load(layerNames[i], false, pin, lfmt == MID_FMT_RGBA16F);
+            if (layerImgs[i].w != w || layerImgs[i].h != h) throw std::runtime_error(layerNames[i] + ": layer size differs from the target image");
+            if (layerImgs[i].format != lfmt) throw std::runtime_error(layerNames[i] + ": the decoded layer is not in the run's guide format");
+        });
+        // an LDR target comes back as RGBA8 (the kernel packs as mid_pack_u8 does), an .exr as RGBA32F, or RGBA16F with --half
+        const int out_fmt = hdr ? (half ? MID_FMT_RGBA16F : MID_FMT_RGBA32F) : MID_FMT_RGBA8;
+        const size_t out_bytes = npix * (out_fmt == MID_FMT_RGBA32F ? 16 : out_fmt == MID_FMT_RGBA16F ? 8 : 4);
+        const mid_median_params p{w, h, opt.median_radius, L && lfmt != MID_FMT_RGBA8 ? MID_FMT_WITH_GUIDE(fmt, lfmt) : fmt};
+        std::vector<unsigned char> result(out_bytes);
+        mid_timer *tm = nullptr;
+        MID_CHECK(mid_timer_create(ctx, &tm));
+        struct TimerGuard { mid_timer *t; ~TimerGuard() { mid_timer_destroy(t); } } tguard{tm};
+        auto timed = [&](double &acc, auto &&fn) {
+            MID_CHECK(mid_timer_tick(tm, nullptr));
+            fn();
+            MID_CHECK(mid_timer_tock(tm, nullptr));
+            float ms = 0;
+            MID_CHECK(mid_timer_ms(tm, &ms));
+            acc += ms;
+        };
+        std::cout << "\tperforming computations\n";
+        struct Dev { mid_ctx *c; std::vector<void *> p; ~Dev() { for (auto q : p) if (q) (void)mid_free(c, q); } } dev{ctx, {}};
+        auto dalloc = [&](size_t bytes) { void *d = nullptr; MID_CHECK(mid_alloc(ctx, bytes, &d)); dev.p.push_back(d); return d; };
+        void *dIn = dalloc(target.size()), *dOut = dalloc(out_bytes);
+        std::vector<const uint32_t *> dLayers;
+        for (int i = 0; i < L; ++i) dLayers.push_back((const uint32_t *)dalloc(layerImgs[i].size()));
+        timed(m_transferMs, [&] {
+            MID_CHECK(mid_memcpy_h2d(ctx, dIn, target.data(), target.size(), nullptr));
+            for (int i = 0; i < L; ++i) MID_CHECK(mid_memcpy_h2d(ctx, (void *)dLayers[i], layerImgs[i].data(), layerImgs[i].size(), nullptr));
+        });
+        timed(m_execMs, [&] { MID_CHECK(mid_median_filter(ctx, &p, L ? sigma.data() : nullptr, dIn, L ? dLayers.data() : nullptr, L, dOut, out_fmt, nullptr)); });
+        std::cout << "\tgetting image back\n";
+        timed(m_transferMs, [&] { MID_CHECK(mid_memcpy_d2h(ctx, result.data(), dOut, out_bytes, nullptr)); });
+        MID_CHECK(mid_stream_sync(ctx, nullptr));
+        const std::string name = std::string("output-nonlinear-median") + (hdr ? ".exr" : ".png");
+        MID_CHECK(mid_image_save(out_path(name).c_str(), result.data(), w, h, out_fmt));
+        std::cout << "\tcleaning up\n";
+    }
+
     // Animation mode (BASELINE config 5; not in the reference, which filters one target per run): every
     // sibling frame of the target is denoised with temporal NLM over frames t-k..t+k.  Frames are split
     // into contiguous blocks, one per device; each device streams its block plus k halo frames on either
@@ -662,7 +735,8 @@ public:
         const AnimationFilter &af = *animation_filter(opt.animation_filter);        // (main has refused unknown names)
         const int n = (int)frameNames.size(), k = !af.temporal ? 0 : opt.temporal_k < 0 ? 2 : opt.temporal_k;
         const bool guided = af.family == SEQ_GUIDED;
-        const bool use_layers = af.layers || (guided && !opt.guide_layer.empty()), nlm_guides = af.family == SEQ_NLM_LAYERS || af.family == SEQ_NLM_LAYERS_TEMPORAL || af.family == SEQ_NLM_JOINT;
+        const bool median = af.family == SEQ_MEDIAN;
+        const bool use_layers = (af.layers && !(median && opt.median_plain)) || (guided && !opt.guide_layer.empty()), nlm_guides = af.family == SEQ_NLM_LAYERS || af.family == SEQ_NLM_LAYERS_TEMPORAL || af.family == SEQ_NLM_JOINT;
         if (!af.windowed() && opt.halo_rccl)
             throw std::runtime_error("--halo rccl is not available with --animation-filter " + opt.animation_filter +
                                      ": its frames read no other frame, there is no halo to exchange");
@@ -722,7 +796,7 @@ public:
         allLayers.insert(allLayers.end(), albedoNames.begin(), albedoNames.end());      // (the albedo planes obey the layers' one-format rule)
         if (nlm_guides) for (const std::string &ln : allLayers) if (is_hdr(ln)) (void)load(ln, true);   // refuses, saying why
         const int lfmt = layer_format(allLayers);
-        const std::vector<float> jointSigma = af.family == SEQ_BILATERAL_JOINT || af.family == SEQ_ATROUS || af.family == SEQ_ATROUS_TEMPORAL || af.family == SEQ_ATROUS_VARIANCE || recursive ? layer_sigmas(frameLayers[0])            // (every frame has frame 0's layers)
+        const std::vector<float> jointSigma = median && !use_layers ? std::vector<float>() : median || af.family == SEQ_BILATERAL_JOINT || af.family == SEQ_ATROUS || af.family == SEQ_ATROUS_TEMPORAL || af.family == SEQ_ATROUS_VARIANCE || recursive ? layer_sigmas(frameLayers[0])            // (every frame has frame 0's layers)
                                               : af.family == SEQ_NLM_JOINT ? layer_sigmas(frameLayers[0], true) : std::vector<float>();
         std::cout << "\tloading " << n << " frames\n";
         // Frames are decoded STRAIGHT INTO pinned host memory (mid_image_load_pinned) and the results land in pinned
@@ -835,6 +909,7 @@ public:
             std::cout << "\tfirefly radius " << opt.firefly_radius << " rank " << opt.firefly_rank << " gain " << opt.firefly_gain << " floor " << opt.firefly_floor << "\n";
         if (guided)
             std::cout << "\tguided guide " << (use_layers ? frameLayers[0][0] : std::string("self")) << " radius " << opt.guided_radius << " eps " << opt.guided_eps << "\n";
+        if (median) std::cout << "\tmedian radius " << opt.median_radius << " layers " << L << "\n";
         if (opt.history_clip) std::cout << "\thistory-clip radius " << opt.history_clip_radius << " gamma " << opt.history_clip_gamma << "\n";
         std::vector<const void *> motion_ptrs(motionPlanes.size());
         for (size_t i = 0; i < motionPlanes.size(); ++i) motion_ptrs[i] = motionPlanes[i].data();
@@ -918,6 +993,10 @@ public:
             case SEQ_GUIDED: {             // the local linear fit to the guide plane (or to the frame itself), every frame alone
                 const mid_guided_params gp{bpp.width, bpp.height, opt.guided_radius, opt.guided_eps, bpp.format};
                 MID_CHECK(mid_sequence_guided(c, &gp, frames, nf, lp, start, count, outs, out_fmt, 1, t)); break;
+            }
+            case SEQ_MEDIAN: {             // the median of every frame alone, plain or weighted by the frame's layers
+                const mid_median_params mp{bpp.width, bpp.height, opt.median_radius, bpp.format};
+                MID_CHECK(mid_sequence_median(c, &mp, lp ? jointSigma.data() : nullptr, frames, nf, lp, lp ? L : 0, start, count, outs, out_fmt, 1, t)); break;
             }
             case SEQ_NLM_JOINT:            // one patch weight from all layers (jointSigma: the h of each layer)
                 MID_CHECK(mid_sequence_nlm_joint(c, &np, jointSigma.data(), frames, nf, lp, L, kk, start, count, outs, out_fmt, 1, t)); break;
@@ -1246,6 +1325,9 @@ static void usage()
         "                            luminance term per pixel (wide where the image is noisy, narrow where it has converged) and is\n"
         "                            filtered along with the colour (--passes, --sigma-layers, --atrous-sigma-lum, --atrous-epsilon;\n"
         "                            the layer rules of atrous), output output-nonlinear-atrous-variance.{png,exr};\n"
+        "                            and median (not part of all): the median of the (2 R + 1)^2 window per channel, weighted by the frame's\n"
+        "                            layers or plain (--median-radius, --median-plain), output output-nonlinear-median.{png,exr}; texels\n"
+        "                            that are not finite take no part, so a NaN pixel is repaired from its neighbours\n"
         "                            and guided (not part of all): the guided filter -- inside every (2 R + 1)^2 window the image is fitted\n"
         "                            as an affine function of the guide's colour and the averaged fit is evaluated at the pixel's own guide\n"
         "                            texel, so the guide's edges and texture are reproduced and the cost does not depend on R\n"
@@ -1272,6 +1354,9 @@ static void usage()
         "                            the pixel's luminance (default 4; 0: no luminance term)\n"
         "  --atrous-epsilon X        atrous-variance: added to X * sqrt(variance), so that a converged pixel (variance 0) still averages\n"
         "                            texels that differ by rounding alone (default 1e-3, for luminances of order 1; > 0)\n"
+        "  --median-radius R         median (--modes median, --animation-filter median): window radius, 1..3 (default 1): 9, 25 or 49 taps\n"
+        "  --median-plain            median: load no layers, the plain median; otherwise the frame's RenderElements layers weigh the taps as\n"
+        "                            for atrous (--sigma-layers, else --sigma-c).  The run prints `median radius <r> layers <n>`\n"
         "  --guided-radius R         guided (--modes guided, --animation-filter guided): window radius, 1..16 (default 8)\n"
         "  --guided-eps X            guided: the regulariser, finite and > 0, in squared units of the guide (default 0.01): windows whose\n"
         "                            guide varies by much less than sqrt(X) are averaged, windows that vary by more carry the guide's edge\n"
@@ -1356,6 +1441,8 @@ static void usage()
         "                            it ignores --temporal-k; not with --halo rccl), outputs output-animation-nonlinear-atrous-recursive-*.\n"
         "                            With --gpus N every frame block starts its history --warmup frames before its block: a sharded\n"
         "                            run equals the unsharded one bit for bit only when the warm-up reaches frame 0;\n"
+        "                            or median: the median of every frame alone, weighted by its own layers or plain (--median-radius,\n"
+        "                            --median-plain), output-animation-nonlinear-median-*\n"
         "                            or guided: the guided filter of every frame alone, guided by the one render element of each frame\n"
         "                            that --guide-layer names, or by the frame itself (--guided-radius, --guided-eps; it ignores\n"
         "                            --temporal-k, frame blocks have no halo, not with --halo rccl), outputs\n"
@@ -1429,6 +1516,12 @@ int main(int argc, char **argv)
             if (!opt.guided_other) opt.guided_other = "--guided-eps";
             if (!(std::isfinite(opt.guided_eps) && opt.guided_eps > 0.f)) { std::cerr << "--guided-eps " << opt.guided_eps << " must be finite and > 0\n"; return EXIT_FAILURE; }
         }
+        else if (a == "--median-radius") {
+            opt.median_radius = atoi(next());
+            if (!opt.median_other) opt.median_other = "--median-radius";
+            if (opt.median_radius < 1 || opt.median_radius > 3) { std::cerr << "--median-radius " << opt.median_radius << " is outside 1..3\n"; return EXIT_FAILURE; }
+        }
+        else if (a == "--median-plain") { opt.median_plain = true; if (!opt.median_other) opt.median_other = "--median-plain"; }
         else if (a == "--guide-layer") { opt.guide_layer = next(); if (!opt.guided_other) opt.guided_other = "--guide-layer"; }
         else if (a == "--gpu-only") opt.run_cpu = false;
         else if (a == "--cpu-only") opt.run_gpu = false;
@@ -1556,6 +1649,10 @@ int main(int argc, char **argv)
         std::cerr << opt.guided_other << " applies to --modes guided and --animation --animation-filter guided only\n";
         return EXIT_FAILURE;
     }
+    if (opt.median_other && !(opt.animation ? opt.animation_filter == "median" : listed("median"))) {
+        std::cerr << opt.median_other << " applies to --modes median and --animation --animation-filter median only\n";
+        return EXIT_FAILURE;
+    }
     if (opt.compare_other && !opt.compare) { std::cerr << opt.compare_other << " applies to --compare only\n"; return EXIT_FAILURE; }
     if (opt.compare) {
         const char *with = modes_given ? "--modes" : filter_given ? "--animation-filter" : gpus_given ? "--gpus" : nullptr;
@@ -1579,7 +1676,9 @@ int main(int argc, char **argv)
         if (!opt.animation && opt.animation_filter != "nlm") { std::cerr << "--animation-filter needs --animation\n"; return EXIT_FAILURE; }
         if (opt.animation) {
             std::cout << "######\nRunning on GPU (animation, " << animation_filter(opt.animation_filter)->banner << ")\n######\n";
-            app.RunAnimation();
+            // (a failed animation run names its filter on stderr; the message itself goes where every mode's goes, below)
+            try { app.RunAnimation(); }
+            catch (const std::exception &) { std::cout.flush(); std::cerr << "--animation --animation-filter " << opt.animation_filter << " failed:\n"; throw; }
             print_time();
             return EXIT_SUCCESS;
         }
@@ -1596,6 +1695,7 @@ int main(int argc, char **argv)
             if (listed("nlm-joint")) { std::cout << "######\nRunning on GPU (joint nonlocal)\n######\n"; app.RunOnGPU(true, true, false, false, true, true); print_time(); }
             if (listed("atrous")) { std::cout << "######\nRunning on GPU (a-trous + layers)\n######\n"; app.RunOnGPU(false, true, false, false, true, true, 1); print_time(); }
             if (listed("guided")) { std::cout << "######\nRunning on GPU (guided filter)\n######\n"; app.RunGuided(); print_time(); }
+            if (listed("median")) { std::cout << "######\nRunning on GPU (median)\n######\n"; app.RunMedian(); print_time(); }
             if (listed("atrous-variance")) { std::cout << "######\nRunning on GPU (a-trous + layers, variance-guided)\n######\n"; app.RunOnGPU(false, true, false, false, true, true, 2); print_time(); }
         }
         if (opt.run_cpu) {

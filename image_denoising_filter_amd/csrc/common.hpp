@@ -307,6 +307,13 @@ int guided_out(mid_ctx *ctx, const mid_guided_params *p, const void *in, const v
 int guided_check(const mid_guided_params *p, const char *who);
 size_t guided_work_bytes(const mid_guided_params *p);
 
+// mid_median_filter without its pointer checks (the caller has made them), one launch on `s`: median.hip; used by the frame pipeline
+// (mid_sequence_median), not exported.  median_check: the size, radius and format word, n_layers in 0..16, and with layers both tables
+// and every sigma finite and > 0 (without: both tables NULL and no guide field).
+int median_out(mid_ctx *ctx, const mid_median_params *p, const float *layer_sigma, const void *in, const uint32_t *const *layers, int n_layers,
+               void *out, int out_fmt, hipStream_t s);
+int median_check(const mid_median_params *p, const char *who, const float *layer_sigma, bool have_layers, int n_layers);
+
 // ROCTx ranges (csrc/markers.cpp): no-ops unless the process already holds a ROCTx (rocprofv3 --marker-trace preloads one).
 bool markers_active();
 void range_push(const char *name);

@@ -641,6 +641,29 @@ extern "C" int mid_sequence_guided(mid_ctx *ctx, const mid_guided_params *p, con
     return run_pipeline(ctx, st, launch, host_frames, n_frames, 0, first, count, host_out, out_format, overlap, timings_ms);
 }
 
+// The median of every frame (section a4p): mid_sequence_atrous_joint's schedule at k = 0 with median_out as the compute stage and no
+// levels.  host_layers == NULL (with n_layers == 0) is the plain form: nothing is uploaded beside the frames.
+extern "C" int mid_sequence_median(mid_ctx *ctx, const mid_median_params *p, const float *layer_sigma, const void *const *host_frames,
+                                   int n_frames, const void *const *host_layers, int n_layers, int first, int count, void *const *host_out,
+                                   int out_format, int overlap, float *timings_ms)
+{
+    Bind b(ctx, nullptr);
+    if (b.rc) return b.rc;
+    const char *who = "sequence_median";
+    if (int rc = refuse_if_recording(ctx->compute, "mid_sequence_median (four streams, host-side waits)")) return rc;
+    if (int rc = median_check(p, who, layer_sigma, host_layers != nullptr, n_layers)) return rc;
+    if (int rc = check_sequence({who, "n_frames", true, true}, host_frames, n_frames, host_layers, n_layers, 0, first, count, host_out, out_format)) return rc;
+    const size_t npix = (size_t)p->width * p->height;
+    const Stage st{who, p->width, p->height, fmt_frames(p->format), npix * fmt_bytes(fmt_guide(p->format)), host_layers, n_layers, true, "median %d"};
+    auto launch = [&](const void *const *tbl, int, const uint32_t *const *lt, int, int t0, int bn, void *const *out, int out_fmt, hipStream_t s) {
+        for (int i = 0; i < bn; ++i)              // (k = 0: output t0 + i reads slot t0 + i and its layers only)
+            if (int rc = median_out(ctx, p, layer_sigma, tbl[t0 + i], n_layers ? lt + (size_t)(t0 + i) * n_layers : nullptr, n_layers, out[i], out_fmt, s))
+                return rc;
+        return (int)MID_OK;
+    };
+    return run_pipeline(ctx, st, launch, host_frames, n_frames, 0, first, count, host_out, out_format, overlap, timings_ms);
+}
+
 // The a-trous filter over neighbouring frames: mid_sequence_atrous_joint with a window -- mid_sequence_bilateral_joint's schedule
 // and layer ring at k, the launch callable of sequence_bilateral_temporal's window tables, the levels of the call above.
 extern "C" int mid_sequence_atrous_joint_temporal(mid_ctx *ctx, const mid_atrous_params *p, const float *layer_sigma,

@@ -1179,6 +1179,76 @@ int mid_sequence_guided(mid_ctx *ctx, const mid_guided_params *p, const void *co
                         const void *const *host_guides /* one plane per frame, or NULL */, int first, int count,
                         void *const *host_out, int out_format, int overlap, float *timings_ms);
 
+/* ---- a4p: the median and the layer-weighted median ------------------------------------------------
+ * Every filter above is a weighted mean or a local linear fit: one texel of value 50 inside a 5 x 5 window moves it by 2 however
+ * the weights fall.  The median is a SELECTION -- the output is one of the inputs -- and ignores outliers of either sign: dark
+ * dropouts, salt-and-pepper noise, dead texels, a NaN.  Its guide-aware form is the weighted median under the per-tap layer weights
+ * of the joint filters: the render layers decide which taps belong to the pixel's surface, the median is robust within that set.
+ * C(q) is the widened texel of `in` (widened as a4i widens a frame), p the output pixel, the taps q the window |i|, |j| <= radius
+ * around p, cut at the image.
+ * Weight of a tap.  n_layers == 0, the plain median: w(q) = 1.  Otherwise w(q) = 2^arg, arg the FMA chain of a4g without its colour
+ * term and without K(o): it starts at 0, arg = fma(-d, d, arg) with d = G_l(p) sc_l - G_l(q) sc_l for layer 0's x, y, z, then layer
+ * 1's, ...; sc_l as in a4e, a guide value entering as the fp32 product g * sc_l.  There is no spatial term.  A weight that is not
+ * finite (a NaN or Inf guide texel at p or q) is 0, and so is a weight below the fp32 normal range (arg < -126, in fp32 as computed).
+ * The guide's alpha is ignored.  The centre is a tap like any other; its weight is
+ * 1 when its guide texels are finite.
+ * Per channel c of r, g, b:  V_c = the taps with C_c(q) finite and w(q) > 0;  W_c = sum_{V_c} w;
+ *   S_c(v) = sum_{q in V_c, C_c(q) <= v} w(q);       out_c = min { C_c(q) : q in V_c, 2 S_c(C_c(q)) >= W_c }
+ * -- the lower weighted median, the usual median when the weights are 1 and the count is odd.  V_c empty: out_c = C_c(p) unchanged.
+ * out.a = in.a.  So a NaN centre with valid neighbours is repaired, a NaN neighbour takes no part, and a frame with nothing valid
+ * comes back as it went in.  `out` is stored in out_format by a4g's output rule.  Where +0 and -0 both qualify either may come back.
+ * Arithmetic.  The sums are fp32.  A tap's place in a sum is its place in the window (rows top to bottom, a row left to right); a
+ * tap that takes no part adds an exact 0: the order depends on the inputs and the parameters alone -- no atomics, the same bits on
+ * every call, stream and kernel class.  When every weight of a window is exactly 0 or 1 every sum is an integer <= 49, exact in
+ * fp32, and the output is determined exactly: the plain form, and a weighted window whose guide differences are either 0 or so large
+ * that 2^arg underflows to 0, are bit for bit the answer of integer arithmetic.
+ * Precision otherwise.  Let L' be the number of layers whose differences are not all 0 in the window and A the largest |arg| among
+ * the taps with w > 2^-24 W (A < 30 always: 2^-24 W <= 49 * 2^-24).  A term d^2 carries the subtraction's rounding, 2^-23 relative;
+ * each of the 3 L' FMAs rounds once, at most 2^-24 of the partial sum, which never exceeds |arg|: the chain is within
+ * (3 L' + 2) * 2^-24 * A of its float64 value on the scaled guide values, which is (3 L' + 2) * 2^-24 * A * ln 2 relative on w.
+ * v_exp_f32 is good to one unit, 2^-23 relative, and up to 49 fp32 additions of non-negative terms add 49 * 2^-24 relative on a sum:
+ *     |S_fp32 / S_float64 - 1| <= ((3 L' + 2) * A * ln 2 + 51) * 2^-24   <=   delta = 2^-16    while (3 L' + 2) * A <= 295.
+ * (One layer: every A; three layers: A <= 26.8; sixteen live layers: A <= 5.9.)  Under it the output is a valid tap
+ * value v whose float64 sums satisfy S_<(v) <= (1/2 + delta) W and S_<=(v) >= (1/2 - delta) W, and where the float64 margin
+ * min(S_<=(v*) - W/2, W/2 - S_<(v*)) / W of the exact answer v* exceeds delta the output is v* bit for bit.
+ * Bit identities: an RGBA8 / RGBA16F frame or guide gives the bits of the widened call (a4g's wording); n_layers == 0 gives the bits
+ * of any number of all-zero layers with any sigmas; one live layer among zero layers gives the bits of that layer alone; in * 2^k
+ * gives out * 2^k while nothing overflows or goes subnormal; the plain median of a frame flipped or transposed is the flipped or
+ * transposed output; every kernel class gives the same bits.
+ * Classes (csrc/median.hip; lanes along x, no scratch memory, no atomics; tiles dealt to at most 4 workgroups per CU):
+ *   n_layers  radius  kernel            tile     LDS tile  LDS bytes (n_layers 0 .. 4)
+ *   0 .. 4    1       tiled             64 x 16  66 x 18   14260, 28516, 42772, 57028, 71284
+ *   0 .. 4    2       tiled             64 x 16  68 x 20   16324, 32644, 48964, 65284, 81604
+ *   0 .. 4    3       tiled             64 x 16  70 x 22   18484, 36964, 55444, 73924, 92404
+ *   0         1 .. 3  plain selection   a tile of the tiled class whose every texel is inside the image with finite r, g, b (a vote
+ *                                       of the workgroup): the taps go through a min / max / median-of-three selection network, the
+ *                                       9-input median network at radius 1, forgetful selection over 25 and 49 inputs at radius 2, 3
+ *   5 .. 16   1 .. 3  global            64 x 4   -         0
+ * tiled: the colour as three float planes (NaN outside the image, so "outside" and "not valid" are one case) and three scaled planes
+ * per layer, decoded from the guide format at the fill (csrc/median_tile.hpp); the weights of a pixel are computed once, and per
+ * channel the window's values and weights sit in registers while every candidate's rank is counted.  global: one pixel per lane,
+ * the taps read from global memory.
+ * MID_ERR_INVALID before anything is queued, `out` untouched: a NULL p, in or out; radius outside 1..3; n_layers outside 0..16; a
+ * layer table or sigma table that is NULL with n_layers > 0 or non-NULL with n_layers == 0; a NULL layer; a sigma that is not finite
+ * and > 0; a non-zero guide field with n_layers == 0; an unknown frame, guide or output format, or bits above 15; in, a layer or out
+ * not aligned to its texel size; out overlapping in or a layer in any way (the filter is a stencil); width or height < 1, or 2^30
+ * pixels and more. */
+typedef struct mid_median_params {
+    int32_t width, height;
+    int32_t radius;   /* 1..3: (2 radius + 1)^2 = 9, 25, 49 taps, cut at the image */
+    int32_t format;   /* MID_FMT_* of `in`; guide format through MID_FMT_WITH_GUIDE as in a4e */
+} mid_median_params;
+int mid_median_filter(mid_ctx *ctx, const mid_median_params *p, const float *layer_sigma /* n_layers host floats, NULL iff n_layers == 0 */,
+                      const void *in, const uint32_t *const *layers /* n_layers device ptrs, NULL iff n_layers == 0 */, int n_layers,
+                      void *out, int out_format, void *stream);
+/* mid_sequence_atrous_joint (section a4g) with mid_median_filter as the compute stage, k = 0 and no levels: host frames and host
+ * layers in, host frames out, output t with the bits of mid_median_filter on frame t.  host_layers == NULL with n_layers == 0 is
+ * the plain form (nothing is uploaded beside the frames).  Launch range "median t".  The refusals above and those of
+ * mid_sequence_atrous_joint, which leave host_out and timings_ms untouched. */
+int mid_sequence_median(mid_ctx *ctx, const mid_median_params *p, const float *layer_sigma, const void *const *host_frames, int n_frames,
+                        const void *const *host_layers, int n_layers, int first, int count, void *const *host_out, int out_format,
+                        int overlap, float *timings_ms);
+
 /* ---- a5: normalize ----------------------------------------------------------------------
  * One dispatch of shaders/normalize.comp (RecordCommandsOfExecuteAndTransfer(normKernel=true)):
  * out = weightColor / normWeight, or (1,0,1,1) where normWeight == 0; bindings {0: out; 1: W}. */

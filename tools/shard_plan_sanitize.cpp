@@ -46,6 +46,8 @@ int mid::color_bounds_check(const mid_color_bounds_params *, const char *) { ret
 int mid::guided_out(mid_ctx *, const mid_guided_params *, const void *, const void *, void *, void *, int, hipStream_t) { return MID_ERR_UNSUPPORTED; }   // (guided.hip)
 int mid::guided_check(const mid_guided_params *, const char *) { return MID_ERR_UNSUPPORTED; }   // (guided.hip)
 size_t mid::guided_work_bytes(const mid_guided_params *) { return 0; }   // (guided.hip)
+int mid::median_out(mid_ctx *, const mid_median_params *, const float *, const void *, const uint32_t *const *, int, void *, int, hipStream_t) { return MID_ERR_UNSUPPORTED; }   // (median.hip)
+int mid::median_check(const mid_median_params *, const char *, const float *, bool, int) { return MID_ERR_UNSUPPORTED; }   // (median.hip)
 int mid::nlm_check_params(const mid_nlm_params *) { return MID_ERR_UNSUPPORTED; }   // (nlm.hip)
 int mid::bilateral_check_params(const mid_bilateral_params *, const char *, bool) { return MID_ERR_UNSUPPORTED; }   // (bilateral.hip)
 
